@@ -6,7 +6,19 @@ One "step" = one frame through MythTracer::RayTrace's pixel loop on the GPU
 and sensor are resident in HBM before the timed region; the frame stays in HBM
 (the PCIe-inclusive rate is in DESIGN.md).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: it sets up, warms up, counts
+the rays of the timed frames in an untimed pass, times the K steps and prints
+the result line.  --full adds everything else: the counting pass over every
+timed frame with crop checks against the oracle, the last frame's SHA-256
+against the reference's, the roofline block, the untimed extras (drop-in
+caller, cold frame, same-frame regime, reference-work counts) and the CPU
+baseline.  --dump-outputs DIR writes the frame of the last timed step as
+DIR/frame.npy (float32, H x W x 3); a frame above 64 MB as float32 is written as
+a fixed, seeded sample of its pixels instead (frame_sample.npy, N x 3, and
+frame_sample_pixel.npy, the pixels' row-major indices).  git ignores
+bench_outputs/, the directory meant for these files.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py starts its own
 ranks: the parent -- before it imports torch or touches HIP -- runs
@@ -41,16 +53,18 @@ Regime of the timed steps (--regime):
           the golden camera (yaw0 + 0, 2, .. 8, 6, .. -8, -6, .. 0, ...), so that
           the workload stays the frame BASELINE.json names whatever K is (a
           monotonic 256-degree turn averages over easier views: 3.6 ms per
-          frame), and ends ON the golden camera: the last timed frame's SHA-256
-          is compared with the frame the compiled reference rendered.  Ray
-          counts come from an untimed pass over the same K frames with the work
-          counters on, in which a dozen frames are also crop-checked against the
-          oracle.
+          frame), and ends ON the golden camera: with --full the last timed
+          frame's SHA-256 is compared with the frame the compiled reference
+          rendered.  Ray counts come from an untimed pass with the work counters
+          on: a frame's ray counts depend on its camera alone, so a plain run
+          renders each distinct camera of the K frames once and weighs it by how
+          often it comes; --full renders all K frames and crop-checks a dozen of
+          them against the oracle.
   warm    every step re-renders the golden camera's frame (round 1/2's headline;
-          reported as extras.warm_same_frame in the default run).
+          reported as extras.warm_same_frame in the --full run).
 
-Rank 0 prints ONE JSON line; the process exits non-zero if a frame does not
-match the reference's.
+Rank 0 prints ONE JSON line; with --full the process exits non-zero if a frame
+does not match the reference's.
 """
 from __future__ import annotations
 
@@ -90,6 +104,30 @@ def reference_bytes(c: dict, pixels: int) -> int:
     Möller–Trumbore test, vertices+normals+material per shaded hit, 3 B/pixel."""
     return (48 * c["box_tests"] + 48 * c["tri_tests"] + 72 * c["mt_tests"] +
             (72 + 72 + 136) * c["shaded_hits"] + 3 * pixels)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240611
+
+
+def write_outputs(out_dir: str, frame) -> list:
+    """--dump-outputs: the frame (H x W x 3, uint8) as float32 .npy files in out_dir.  A frame above
+    DUMP_LIMIT_BYTES as float32 (3840x2160 and up) is written as a fixed, seeded sample of its pixels:
+    frame_sample.npy (N x 3) and frame_sample_pixel.npy (N, the pixels' row-major indices, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.asarray(frame)
+    H, W = frame.shape[:2]
+    if frame.size * 4 <= DUMP_LIMIT_BYTES:
+        files = {"frame": frame.astype(np.float32)}
+    else:
+        n = min(H * W, DUMP_LIMIT_BYTES // 2 // (3 * 4 + 8))
+        pix = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=n, replace=False))
+        files = {"frame_sample": frame.reshape(H * W, -1)[pix].astype(np.float32),
+                 "frame_sample_pixel": pix.astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
 
 
 def cpu_baseline(scene_obj, cam, lights, W, H, chunk, max_depth, rays_in_chunk):
@@ -148,13 +186,20 @@ def main():
     ap.add_argument("--ownership", choices=("dealt", "modular"), default="dealt",
                     help="N > 1: tiles dealt out by the previous frame's costs (default) or k = rank (mod N)")
     ap.add_argument("--engine", type=int, default=0, help="0 automatic (default), 1 state machine, 2 ray pool, 3 hybrid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", choices=("full", "band"), default="full",
-                    help="reference timed on the whole frame (about 30 s) or on a quarter-frame band")
+                    help="--full: reference timed on the whole frame (about 30 s) or on a quarter-frame band")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extras (cold frame, same-frame regime, reference-work counts, crop checks)")
-    ap.add_argument("--crop-checks", type=int, default=12, help="frames of the counting pass checked on a crop against the oracle")
+                    help="--full: skip the untimed extras (cold frame, same-frame regime, reference-work counts, crop checks)")
+    ap.add_argument("--crop-checks", type=int, default=12,
+                    help="--full: frames of the counting pass checked on a crop against the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks against the reference and oracle, the roofline, the untimed extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR as .npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))  # before anything imports torch / touches the GPU
@@ -367,8 +412,8 @@ def main():
         return sha, ("MISMATCH vs golden frame" if bad else text), bad
 
     mismatch = False
-    # ---- 1. warm-up and the COUNTING pass (untimed, work counters on): the rays of every timed frame, and a
-    # dozen of the frames checked on a crop against the oracle
+    # ---- 1. warm-up and the COUNTING pass (untimed, work counters on): the rays of every timed frame, and with
+    # --full a dozen of the frames checked on a crop against the oracle
     for s12 in sens_warm:
         step(s12)
     fence()
@@ -377,25 +422,37 @@ def main():
             "tri_tests", "mt_tests", "shaded_hits", "wave_node_steps", "wave_tri_steps",
             "bytes_scalar", "bytes_vector"]
     tot = {k: 0 for k in keys}
-    last_counters = None
     orc = None
     crops_ok, crops_n = True, 0
-    n_checks = 0 if (args.no_extras or rank != 0 or args.regime != "moving") else min(args.crop_checks, K)
+    n_checks = 0 if (not args.full or args.no_extras or rank != 0 or args.regime != "moving") else min(args.crop_checks, K)
     check_at = set(int(round(j * (K - 1) / max(n_checks - 1, 1))) for j in range(n_checks))
     if n_checks:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import orclib
         orc = orclib.OracleScene(info["obj"])
         orc.set_lights(lights)
+    # the frames the counting pass renders, each with its weight: --full renders every timed frame once; a plain run
+    # renders each distinct camera of the timed frames once, weighed by how often it comes (a frame's ray counts
+    # depend on its camera alone; the counts that depend on the schedule -- boxes, nodes, bytes -- are reported by
+    # --full only)
+    cam_key = lambda i: np.asarray(sens_timed[i], dtype=np.float64).tobytes()
+    if args.full:
+        count_at = [(i, 1) for i in range(K)]
+    else:
+        frames_of = {}
+        for i in range(K):
+            frames_of.setdefault(cam_key(i), []).append(i)
+        count_at = [(f[0], len(f)) for f in frames_of.values()]
+    counters_of = {}
     elapsed_counting = 0.0
-    for i in range(K):
+    for i, weight in count_at:
         t1 = time.perf_counter()
         step(sens_timed[i])
         torch.cuda.synchronize()
         elapsed_counting += time.perf_counter() - t1
-        last_counters = abi.read_stats(h)  # this rank, this frame
+        counters_of[cam_key(i)] = abi.read_stats(h)  # this rank, this frame
         for k in keys:
-            tot[k] += last_counters[k]
+            tot[k] += weight * counters_of[cam_key(i)][k]
         if i in check_at:
             cw, ch = 96, 48
             cx, cy = (211 * i) % (W - cw), (H // 3 + 37 * i) % (H - ch)
@@ -403,7 +460,8 @@ def main():
             got = frame[cy:cy + ch, cx:cx + cw].cpu().numpy()
             crops_ok = crops_ok and bool(np.array_equal(got, want))
             crops_n += 1
-    elapsed_counting /= max(K, 1)
+    elapsed_counting /= len(count_at)
+    last_counters = counters_of[cam_key(K - 1)]  # the last timed frame's camera
     mismatch = mismatch or not crops_ok
     abi.kernel_times(h)
     # ---- 2. the TIMED steps: the kernels built without the work counters (mt_scene_set_stats: counting costs
@@ -420,10 +478,12 @@ def main():
         step(sens_timed[i], i)
     fence()
     elapsed = time.perf_counter() - t0
-    # the frame the LAST timed step wrote (the golden camera, counter-free kernels): hashed before anything
-    # else renders into `frame`
+    # the frame the LAST timed step wrote (the golden camera, counter-free kernels): written out and hashed before
+    # anything else renders into `frame`
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, frame.cpu().numpy())
     sha_timed, parity_timed, bad = (None, None, False)
-    if rank == 0:
+    if rank == 0 and args.full:
         sha_timed, parity_timed, bad = verdict(frame)
     mismatch = mismatch or bad
     # per-kernel device durations of the timed steps: HIP events the library
@@ -451,7 +511,7 @@ def main():
     if rank == 0:
         k_ms, k_order_ms, k_step_ms, k_exchange_ms = (float(x) for x in kmax.tolist())
         roof = None
-        if world == 1:
+        if world == 1 and args.full:
             # ---- roofline of the dominant kernel (the frame kernel).  What binds it is VALU instruction issue (no
             # contraction -> no MFMA; 33 MB working set -> caches, not HBM): `achieved` = SIMD cycles per second in
             # which a VALU instruction issues = VALU-busy cycles per launch (rocprofv3 PMC pass, stamped with the
@@ -519,14 +579,17 @@ def main():
                        "regime": ("moving camera: yaw changes by 2 degrees per step as in the reference's loop (main_local.cc:51-76), "
                                   "panning within +-8 degrees of the golden camera; every step is a NEW frame scheduled from the "
                                   "previous frame's block costs re-projected through the camera change; the last step is the "
-                                  "golden camera (extras.warm_same_frame / cold_frame_ms give the other regimes)") if args.regime == "moving" else
+                                  "golden camera (extras.warm_same_frame / cold_frame_ms of --full give the other regimes)") if args.regime == "moving" else
                                  "warm: every timed step re-renders the golden camera's frame, scheduled from its own measured block costs",
                        "engine": {0: "automatic", 1: "state machine", 2: "ray pool", 3: "hybrid"}[args.engine],
                        "scene_sha256": info["sha256"]},
             "frame_ms_wall": elapsed / max(K, 1) * 1e3,
             "frame_ms_wall_with_work_counters_and_a_sync_per_frame": elapsed_counting * 1e3,
-            "work_counters": "off in the timed steps (mt_scene_set_stats(scene, 0)); ray counts and requested bytes "
-                             "are those of an untimed pass over the SAME K frames rendered with the counters on",
+            "work_counters": "off in the timed steps (mt_scene_set_stats(scene, 0)); " + (
+                             "ray counts and requested bytes are those of an untimed pass over the SAME K frames rendered "
+                             "with the counters on" if args.full else
+                             "ray counts are those of an untimed pass over the distinct cameras of the SAME K frames "
+                             "rendered with the counters on, each weighed by the number of its frames"),
             "render_ms_device": k_step_ms,
             "rays_per_frame_mean": {k: per_frame[k] for k in RAY_KEYS},
             "rays_last_frame": {k: last_counters[k] for k in RAY_KEYS} if world == 1 else None,
@@ -543,9 +606,13 @@ def main():
             out["exchange_ms_device"] = {"gather_plus_blit_rank0_plus_cost_map_all_reduce": k_exchange_ms,
                                          "bytes_gathered": int(n_max * tiling.slot_bytes(tw, th) * world),
                                          "cost_map_bytes_all_reduced": int(map_w * map_h * 4) if exchange_costs else 0}
+        if not args.full:  # measured or checked by --full only
+            for k in ("frame_ms_wall_with_work_counters_and_a_sync_per_frame", "frame_sha256", "parity", "parity_scope",
+                      "roofline"):
+                del out[k]
 
     # ---- untimed extras, one GPU only
-    if world == 1 and rank == 0 and not args.no_extras:
+    if world == 1 and rank == 0 and args.full and not args.no_extras:
         extras = {}
         scratch = torch.zeros_like(frame)
         sp = ctypes.c_void_p(scratch.data_ptr())

@@ -377,7 +377,7 @@ def main():
             big_frames(td)
 
 
-if __name__ == "__main__" and "--depth4" not in sys.argv:
+if __name__ == "__main__" and "--depth4" not in sys.argv and "--live" not in sys.argv:
     main()
 
 
@@ -407,3 +407,20 @@ def depth4_frames():
 
 if "--depth4" in sys.argv and __name__ == "__main__":
     depth4_frames()
+
+
+LIVE_CAM = (120.0, 90.0, 60.0, 5.0, 20.0, -3.0, 100.0)
+
+
+def live_case():
+    """The case of tests/test_oracle_golden.py::test_live_reference_agrees (mini scene, a camera and two lights no
+    other fixture uses), stored so that the test runs without the compiled reference:
+        python tests/golden/make_golden.py --live"""
+    assert orclib.have_ref(), "build the reference first: make -C oracle ref"
+    with tempfile.TemporaryDirectory() as td:
+        mini = scenegen.write_scene("mini", os.path.join(td, "scenes"))
+        render_case(td, "mini_live_200x120", mini["obj"], 200, 120, LIVE_CAM, scenegen.ROOM_LIGHTS[:2])
+
+
+if "--live" in sys.argv and __name__ == "__main__":
+    live_case()

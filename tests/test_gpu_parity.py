@@ -1572,7 +1572,7 @@ def test_bench_line_contract(extra):
     else null -- never stale)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--crop-checks", "2"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1591,6 +1591,42 @@ def test_bench_line_contract(extra):
         assert 0.2 < ro["frac"] < 1.0 and ro["pmc_source"]["measured_at_commit"]
     ex = d["extras"]
     assert ex["cold_frame_parity"] == ex["warm_same_frame"]["parity"] == ex["counters_on_frame_parity"] == d["parity"]
+
+
+def test_bench_plain_run_and_output_dump(engine, tmp_path):
+    """bench.py without --full (the run repeated for every change): exit code 0, ONE JSON line with the contract's
+    keys and none of what --full adds; --steps sets the timed steps; --dump-outputs writes the frame of the last timed
+    step (the golden camera's) as float32, and it is the reference's frame.  The plain run counts the rays of each
+    distinct camera once and weighs it: its ray counts must equal those of --full's pass over every frame."""
+    import hashlib, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    eng = {"state_machine": "1", "ray_pool": "2", "hybrid": "3", "auto": "0"}[engine]
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "18", "--warmup", "2",
+                            "--engine", eng] + list(extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    d = run("--dump-outputs", str(tmp_path / "out"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    for k in ("roofline", "parity", "frame_sha256", "extras", "cpu_baseline", "value_warm"):
+        assert k not in d, k
+    assert d["steps"] == 18 and d["unit"] == "Mray/s" and d["higher_is_better"] and d["ms_per_step"] > 0
+    assert d["value"] > 100.0
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame.npy"]
+    img = np.load(tmp_path / "out" / "frame.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 3)
+    u8 = img.astype(np.uint8)
+    assert np.array_equal(u8.astype(np.float32), img)
+    golden = json.load(open(os.path.join(GOLDEN, "frames.json")))["room_1920x1080_d5"]["sha256"]
+    assert hashlib.sha256(u8.tobytes()).hexdigest() == golden
+    f = run("--full", "--no-extras")
+    assert f["parity"] == "frame identical to the reference's"
+    assert d["rays_per_frame_mean"] == f["rays_per_frame_mean"] and d["rays_last_frame"] == f["rays_last_frame"]
 
 
 @pytest.mark.parametrize("n_straddlers", [450, 1100, 6000])
@@ -1655,7 +1691,7 @@ def test_bench_two_ranks_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MT_BENCH_EMULATE_RANKS="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                        "--full", "--no-cpu-baseline", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -688,16 +688,6 @@ int main() {
     subprocess.check_call([str(exe)])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/VerStarting"), reason="reference tree not present")
-def test_reference_drivers_compile_against_our_headers(tmp_path):
-    """Drop-in check: the reference's own drivers build, unmodified, against the
-    facade headers (syntax + semantic check only; nothing from them is linked or run)."""
-    inc = os.path.join(ROOT, "mythtracer_amd", "host", "include")
-    for drv in ("main_local.cc",):
-        subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I", inc,
-                               "/root/reference/VerStarting/" + drv])
-
-
 def test_hand_issued_scalar_prefetch_is_safe_on_the_isa():
     """The scan loop issues its box fetches from inline asm; hipcc does not model
     them.  tools/check_asm_prefetch.py compiles the library to ISA and proves that
