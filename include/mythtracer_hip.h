@@ -373,9 +373,10 @@ int mt_scene_set_tuning(mt_scene *scene, int knob, double value);
 
 /* Device durations of the launches made since the previous call (at most the
  * last 64, oldest first; at most max_n): primary_ms[i] = the kernels that
- * prepare the work order (mt::order_kernel with cost history, else
- * mt::primary_kernel; for the latency engine's first frame mt::probe_kernel +
- * mt::order_kernel), render_ms[i] = the frame kernel
+ * prepare the work order (mt::order_forecast_kernel, mt::order_count_kernel
+ * and mt::order_scatter_kernel with cost history, else mt::primary_kernel;
+ * for the latency engine's first frame mt::probe_kernel + those three),
+ * render_ms[i] = the frame kernel
  * (mt::render_kernel or mt::pool_kernel) of launch i, from HIP events recorded on
  * the launch's own stream.  Waits for those launches.  Returns the number of
  * entries written, or a negative MT_ERR_*.  (No reference counterpart: the

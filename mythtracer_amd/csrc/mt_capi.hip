@@ -48,7 +48,41 @@ int fail(int code, const char *fmt, ...) {
                   __FILE__, __LINE__);                                                  \
   } while (0)
 
+
+// MT_OK or return the MT_ERR_* of `expr`
+#define MT_TRY(expr)                                                                    \
+  do {                                                                                  \
+    const int rc_ = (expr);                                                             \
+    if (rc_ != MT_OK) return rc_;                                                       \
+  } while (0)
+
 constexpr size_t kLdsBudget = 160 * 1024;
+
+// A growable scratch buffer that owns its allocation: device memory, or page-locked host memory (HOST).  It only grows
+// -- a request above the capacity reallocates, at least 1 byte -- and is freed with its owner.
+template <typename T, bool HOST = false>
+struct Buf {
+  T *p = nullptr;
+  size_t bytes = 0;
+  Buf() = default;
+  Buf(const Buf &) = delete;
+  Buf &operator=(const Buf &) = delete;
+  ~Buf() {
+    if (p) (void)(HOST ? hipHostFree(p) : hipFree(p));
+  }
+  operator T *() const { return p; }
+  int ensure(size_t need, unsigned host_flags = hipHostMallocDefault) {
+    if (bytes >= need && p) return MT_OK;
+    void **ptr = (void **)&p;
+    if (p) HIP_TRY(HOST ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    bytes = 0;
+    if (HOST) HIP_TRY(hipHostMalloc(ptr, need ? need : 1, host_flags));
+    else HIP_TRY(hipMalloc(ptr, need ? need : 1));
+    bytes = need;
+    return MT_OK;
+  }
+};
 
 // Tuning constants of the work order and of the engine choice, with the values the sweeps of DESIGN.md section 5
 // settled on.  Changed through mt_scene_set_tuning only (tests, experiment scripts): the library reads no
@@ -89,7 +123,7 @@ struct Tuning {
     v[MT_TUNE_SM_CELL_SHARE] = 0.8;  // (x the quarters' cutting threshold; blocks with zero-component rays only: mt_order.h)
     v[MT_TUNE_SM_CELL_TIME] = 0.2;
     v[MT_TUNE_SM_CELL_WORK] = 3.0;
-    v[MT_TUNE_ORDER_GROUPS] = (double)kOrdGroups;  // workgroups of order_kernel (mt_order.h)
+    v[MT_TUNE_ORDER_GROUPS] = (double)kOrdGroups;  // workgroups of the work-order kernels (mt_order.h)
     v[MT_TUNE_XCD_QUEUES] = 2.0;  // one work order per XCD over a 4 x 2 grid of regions of equal forecast cost (L2 hit rate 0.82 -> 0.92 room, 0.66 -> 0.82 loft)
   }
 };
@@ -102,62 +136,45 @@ std::atomic<int> g_default_engine{0};
 struct mt_scene {
   int device = 0;
   DevScene dev{};
-  std::vector<void *> allocs;  // everything to hipFree
-  mt_light *d_lights = nullptr;
-  int lights_cap = 0;
-  unsigned long long *d_counters = nullptr;
-  unsigned int *d_work = nullptr;
-  unsigned int *d_queues = nullptr;  // kQueueWords: the per-XCD work orders' counters and bounds (RenderParams::queues)
-  unsigned int *d_order_ctl = nullptr;  // kOrdWords: the order kernels' sums, histograms, grids (zero at creation, never reset by the host)
-  unsigned int *d_order_whist = nullptr; // [kOrdGroupsMax][kOrdKeysMax]
-  unsigned int *d_item_unit = nullptr;
-  size_t item_unit_bytes = 0;
-  unsigned order_epoch = 0;             // order_kernel launches of this scene so far
+  std::vector<void *> allocs;  // the scene's uploads (scene_create_impl)
+  Buf<mt_light> d_lights;
+  Buf<unsigned long long> d_counters;
+  Buf<unsigned int> d_work;
+  Buf<unsigned int> d_queues;  // kQueueWords: the per-XCD work orders' counters and bounds (RenderParams::queues)
+  Buf<unsigned int> d_order_ctl;  // kOrdWords: the work-order kernels' sums, histograms, grids (zero at creation, never reset by the host)
+  Buf<unsigned int> d_order_whist; // [kOrdGroupsMax][kOrdKeysMax]
+  Buf<unsigned int> d_item_unit;
+  unsigned order_epoch = 0;             // work orders of this scene so far (order_forecast_kernel, order_count_kernel, order_scatter_kernel)
   mt_sensor irr_sensor{};               // the sensor `irr_sensor_has` was found for (image irr_w x irr_h)
   int irr_w = 0, irr_h = 0, irr_sensor_has = 0;
   bool irr_sensor_valid = false;
   DevScene dev_uploaded;                // what d_dev holds
   bool dev_uploaded_valid = false;
-  unsigned short *d_item_cell = nullptr;
-  size_t item_cell_bytes = 0;
-  double *d_frames = nullptr;      // throughput engine: recursion frames
-  size_t frames_bytes = 0;
-  int32_t *d_hit_prim = nullptr;   // launch 1 -> launch 2 hand-off (per pixel)
-  size_t hit_prim_bytes = 0;
-  double *d_hit_t = nullptr;
-  size_t hit_t_bytes = 0;
-  unsigned int *d_class_list = nullptr;  // [3][n_items]
-  size_t class_list_bytes = 0;
-  char *d_pool = nullptr;          // latency engine: ray pool scratch of every wave (mt_pool.h)
-  size_t pool_bytes = 0;
+  Buf<unsigned short> d_item_cell;
+  Buf<double> d_frames;            // throughput engine: recursion frames
+  Buf<int32_t> d_hit_prim;         // launch 1 -> launch 2 hand-off (per pixel)
+  Buf<double> d_hit_t;
+  Buf<unsigned int> d_class_list;  // [3][n_items]
+  Buf<char> d_pool;                // latency engine: ray pool scratch of every wave (mt_pool.h)
   int engine = 0;                  // 0 = automatic, 1 = throughput (state machine), 2 = latency (ray pool)
   int last_engine = 0;             // engine of the previous launch (cost histories are per engine)
   // cost feedback (schedule_kernel): valid for launches of the same geometry
-  unsigned int *d_item_cost = nullptr;   // [n_items]
-  size_t item_cost_bytes = 0;
-  unsigned int *d_item_forecast = nullptr;  // [n_items]
-  size_t item_forecast_bytes = 0;
-  unsigned int *d_item_forms = nullptr;     // [2 n_items] cost of a block as one unit / as four quarters (forecast_kernel)
-  size_t item_forms_bytes = 0;
-  unsigned char *d_item_form = nullptr;     // [n_items] hybrid launches: how each block was rendered (hybrid_schedule_kernel)
-  size_t item_form_bytes = 0;
+  Buf<unsigned int> d_item_cost;       // [n_items]
+  Buf<unsigned int> d_item_forecast;   // [n_items]
+  Buf<unsigned int> d_item_forms;      // [2 n_items] cost of a block as one unit / as four quarters (forecast_kernel)
+  Buf<unsigned char> d_item_form;      // [n_items] hybrid launches: how each block was rendered (hybrid_schedule_kernel)
   mt_sensor cost_sensor{};               // camera of the launch that measured the costs
-  unsigned int *d_order_item = nullptr;  // [4 n_items]
-  size_t order_item_bytes = 0;
-  signed char *d_order_sub = nullptr;    // [4 n_items]
-  size_t order_sub_bytes = 0;
+  Buf<unsigned int> d_order_item;      // [4 n_items]
+  Buf<signed char> d_order_sub;        // [4 n_items]
   unsigned long long cost_signature = 0;  // 0 = no history
   bool use_history = true;
-  uint8_t *d_rgb = nullptr;
-  size_t rgb_bytes = 0;
-  mt_debug_px *d_debug = nullptr;
-  size_t debug_bytes = 0;
+  Buf<uint8_t> d_rgb;
+  Buf<mt_debug_px> d_debug;
   std::vector<mt_light> lights_host;  // what d_lights holds
   int forecasts_in_a_row = 0;  // launches with this geometry and camera whose work order came from a forecast
   int waves_per_block = 4;
   int deep = 0;                    // which DEEP instantiations of the kernels: 0, 1, 2 (mt_device.h, deep_layout)
-  char *d_deep = nullptr;          // their per-wave areas
-  size_t deep_bytes = 0;
+  Buf<char> d_deep;                // their per-wave areas
   size_t lds_bytes = 0;
   int grid_blocks = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -168,15 +185,14 @@ struct mt_scene {
   unsigned long long launches_timed = 0, launches_read = 0;
   int n_cu = 0;
   bool stats_enabled = true;
-  unsigned long long *hb_host = nullptr;  // MT_DEBUG_HEARTBEAT: pinned, device-visible
-  unsigned long long *d_prof = nullptr;   // -DMT_PROF build: phase cycle sums
-  DevScene *d_dev = nullptr;              // device copy of `dev` (DevScene::self)
+  Buf<unsigned long long, true> hb_host;  // MT_DEBUG_HEARTBEAT: pinned, device-visible
+  Buf<unsigned long long> d_prof;         // -DMT_PROF build: phase cycle sums
+  Buf<DevScene> d_dev;                    // device copy of `dev` (DevScene::self)
   Tuning tune;
   // multi-GPU frames with a moving camera: every rank's costs of the previous frame (mt_scene_import_costs_device)
   RenderParams last_P{};                  // geometry of the last launch (mt_scene_export_costs_device)
   bool last_P_valid = false;
-  unsigned int *d_cost_map = nullptr;
-  size_t cost_map_bytes = 0;
+  Buf<unsigned int> d_cost_map;
   int cost_map_w = 0, cost_map_h = 0;
   unsigned long long cost_map_for_launch = ~0ull;  // the map describes the frame of launch number ... (launches_timed then)
   int tree_depth_levels = 0, n_tris_total = 0, n_nodes_total = 0;  // for MT_TUNE_PACKED_STACK
@@ -184,41 +200,29 @@ struct mt_scene {
   std::string dbg_item_cycles, dbg_timeline;
   int dbg_print_units = 0;
   // mt_render_frame_multi: this scene's tile buffer and stream, the frame + gathered tiles on the first scene's GPU
-  uint8_t *d_multi_tiles = nullptr;
-  size_t multi_tiles_bytes = 0;
-  uint8_t *d_multi_gather = nullptr;
-  size_t multi_gather_bytes = 0;
-  uint8_t *d_multi_frame = nullptr;
-  size_t multi_frame_bytes = 0;
+  Buf<uint8_t> d_multi_tiles;
+  Buf<uint8_t> d_multi_gather;
+  Buf<uint8_t> d_multi_frame;
   hipStream_t multi_stream = nullptr;
   hipEvent_t multi_done = nullptr;
-  unsigned int *d_multi_map = nullptr;    // this replica's block costs / the combined map on its way back
-  size_t multi_map_bytes = 0;
-  unsigned int *d_multi_maps = nullptr;   // first replica: all replicas' maps
-  size_t multi_maps_bytes = 0;
+  Buf<unsigned int> d_multi_map;    // this replica's block costs / the combined map on its way back
+  Buf<unsigned int> d_multi_maps;   // first replica: all replicas' maps
   hipEvent_t multi_comb_done = nullptr;
   // mt_render_chunk (host buffers): page-locked staging for the frame on its way to the caller's buffer (copied in
   // pieces, each piece's host copy under the next piece's DMA), pinned words for the counters
-  uint8_t *h_stage = nullptr;
-  size_t stage_bytes = 0;
+  Buf<uint8_t, true> h_stage;
   static constexpr int kStagePieces = 16;
   hipEvent_t ev_stage[kStagePieces] = {};
-  unsigned long long *h_counters = nullptr;
+  Buf<unsigned long long, true> h_counters;
   // tile-list launches (mt_render_tile_list_device): the launch's own copy of the list, and tile -> slot
-  int32_t *d_tile_list = nullptr;
-  size_t tile_list_bytes = 0;
-  int32_t *d_tile_slot = nullptr;
-  size_t tile_slot_bytes = 0;
+  Buf<int32_t> d_tile_list;
+  Buf<int32_t> d_tile_slot;
   // mt_order_tiles_device: summed block costs per tile
-  unsigned long long *d_tile_cost = nullptr;
-  size_t tile_cost_bytes = 0;
+  Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
-  int32_t *d_multi_order = nullptr;
-  size_t multi_order_bytes = 0;
-  int32_t *d_multi_list = nullptr;
-  size_t multi_list_bytes = 0;
-  int32_t *d_multi_lists = nullptr;
-  size_t multi_lists_bytes = 0;
+  Buf<int32_t> d_multi_order;
+  Buf<int32_t> d_multi_list;
+  Buf<int32_t> d_multi_lists;
   unsigned long long multi_geom = 0;      // geometry (image, tiles, depth, replicas) the state below belongs to
   unsigned long long multi_list_id = 0;   // changes whenever the tiles are dealt out anew
   bool multi_have_map = false;            // d_multi_map holds the combined costs of the previous frame of multi_geom
@@ -247,6 +251,45 @@ bool finite3(const double *p, size_t n) {
   return true;
 }
 
+// tiles of tile_w x tile_h over an image of image_w x image_h
+long long tile_count(int image_w, int image_h, int tile_w, int tile_h) {
+  return (long long)((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
+}
+
+// FNV-1a over a list of integers, never 0 (0 = no signature)
+unsigned long long fnv1a(std::initializer_list<long long> key) {
+  unsigned long long h = 1469598103934665603ull;
+  for (long long v : key) h = (h ^ (unsigned long long)v) * 1099511628211ull;
+  return h != 0 ? h : 1;
+}
+
+// 16-byte traversal stack frames when "first child" and "best triangle + 1" share one word: a quarter less LDS per
+// wave.  The shift of the packed word, or 0 where the two do not fit in 32 bits.
+int pack_shift_for(int n_tris, int n_nodes) {
+  int tri_bits = 1;
+  while (tri_bits < 31 && ((long long)n_tris + 1) > (1ll << tri_bits)) tri_bits++;
+  int node_bits = 1;
+  while (node_bits < 31 && (long long)n_nodes > (1ll << node_bits)) node_bits++;
+  return tri_bits + node_bits <= 32 ? tri_bits : 0;
+}
+
+// The kernels of one deep layout D = 0, 1, 2 (mt_device.h, deep_layout); the frame kernels by [STATS]
+using SceneKernel = void (*)(DevScene, RenderParams);
+struct LayoutKernels {
+  SceneKernel render[2], primary[2], pool[2], hybrid[2], probe;
+  void (*intersect)(DevScene, int, const double *, int *, int *, double *, double *, unsigned long long *);
+};
+template <int D>
+LayoutKernels layout_kernels() {
+  return {{render_kernel<false, D>, render_kernel<true, D>}, {primary_kernel<false, D>, primary_kernel<true, D>},
+          {pool_kernel<false, D>, pool_kernel<true, D>}, {hybrid_kernel<false, D>, hybrid_kernel<true, D>},
+          probe_kernel<D>, intersect_kernel<D>};
+}
+const LayoutKernels &kernels_of(int deep) {
+  static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
+  return k[deep];
+}
+
 // Launch geometry: workgroups of 4 waves -- or of 2 or 1 where that puts more waves on a CU: a deep octree's traversal
 // frames (27 KB per wave at 16 levels) let one 4-wave workgroup fill two thirds of the LDS and leave room for a fifth
 // wave only as a workgroup of its own.
@@ -265,16 +308,14 @@ int configure_launch(mt_scene *s) {
     std::lock_guard<std::mutex> lock(mu);
     size_t &have = lds_attr[s->device];
     if (bytes > have) {
-#define MT_KERNELS_OF(D_)                                                                                  \
-  (const void *)render_kernel<true, D_>, (const void *)render_kernel<false, D_>,                              \
-  (const void *)primary_kernel<true, D_>, (const void *)primary_kernel<false, D_>,                            \
-  (const void *)pool_kernel<true, D_>, (const void *)pool_kernel<false, D_>,                                  \
-  (const void *)hybrid_kernel<true, D_>, (const void *)hybrid_kernel<false, D_>,                              \
-  (const void *)probe_kernel<D_>, (const void *)intersect_kernel<D_>
-      const void *kernels[] = {MT_KERNELS_OF(0), MT_KERNELS_OF(1), MT_KERNELS_OF(2)};
-#undef MT_KERNELS_OF
-      for (const void *k : kernels) {
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+      constexpr hipFuncAttribute kLdsAttr = hipFuncAttributeMaxDynamicSharedMemorySize;
+      for (int d = 0; d < 3; d++) {
+        const LayoutKernels &k = kernels_of(d);
+        for (const SceneKernel *f : {k.render, k.primary, k.pool, k.hybrid}) {
+          for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)f[st], kLdsAttr, (int)bytes));
+        }
+        HIP_TRY(hipFuncSetAttribute((const void *)k.probe, kLdsAttr, (int)bytes));
+        HIP_TRY(hipFuncSetAttribute((const void *)k.intersect, kLdsAttr, (int)bytes));
       }
       have = bytes;
     }
@@ -283,10 +324,9 @@ int configure_launch(mt_scene *s) {
   int best_wpb = 0, best_per_cu = 0;
   for (int wpb = 4; wpb >= 1; wpb >>= 1) {
     if (per_wave * wpb > kLdsBudget) continue;
-    int rc = set_attribute(per_wave * wpb);
-    if (rc != MT_OK) return rc;
+    MT_TRY(set_attribute(per_wave * wpb));
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s->deep == 2 ? (const void *)render_kernel<true, 2> : (s->deep == 1 ? (const void *)render_kernel<true, 1> : (const void *)render_kernel<true, 0>), wpb * 64, per_wave * wpb));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernels_of(s->deep).render[1], wpb * 64, per_wave * wpb));
     if (per_cu < 1) per_cu = 1;
     if (per_cu * wpb > 16) per_cu = 16 / wpb;  // more waves only add divergence state
     if (per_cu * wpb > best_per_cu * best_wpb) {  // (ties: the larger workgroup, tried first)
@@ -305,74 +345,55 @@ int configure_launch(mt_scene *s) {
   return MT_OK;
 }
 
-int ensure_bytes(void **ptr, size_t *have, size_t need) {
-  if (*have >= need && *ptr) return MT_OK;
-  if (*ptr) HIP_TRY(hipFree(*ptr));
-  *ptr = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(ptr, need ? need : 1));
-  *have = need;
-  return MT_OK;
-}
-
-// launches kernel<STATS, DEEP> (or kernel<DEEP>) for the scene's layout
-#define MT_LAUNCH_SD(kernel, stats, grid_, block_, lds_, stream_, ...)                                              \
-  do {                                                                                                                \
-    if (s->deep == 2) {                                                                                               \
-      if (stats) hipLaunchKernelGGL((kernel<true, 2>), grid_, block_, lds_, stream_, __VA_ARGS__);                    \
-      else hipLaunchKernelGGL((kernel<false, 2>), grid_, block_, lds_, stream_, __VA_ARGS__);                         \
-    } else if (s->deep == 1) {                                                                                        \
-      if (stats) hipLaunchKernelGGL((kernel<true, 1>), grid_, block_, lds_, stream_, __VA_ARGS__);                    \
-      else hipLaunchKernelGGL((kernel<false, 1>), grid_, block_, lds_, stream_, __VA_ARGS__);                         \
-    } else {                                                                                                          \
-      if (stats) hipLaunchKernelGGL((kernel<true, 0>), grid_, block_, lds_, stream_, __VA_ARGS__);                    \
-      else hipLaunchKernelGGL((kernel<false, 0>), grid_, block_, lds_, stream_, __VA_ARGS__);                         \
-    }                                                                                                                 \
-  } while (0)
-#define MT_LAUNCH_D(kernel, grid_, block_, lds_, stream_, ...)                                                      \
-  do {                                                                                                                \
-    if (s->deep == 2) hipLaunchKernelGGL((kernel<2>), grid_, block_, lds_, stream_, __VA_ARGS__);                     \
-    else if (s->deep == 1) hipLaunchKernelGGL((kernel<1>), grid_, block_, lds_, stream_, __VA_ARGS__);                \
-    else hipLaunchKernelGGL((kernel<0>), grid_, block_, lds_, stream_, __VA_ARGS__);                                  \
-  } while (0)
-
 // the per-wave global areas of the DEEP instantiations, for a launch of `waves` waves
 int ensure_deep(mt_scene *s, size_t waves) {
   if (!s->deep) return MT_OK;
   const size_t stride = (wave_deep_bytes(s->dev.tree_depth) + 255) & ~(size_t)255;
-  int rc = ensure_bytes((void **)&s->d_deep, &s->deep_bytes, stride * waves);
-  if (rc != MT_OK) return rc;
+  MT_TRY(s->d_deep.ensure(stride * waves));
   s->dev.deep_base = s->d_deep;
   s->dev.deep_stride = stride;
   return MT_OK;
 }
 
-int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int rx, int ry,
-                  int rw, int rh, int tile_w, int tile_h, int first_tile, int tile_stride,
-                  int n_tiles, int max_depth, uint8_t *d_rgb, mt_debug_px *d_debug,
-                  hipStream_t stream, const int32_t *d_list = nullptr, unsigned long long list_id = 0) {
-  if (max_depth < 0 || max_depth > MT_MAX_RECURSION) {
-    return fail(MT_ERR_ARG, "max_depth %d outside [0, %d]", max_depth, MT_MAX_RECURSION);
+// Did the frame of sensor `o` have pixels whose primary rays have a zero direction component?  Found on the host,
+// exactly: per scanline and component the direction is r + dp x with r = start + ds y (the kernels' own expression,
+// Sensor::GetRay), zero for at most the pixels next to -r / dp -- a whole column or row for a camera on an axis,
+// isolated pixels for one with roll or pitch.  Those blocks' costs are skipped by a re-projected forecast
+// (forecast_kernel).
+int has_zero_component_pixel(const mt_sensor &o, int image_w, int image_h) {
+  for (int k = 0; k < 3; k++) {
+    for (int y = 0; y < image_h; y++) {
+      const double r = o.start_point[k] + o.delta_scanline[k] * (double)y;
+      if (o.delta_pixel[k] == 0.0 || !std::isfinite(r / o.delta_pixel[k])) {
+        if (r + o.delta_pixel[k] * 0.0 == 0.0) return 1;
+        continue;
+      }
+      const double x0 = std::nearbyint(-r / o.delta_pixel[k]);
+      for (int dx = -1; dx <= 1; dx++) {
+        const double x = x0 + dx;
+        if (x >= 0.0 && x < (double)image_w && r + o.delta_pixel[k] * x == 0.0) return 1;
+      }
+    }
   }
-  RenderParams P{};
-  P.sensor = *sensor;
-  P.image_w = image_w;
-  P.image_h = image_h;
-  P.region_x = rx; P.region_y = ry; P.region_w = rw; P.region_h = rh;
-  P.tile_w = tile_w; P.tile_h = tile_h;
-  P.tiles_x = (rw + tile_w - 1) / tile_w;
-  P.first_tile = first_tile; P.tile_stride = tile_stride; P.n_tiles = n_tiles;
-  P.blocks_x = (tile_w + 7) / 8;
-  P.blocks_y = (tile_h + 7) / 8;
-  P.max_depth = max_depth;
-  const unsigned long long items = (unsigned long long)n_tiles * P.blocks_x * P.blocks_y;
-  if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
-  P.n_items = (unsigned)items;
-  P.out_rgb = d_rgb;
-  P.out_debug = d_debug;
-  P.counters = s->d_counters;
-  P.work_counter = s->d_work;
-  const size_t waves = (size_t)s->grid_blocks * s->waves_per_block;
+  return 0;
+}
+
+// What a launch does, decided from its geometry and the scene's history (decide_launch, no HIP call)
+struct LaunchPlan {
+  unsigned long long sig = 0;  // the launch's geometry: costs measured by a launch with the same one are a history
+  bool from_map = false;       // the history is the frame-wide cost map imported since the previous launch
+  bool history = false;        // the work order comes from a history (else from probe_kernel / primary_kernel)
+  int engine = 0;              // 1 state machine, 2 ray pool, 3 hybrid
+  long long pool_cap = 0;      // ray pool: records per wave
+  size_t pool_stride = 0;      // ... and bytes per wave
+  int reproject = 0, radius = 0;  // forecast_kernel: the camera moved since the costs were measured
+  float blend = 0.0f;
+  int old_irr = 0, new_irr = 0;   // zero-component pixels in the frame that measured the costs / in this one
+};
+
+int decide_launch(mt_scene *s, const RenderParams &P, const mt_sensor *sensor, bool debug, const int32_t *d_list,
+                  unsigned long long list_id, size_t waves, LaunchPlan &L) {
+  const int image_w = P.image_w, image_h = P.image_h, max_depth = P.max_depth;
   // The block costs of the previous launch are a valid forecast when that
   // launch had the same geometry (an animation frame, main_local.cc:79-110, or a
   // repeated benchmark step) -- whichever engine measured them.  Then the blocks
@@ -380,25 +401,18 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   // pool forecasts from 1/16 of the primary rays (probe_kernel); the state
   // machine classifies the blocks by material in a launch of its own
   // (primary_kernel).
-  unsigned long long sig = 1469598103934665603ull;
-  {
-    const long long key[] = {image_w, image_h, rx, ry, rw, rh, tile_w, tile_h, first_tile, tile_stride,
-                             n_tiles, max_depth, s->dev.n_lights, d_list ? 1 : 0, d_list ? (long long)list_id : 0};
-    for (long long v : key) {
-      sig = (sig ^ (unsigned long long)v) * 1099511628211ull;
-    }
-    if (sig == 0) sig = 1;
-  }
+  L.sig = fnv1a({image_w, image_h, P.region_x, P.region_y, P.region_w, P.region_h, P.tile_w, P.tile_h, P.first_tile,
+                 P.tile_stride, P.n_tiles, max_depth, s->dev.n_lights, d_list ? 1 : 0, d_list ? (long long)list_id : 0});
   // (a tile list promises to be the previous launch's list by its non-zero list_id only)
-  bool have_costs = s->use_history && s->cost_signature == sig && !(d_list != nullptr && list_id == 0);
+  bool have_costs = s->use_history && s->cost_signature == L.sig && !(d_list != nullptr && list_id == 0);
   // A list launch with ANOTHER list (the tiles were dealt out anew): the slots' cost words belong to other tiles, but the
   // frame-wide map imported since the previous launch has every block's cost by image position.
   const bool map_ready = s->d_cost_map != nullptr && s->cost_map_for_launch == s->launches_timed &&
                          s->cost_map_w >= (image_w + 7) / 8 && s->cost_map_h >= (image_h + 7) / 8;
-  const bool from_map = s->use_history && d_list != nullptr && !have_costs && map_ready && s->last_P_valid &&
-                        (tile_w & 7) == 0 && (tile_h & 7) == 0 && (rx & 7) == 0 && (ry & 7) == 0 &&
-                        s->last_P.image_w == image_w && s->last_P.image_h == image_h && s->last_P.max_depth == max_depth;
-  if (from_map) have_costs = true;
+  L.from_map = s->use_history && d_list != nullptr && !have_costs && map_ready && s->last_P_valid &&
+               (P.tile_w & 7) == 0 && (P.tile_h & 7) == 0 && (P.region_x & 7) == 0 && (P.region_y & 7) == 0 &&
+               s->last_P.image_w == image_w && s->last_P.image_h == image_h && s->last_P.max_depth == max_depth;
+  if (L.from_map) have_costs = true;
   // ---- which engine?  Both compute every pixel with the same operations in the
   // same order (tests render through both).  The state machine (one lane per
   // pixel, its context in registers) has the lower cost per ray and is the
@@ -414,14 +428,12 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   // -- to keep the scratch of all resident waves within MT_TUNE_POOL_SCRATCH_MB.
   const int n_l = s->dev.n_lights;
   constexpr int kPoolMaxLights = 254;  // a pool entry has 8 bits for (light + 1)
-  long long pool_cap = 0;
-  size_t pool_stride = 0;
   bool pool_fits = n_l <= kPoolMaxLights, pool_roomy = pool_fits;
   if (pool_fits) {
     constexpr long long kPoolCapMax = 1024;
     const long long all = 64ll * ((2ll << max_depth) - 1);
     const long long floor_cap = 64 + 128 + 4ll * (max_depth + 1) + 64;
-    pool_cap = all < kPoolCapMax ? all : kPoolCapMax;
+    long long pool_cap = all < kPoolCapMax ? all : kPoolCapMax;
     const size_t rec_bytes = (size_t)(kRecFixed + kLightSlot * n_l) * sizeof(double);
     const size_t per_rec = rec_bytes + (size_t)(n_l > 0 ? n_l : 1) * 4 + 4;
     const double budget = s->tune.v[MT_TUNE_POOL_SCRATCH_MB] * 1048576.0;
@@ -436,7 +448,8 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
       pool_fits = (double)floor_cap * (double)per_rec * (double)(waves ? waves : 1) <= 4.0 * budget;
       pool_cap = floor_cap;
     }
-    pool_stride = ((size_t)pool_cap * per_rec + 255) & ~(size_t)255;
+    L.pool_cap = pool_cap;
+    L.pool_stride = ((size_t)pool_cap * per_rec + 255) & ~(size_t)255;
   }
   if (engine_auto) {
     // blocks per wave below which a launch is taken to be tail-bound (one rank's share of the 4K frame
@@ -451,29 +464,55 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
     // 3.63 ms against the pool's 3.88 and the state machine's 4.36; at N = 4 the state machine alone is ahead, 5.71
     // against 5.80).  It has no debug-buffer path: such launches stay with the pool.
     const bool small = (float)P.n_items < per_wave * (float)waves;
-    engine = !(pool_fits && pool_roomy) ? 1 : (!have_costs ? 2 : (small ? (d_debug == nullptr ? 3 : 2) : 1));
+    engine = !(pool_fits && pool_roomy) ? 1 : (!have_costs ? 2 : (small ? (!debug ? 3 : 2) : 1));
   }
   // Engine 3 (hybrid: the longest blocks through the ray pool in pieces, the rest through the state machine, one
   // kernel) needs measured costs to tell the two kinds apart and has no debug-buffer path; a launch without either
   // is rendered by the ray pool (or the state machine where the pool does not fit).
-  if (engine == 3 && !(have_costs && pool_fits && d_debug == nullptr)) engine = pool_fits ? 2 : 1;
+  if (engine == 3 && !(have_costs && pool_fits && !debug)) engine = pool_fits ? 2 : 1;
   if (engine == 2 && !pool_fits) {
     return fail(MT_ERR_UNSUPPORTED, "the ray pool (engine 2) holds at most %d lights within its scratch budget; "
                 "%d were set -- engine 0 (automatic) or 1 renders such scenes", kPoolMaxLights, n_l);
   }
-  const bool pool_engine = engine == 2, hybrid = engine == 3;
-  const bool history = have_costs && (pool_engine || d_debug == nullptr);  // (hybrid: both hold, see above)
-  P.from_primary = history ? 0 : 1;
-  {
-    int rc = ensure_bytes((void **)&s->d_item_cost, &s->item_cost_bytes, (size_t)P.n_items * 4);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_item_forecast, &s->item_forecast_bytes, (size_t)P.n_items * 4);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_item_forms, &s->item_forms_bytes, (size_t)P.n_items * 8);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_order_item, &s->order_item_bytes, (size_t)P.n_items * 64);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_order_sub, &s->order_sub_bytes, (size_t)P.n_items * 16);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_item_form, &s->item_form_bytes, (size_t)P.n_items);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_item_unit, &s->item_unit_bytes, (size_t)P.n_items * 4);
-    if (rc != MT_OK) return rc;
+  L.engine = engine;
+  L.history = have_costs && (engine == 2 || !debug);  // (hybrid: both hold, see above)
+  if (!L.history) return MT_OK;
+  // (kept per sensor: a camera at rest is looked at once)
+  if (!s->irr_sensor_valid || memcmp(&s->irr_sensor, sensor, sizeof(mt_sensor)) != 0 || s->irr_w != image_w || s->irr_h != image_h) {
+    s->irr_sensor = *sensor; s->irr_w = image_w; s->irr_h = image_h;
+    s->irr_sensor_has = has_zero_component_pixel(*sensor, image_w, image_h);
+    s->irr_sensor_valid = true;
   }
+  L.new_irr = s->irr_sensor_has;
+  // Has the camera moved since the costs were measured?  Then forecast_kernel
+  // re-projects them (radius 1 block; 2 when the origin moved too: parallax).
+  if (memcmp(&s->cost_sensor, sensor, sizeof(mt_sensor)) != 0) {
+    L.old_irr = has_zero_component_pixel(s->cost_sensor, image_w, image_h);
+    L.reproject = 1;
+    L.radius = memcmp(s->cost_sensor.origin, sensor->origin, sizeof sensor->origin) != 0 ? 2 : 1;
+    if (s->tune.v[MT_TUNE_FORECAST_RADIUS] >= 0.0) L.radius = (int)s->tune.v[MT_TUNE_FORECAST_RADIUS];
+  }
+  if (!L.reproject && !L.from_map && s->forecasts_in_a_row > 0) {
+    // swept (scripts/blend_sweep.py, state machine, 64 frames): 0 -> every other frame 6 % slower (mean 7.09 ms), 0.5 -> one
+    // in three (7.03), 0.9 -> one in eight (7.01); a frozen forecast (1.0) repeats its frame time to 0.2 % (scripts/alternation.py)
+    // (a running mean of the measurements first -- 1/2, 2/3, ... -- so that the first frames' costs, measured under a
+    // guessed order, do not linger)
+    const float cap = (float)s->tune.v[MT_TUNE_BLEND];
+    L.blend = std::min(cap, (float)s->forecasts_in_a_row / (float)(s->forecasts_in_a_row + 1));
+  }
+  return MT_OK;
+}
+
+// The buffers a launch of plan L needs, and P's pointers to them
+int size_buffers(mt_scene *s, const LaunchPlan &L, const int32_t *d_list, size_t waves, RenderParams &P) {
+  const size_t n = P.n_items;
+  MT_TRY(s->d_item_cost.ensure(n * 4));
+  MT_TRY(s->d_item_forecast.ensure(n * 4));
+  MT_TRY(s->d_item_forms.ensure(n * 8));
+  MT_TRY(s->d_order_item.ensure(n * 64));
+  MT_TRY(s->d_order_sub.ensure(n * 16));
+  MT_TRY(s->d_item_form.ensure(n));
+  MT_TRY(s->d_item_unit.ensure(n * 4));
   P.item_cost = s->d_item_cost;
   P.item_forecast = s->d_item_forecast;
   P.item_whole = s->d_item_forms;
@@ -483,59 +522,36 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   P.order_sub = s->d_order_sub;
   P.n_work = s->d_work + 7;
   // the combined cost map of all ranks, if one was imported after the previous launch (else nullptr: own costs only)
-  P.cost_map = (s->d_cost_map != nullptr && s->cost_map_for_launch == s->launches_timed) ? s->d_cost_map : nullptr;
+  P.cost_map = s->cost_map_for_launch == s->launches_timed ? s->d_cost_map.p : nullptr;
   P.cost_map_w = s->cost_map_w;
   P.cost_map_h = s->cost_map_h;
-  P.from_map = from_map ? 1 : 0;
-  if (from_map) P.item_whole = P.item_qsum = nullptr;  // (the two measured forms of a block are kept per slot)
-  if (d_list != nullptr && n_tiles > 0) {
-    const int tiles_total = P.tiles_x * ((rh + tile_h - 1) / tile_h);
-    int rc = ensure_bytes((void **)&s->d_tile_list, &s->tile_list_bytes, (size_t)n_tiles * 4);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_tile_slot, &s->tile_slot_bytes, (size_t)tiles_total * 4);
-    if (rc != MT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_tile_list, d_list, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((tiles_total + 255) / 256), dim3(256), 0, stream, s->d_tile_list, n_tiles, s->d_tile_slot, tiles_total, 0);
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, stream, s->d_tile_list, n_tiles, s->d_tile_slot, tiles_total, 1);
-    HIP_TRY(hipGetLastError());
+  if (L.from_map) P.item_whole = P.item_qsum = nullptr;  // (the two measured forms of a block are kept per slot)
+  if (d_list != nullptr && P.n_tiles > 0) {
+    MT_TRY(s->d_tile_list.ensure((size_t)P.n_tiles * 4));
+    MT_TRY(s->d_tile_slot.ensure((size_t)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h) * 4));
     P.tile_list = s->d_tile_list;
     P.tile_slot = s->d_tile_slot;
   }
-  if (pool_engine || hybrid) {
-    int rc = ensure_bytes((void **)&s->d_pool, &s->pool_bytes, pool_stride * waves);
-    if (rc != MT_OK) return rc;
+  if (L.engine == 2 || L.engine == 3) {
+    MT_TRY(s->d_pool.ensure(L.pool_stride * waves));
     P.pool_scratch = s->d_pool;
-    P.pool_stride = pool_stride;
-    P.pool_cap = (int)pool_cap;
+    P.pool_stride = L.pool_stride;
+    P.pool_cap = (int)L.pool_cap;
     P.prio_units = (unsigned)(s->n_cu * 4);  // one per SIMD
   }
-  if (!pool_engine) {
-    size_t fbytes = waves * ((size_t)(max_depth > 0 ? max_depth : 1) * kFrameSlots + kParkSlots) * 64 * sizeof(double);
-    const size_t slots_px = (size_t)n_tiles * (size_t)tile_w * (size_t)tile_h;
-    int rc = ensure_bytes((void **)&s->d_frames, &s->frames_bytes, fbytes);
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_hit_prim, &s->hit_prim_bytes, slots_px * sizeof(int32_t));
-    if (rc == MT_OK) rc = ensure_bytes((void **)&s->d_hit_t, &s->hit_t_bytes, slots_px * sizeof(double));
-    if (rc == MT_OK) {
-      rc = ensure_bytes((void **)&s->d_class_list, &s->class_list_bytes,
-                        3 * (size_t)P.n_items * sizeof(unsigned int));
-    }
-    if (rc != MT_OK) return rc;
+  if (L.engine != 2) {
+    const size_t slots_px = (size_t)P.n_tiles * (size_t)P.tile_w * (size_t)P.tile_h;
+    MT_TRY(s->d_frames.ensure(waves * ((size_t)(P.max_depth > 0 ? P.max_depth : 1) * kFrameSlots + kParkSlots) * 64 * sizeof(double)));
+    MT_TRY(s->d_hit_prim.ensure(slots_px * sizeof(int32_t)));
+    MT_TRY(s->d_hit_t.ensure(slots_px * sizeof(double)));
+    MT_TRY(s->d_class_list.ensure(3 * n * sizeof(unsigned int)));
     P.frames = s->d_frames;
     P.hit_prim = s->d_hit_prim;
     P.hit_t = s->d_hit_t;
     P.class_list = s->d_class_list;
     P.class_count = s->d_work + 4;  // d_work: [0..1] work counters, [4..6] class counts
   }
-  P.item_cycles = nullptr;
-  unsigned long long *d_item = nullptr;
-  const char *item_dump = s->dbg_item_cycles.empty() ? nullptr : s->dbg_item_cycles.c_str();
-  if (item_dump && P.n_items > 0) {
-    HIP_TRY(hipMalloc((void **)&d_item, (size_t)P.n_items * 16 * 16 * 4));
-    HIP_TRY(hipMemset(d_item, 0, (size_t)P.n_items * 16 * 16 * 4));
-    P.item_cycles = d_item;
-  }
-  if (P.n_items == 0) return MT_OK;
-  // (launches with a work order: order_kernel zeroes the counters on its way)
-  if (!history && !pool_engine) HIP_TRY(hipMemsetAsync(s->d_work, 0, 16 * sizeof(unsigned), stream));
+  if (n == 0) return MT_OK;  // (nothing is launched)
   P.order_ctl = s->d_order_ctl;
   P.order_whist = s->d_order_whist;
   P.item_unit = s->d_item_unit;
@@ -543,178 +559,135 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   // (measured and left out: first frames through the ray pool -- room 8.4 -> 8.9 ms, loft 19.7 -> 20.9: the probe's guess
   // balances the regions too roughly, and such a frame ends with its longest units either way --; the state machine's
   // part of hybrid launches, i.e. a rank's share of a frame -- mean of eight ranks' 4K shares 2.71 -> 2.77 ms)
-  P.queues = (s->tune.v[MT_TUNE_XCD_QUEUES] != 0.0 && history && !pool_engine && !hybrid) ? s->d_queues : nullptr;
+  P.queues = (s->tune.v[MT_TUNE_XCD_QUEUES] != 0.0 && L.history && L.engine == 1) ? s->d_queues.p : nullptr;
   if (P.queues) {
-    int rc = ensure_bytes((void **)&s->d_item_cell, &s->item_cell_bytes, (size_t)P.n_items * 2);
-    if (rc != MT_OK) return rc;
+    MT_TRY(s->d_item_cell.ensure(n * 2));
     P.item_cell = s->d_item_cell;
   }
-  const dim3 grid(s->grid_blocks), block(s->waves_per_block * 64);
-  {  // (the probe's grid follows the number of blocks: 16 of them per wave)
-    const size_t probe_waves = ((size_t)4 * P.n_items + block.x - 1) / block.x * s->waves_per_block;
-    int rc = ensure_deep(s, std::max(waves, probe_waves));
-    if (rc != MT_OK) return rc;
+  // (the probe's grid follows the number of blocks: 16 of them per wave)
+  const size_t block = (size_t)s->waves_per_block * 64;
+  const size_t probe_waves = (4 * n + block - 1) / block * s->waves_per_block;
+  return ensure_deep(s, std::max(waves, probe_waves));
+}
+
+// the three kernels of the work order (mt_order.h) of kind KIND: 0 state machine, 1 hybrid, 2 ray pool
+template <int KIND>
+void launch_order(const RenderParams &P, const ForecastArgs &fa, const OrderArgs &oa, int groups, hipStream_t stream) {
+  hipLaunchKernelGGL(order_forecast_kernel<KIND>, dim3(groups), dim3(kOrdThreads), 0, stream, P, fa, oa);
+  hipLaunchKernelGGL(order_count_kernel<KIND>, dim3(groups), dim3(kOrdThreads), 0, stream, P, oa);
+  hipLaunchKernelGGL(order_scatter_kernel<KIND>, dim3(groups), dim3(kOrdThreads), 0, stream, P, oa);
+}
+
+// The work order of a launch with a cost history, or of the ray pool's first frame (from probe_kernel's forecast)
+void launch_work_order(mt_scene *s, const LaunchPlan &L, const RenderParams &P, hipStream_t stream) {
+  const double *tv = s->tune.v;
+  const int last = s->last_engine;  // (the engine that measured the costs)
+  const bool pool = L.engine == 2, hybrid = L.engine == 3;
+  // blocks above this share of an even split are cut into quarters; a re-projected forecast (moving camera) is
+  // cut more eagerly -- it is a neighbourhood maximum of stale costs (swept, scripts/quad_sweep.py: repeated frame
+  // 0.6 / 0.8 / 1.0 -> 7.18 / 6.84 / 7.28 ms, moving camera 6.69 / 7.20 / 9.89; with work 1.5: share 0.7 -> 6.40)
+  // (with the per-block ratio of the two forms' costs -- forecast_kernel -- the repeated frame no longer alternates,
+  // and re-swept: 0.8 / 0.9 / 0.95 / 1.0 / 1.05 / 1.1 -> 6.67 / 6.49 / 6.47 / 6.46 / 6.56 / 6.93 ms)
+  const float quad_share = (float)tv[L.reproject ? MT_TUNE_QUAD_SHARE_MOVING : MT_TUNE_QUAD_SHARE];  // 0.7 / 0.95
+  // work of a block rendered as quarters / rendered whole (swept with the share): 1.5 / 1.7
+  const float quad_work = (float)tv[L.reproject ? MT_TUNE_QUAD_WORK_MOVING : MT_TUNE_QUAD_WORK];
+  // the ray pool: blocks above cut_share of an even split of the frame are handed out in pieces; a forecast is cut more
+  // eagerly (own_costs: granularity in bits 30-31)
+  SchedParams sp{L.history ? 1.0f : 0.3f, {1.0f, (float)tv[MT_TUNE_POOL_PIECE_TIME1], (float)tv[MT_TUNE_POOL_PIECE_TIME2]},
+                 {1.0f, (float)tv[MT_TUNE_POOL_PIECE_WORK1], (float)tv[MT_TUNE_POOL_PIECE_WORK2]},
+                 (float)tv[MT_TUNE_POOL_CELL_FACTOR], (!L.from_map && (!L.history || last == 2)) ? 1 : 0};
+  if (tv[MT_TUNE_POOL_CUT_SHARE] >= 0.0) sp.cut_share = (float)tv[MT_TUNE_POOL_CUT_SHARE];
+  // How forecast_kernel reads the measured costs -- per engine, side by side (the state machine and the hybrid kernel
+  // always have a history):
+  //   pool  the cost words carry the ray pool's granularity
+  //   w1    cost of a block's quarters over the block's whole cost, w2 the same for its cells
+  ForecastArgs fa{s->cost_sensor, L.reproject, L.radius,
+                  pool ? ((L.history && (last == 1 || last == 3)) ? 0 : 1) : (last == 2 ? 1 : 0),
+                  pool ? ((L.history && last == 1) ? 1.7f : sp.piece_work[1]) : (last == 2 ? 1.1f : quad_work),
+                  pool ? sp.piece_work[2] : 3.0f,
+                  16000u, L.blend, (L.history && last == 3) ? s->d_item_form.p : nullptr, (float)tv[MT_TUNE_HYBRID_WORK1],
+                  (float)tv[MT_TUNE_HYBRID_WORK2], (float)tv[MT_TUNE_FORECAST_STEP], (float)tv[MT_TUNE_SM_CELL_WORK],
+                  L.old_irr, L.new_irr};
+  OrderArgs oa{};
+  oa.n_waves = s->grid_blocks * s->waves_per_block;
+  oa.epoch = s->order_epoch++;
+  const int groups = std::max(1, std::min((int)tv[MT_TUNE_ORDER_GROUPS], kOrdGroupsMax));
+  if (pool) {
+    oa.sp = sp;
+    launch_order<2>(P, fa, oa, groups, stream);
+  } else if (hybrid) {
+    const float k = L.reproject ? (float)(tv[MT_TUNE_QUAD_SHARE_MOVING] / tv[MT_TUNE_QUAD_SHARE]) : 1.0f;  // a re-projected forecast is cut more eagerly
+    oa.quad_share = k * (float)tv[MT_TUNE_HYBRID_QUAD_SHARE];
+    oa.pool_share = k * (float)tv[MT_TUNE_HYBRID_POOL_SHARE];
+    oa.piece_time1 = (float)tv[MT_TUNE_POOL_PIECE_TIME1];
+    oa.piece_time2 = (float)tv[MT_TUNE_POOL_PIECE_TIME2];
+    oa.cell_factor = (float)tv[MT_TUNE_HYBRID_CELL_FACTOR];
+    oa.form_out = s->d_item_form;
+    oa.starter_share = (float)tv[MT_TUNE_HYBRID_STARTER_SHARE];
+    oa.max_starters = (unsigned)std::min(s->grid_blocks, (int)(0.25 * s->grid_blocks * s->waves_per_block));
+    launch_order<1>(P, fa, oa, groups, stream);
+  } else {
+    oa.quad_share = quad_share;
+    // ... and stay so above this fraction of that threshold (1 = no hysteresis: swept, scripts/quad_sweep.py --
+    // settings that steady the repeated frame cost the moving camera 50 %)
+    oa.quad_keep = (float)tv[MT_TUNE_QUAD_KEEP];
+    oa.cell_share = (float)tv[MT_TUNE_SM_CELL_SHARE];
+    // (cells only on MEASURED costs: a re-projected forecast of such a block is a guess -- thirty times a mean block --
+    // that cannot tell the loft's column, 1.4 frames long as quarters, from the room's, 0.87: room panning +0.5 % with
+    // the guess trusted, loft -2 %)
+    oa.new_irr = L.reproject ? 0 : L.new_irr;
+    oa.cell_time = (float)tv[MT_TUNE_SM_CELL_TIME];
+    oa.queue_mode = (int)tv[MT_TUNE_XCD_QUEUES];
+    launch_order<0>(P, fa, oa, groups, stream);
   }
+}
+
+// Everything a launch puts on its stream.  Events: [0] -> [1] forecast / classification + work order; [1] -> [2] the
+// frame kernel.
+int launch_kernels(mt_scene *s, const LaunchPlan &L, const RenderParams &P, const int32_t *d_list, hipStream_t stream) {
+  if (P.tile_list) {
+    const int tiles_total = (int)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h);
+    HIP_TRY(hipMemcpyAsync(s->d_tile_list, d_list, (size_t)P.n_tiles * 4, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(tile_slot_kernel, dim3((tiles_total + 255) / 256), dim3(256), 0, stream, s->d_tile_list.p, P.n_tiles, s->d_tile_slot.p, tiles_total, 0);
+    hipLaunchKernelGGL(tile_slot_kernel, dim3((P.n_tiles + 255) / 256), dim3(256), 0, stream, s->d_tile_list.p, P.n_tiles, s->d_tile_slot.p, tiles_total, 1);
+    HIP_TRY(hipGetLastError());
+  }
+  // (launches with a work order: order_forecast_kernel zeroes the counters on its way)
+  if (!L.history && L.engine != 2) HIP_TRY(hipMemsetAsync(s->d_work, 0, 16 * sizeof(unsigned), stream));
   if (!s->dev_uploaded_valid || memcmp(&s->dev_uploaded, &s->dev, sizeof(DevScene)) != 0) {  // (nearly never: the scene description changes with the lights, the traversal mode, the layout)
     HIP_TRY(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, stream));
     memcpy(&s->dev_uploaded, &s->dev, sizeof(DevScene));
     s->dev_uploaded_valid = true;
   }
-  // events: [0] -> [1] forecast / classification + work order; [1] -> [2] the frame kernel
   hipEvent_t *ek = s->ev_k[s->launches_timed % mt_scene::kTimedLaunches];
   for (int i = 0; i < 3; i++) {
     if (!ek[i]) HIP_TRY(hipEventCreate(&ek[i]));
   }
   HIP_TRY(hipEventRecord(ek[0], stream));
-  // Has the camera moved since the costs were measured?  Then forecast_kernel
-  // re-projects them (radius 1 block; 2 when the origin moved too: parallax).
-  int reproject = 0, radius = 0;
-  float blend = 0.0f;  // see forecast_kernel
-  // Did the frame that measured the costs have pixels whose primary rays had a zero direction component?  Found on the
-  // host, exactly: per scanline and component the direction is r + dp x with r = start + ds y (the kernels' own
-  // expression, Sensor::GetRay), zero for at most the pixels next to -r / dp -- a whole column or row for a camera on
-  // an axis, isolated pixels for one with roll or pitch.  Those blocks' costs are skipped by a re-projected forecast
-  // (forecast_kernel).
-  auto has_zero_component_pixel = [&](const mt_sensor &o) -> int {
-    for (int k = 0; k < 3; k++) {
-      for (int y = 0; y < image_h; y++) {
-        const double r = o.start_point[k] + o.delta_scanline[k] * (double)y;
-        if (o.delta_pixel[k] == 0.0 || !std::isfinite(r / o.delta_pixel[k])) {
-          if (r + o.delta_pixel[k] * 0.0 == 0.0) return 1;
-          continue;
-        }
-        const double x0 = std::nearbyint(-r / o.delta_pixel[k]);
-        for (int dx = -1; dx <= 1; dx++) {
-          const double x = x0 + dx;
-          if (x >= 0.0 && x < (double)image_w && r + o.delta_pixel[k] * x == 0.0) return 1;
-        }
-      }
-    }
-    return 0;
-  };
-  int old_irr = 0, new_irr = 0;
-  if (history) {  // (kept per sensor: a camera at rest is looked at once)
-    if (!s->irr_sensor_valid || memcmp(&s->irr_sensor, sensor, sizeof(mt_sensor)) != 0 || s->irr_w != image_w || s->irr_h != image_h) {
-      s->irr_sensor = *sensor; s->irr_w = image_w; s->irr_h = image_h;
-      s->irr_sensor_has = has_zero_component_pixel(*sensor);
-      s->irr_sensor_valid = true;
-    }
-    new_irr = s->irr_sensor_has;
-  }
-  if (history && memcmp(&s->cost_sensor, sensor, sizeof(mt_sensor)) != 0) {
-    old_irr = has_zero_component_pixel(s->cost_sensor);
-    reproject = 1;
-    radius = memcmp(s->cost_sensor.origin, sensor->origin, sizeof sensor->origin) != 0 ? 2 : 1;
-    if (s->tune.v[MT_TUNE_FORECAST_RADIUS] >= 0.0) radius = (int)s->tune.v[MT_TUNE_FORECAST_RADIUS];
-  }
-  if (history && !reproject && !from_map && s->forecasts_in_a_row > 0) {
-    // swept (scripts/blend_sweep.py, state machine, 64 frames): 0 -> every other frame 6 % slower (mean 7.09 ms), 0.5 -> one
-    // in three (7.03), 0.9 -> one in eight (7.01); a frozen forecast (1.0) repeats its frame time to 0.2 % (scripts/alternation.py)
-    // (a running mean of the measurements first -- 1/2, 2/3, ... -- so that the first frames' costs, measured under a
-    // guessed order, do not linger)
-    const float cap = (float)s->tune.v[MT_TUNE_BLEND];
-    blend = std::min(cap, (float)s->forecasts_in_a_row / (float)(s->forecasts_in_a_row + 1));
-  }
   // (the two measurements of a block belong to ONE camera, geometry and set of lights)
   if (s->forecasts_in_a_row == 0) HIP_TRY(hipMemsetAsync(s->d_item_forms, 0, (size_t)P.n_items * 8, stream));
-  // (a forecast made from the OTHER engine's costs -- the frame after a first frame -- does not count: the next one
-  // starts the running mean with this engine's own measurement)
-  s->forecasts_in_a_row = (history && !reproject && !from_map && s->last_engine == engine) ? s->forecasts_in_a_row + 1 : 0;
-  if (pool_engine) {
-    if (!history) {
-      MT_LAUNCH_D(probe_kernel, dim3((4 * P.n_items + block.x - 1) / block.x), block, s->lds_bytes, stream, s->dev, P);
-      HIP_TRY(hipGetLastError());
-    }
-    // blocks above cut_share of an even split of the frame are handed out in pieces
-    const double *tv = s->tune.v;
-    SchedParams sp{history ? 1.0f : 0.3f, {1.0f, (float)tv[MT_TUNE_POOL_PIECE_TIME1], (float)tv[MT_TUNE_POOL_PIECE_TIME2]},
-                   {1.0f, (float)tv[MT_TUNE_POOL_PIECE_WORK1], (float)tv[MT_TUNE_POOL_PIECE_WORK2]},
-                   (float)tv[MT_TUNE_POOL_CELL_FACTOR],
-                   (!from_map && (!history || s->last_engine == 2)) ? 1 : 0};  // a forecast is cut more eagerly (own_costs: granularity in bits 30-31)
-    if (tv[MT_TUNE_POOL_CUT_SHARE] >= 0.0) sp.cut_share = (float)tv[MT_TUNE_POOL_CUT_SHARE];
-    ForecastArgs fa{s->cost_sensor, reproject, radius, (history && (s->last_engine == 1 || s->last_engine == 3)) ? 0 : 1,
-                    (history && s->last_engine == 1) ? 1.7f : sp.piece_work[1], sp.piece_work[2], 16000u, blend,
-                    (history && s->last_engine == 3) ? s->d_item_form : nullptr, (float)tv[MT_TUNE_HYBRID_WORK1],
-                    (float)tv[MT_TUNE_HYBRID_WORK2], (float)tv[MT_TUNE_FORECAST_STEP], (float)tv[MT_TUNE_SM_CELL_WORK], old_irr, new_irr};
-    OrderArgs oa{};
-    oa.n_waves = s->grid_blocks * s->waves_per_block;
-    oa.epoch = s->order_epoch++;
-    const int ord_groups = std::max(1, std::min((int)s->tune.v[MT_TUNE_ORDER_GROUPS], kOrdGroupsMax));
-    oa.sp = sp;
-    hipLaunchKernelGGL(order_forecast_kernel<2>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, fa, oa);
-        hipLaunchKernelGGL(order_count_kernel<2>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
-        hipLaunchKernelGGL(order_scatter_kernel<2>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
+  const dim3 grid(s->grid_blocks), block(s->waves_per_block * 64);
+  const LayoutKernels &k = kernels_of(s->deep);
+  const int stats = s->stats_enabled ? 1 : 0;
+  if (L.engine == 2 && !L.history) {
+    hipLaunchKernelGGL(k.probe, dim3((4 * P.n_items + block.x - 1) / block.x), block, s->lds_bytes, stream, s->dev, P);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ek[1], stream));
-    MT_LAUNCH_SD(pool_kernel, s->stats_enabled, grid, block, s->lds_bytes, stream, s->dev, P);
-  } else {
-    if (history) {
-      // blocks above this share of an even split are cut into quarters; a re-projected forecast (moving camera) is
-      // cut more eagerly -- it is a neighbourhood maximum of stale costs (swept, scripts/quad_sweep.py: repeated frame
-      // 0.6 / 0.8 / 1.0 -> 7.18 / 6.84 / 7.28 ms, moving camera 6.69 / 7.20 / 9.89; with work 1.5: share 0.7 -> 6.40)
-      // (with the per-block ratio of the two forms' costs -- forecast_kernel -- the repeated frame no longer alternates,
-      // and re-swept: 0.8 / 0.9 / 0.95 / 1.0 / 1.05 / 1.1 -> 6.67 / 6.49 / 6.47 / 6.46 / 6.56 / 6.93 ms)
-      const float quad_share = (float)s->tune.v[reproject ? MT_TUNE_QUAD_SHARE_MOVING : MT_TUNE_QUAD_SHARE];  // 0.7 / 0.95
-      // ... and stay so above this fraction of that threshold (1 = no hysteresis: swept, scripts/quad_sweep.py --
-      // settings that steady the repeated frame cost the moving camera 50 %)
-      const float quad_keep = (float)s->tune.v[MT_TUNE_QUAD_KEEP];
-      // work of a block rendered as quarters / rendered whole (swept with the share): 1.5 / 1.7
-      const float quad_work = (float)s->tune.v[reproject ? MT_TUNE_QUAD_WORK_MOVING : MT_TUNE_QUAD_WORK];
-      const double *tv = s->tune.v;
-      ForecastArgs fa{s->cost_sensor, reproject, radius, s->last_engine == 2 ? 1 : 0, s->last_engine == 2 ? 1.1f : quad_work, 3.0f,
-                      16000u, blend, s->last_engine == 3 ? s->d_item_form : nullptr, (float)tv[MT_TUNE_HYBRID_WORK1],
-                      (float)tv[MT_TUNE_HYBRID_WORK2], (float)tv[MT_TUNE_FORECAST_STEP], (float)tv[MT_TUNE_SM_CELL_WORK], old_irr, new_irr};
-      OrderArgs oa{};
-      oa.n_waves = s->grid_blocks * s->waves_per_block;
-      oa.epoch = s->order_epoch++;
-    const int ord_groups = std::max(1, std::min((int)s->tune.v[MT_TUNE_ORDER_GROUPS], kOrdGroupsMax));
-      if (hybrid) {
-        const float k = reproject ? (float)(tv[MT_TUNE_QUAD_SHARE_MOVING] / tv[MT_TUNE_QUAD_SHARE]) : 1.0f;  // a re-projected forecast is cut more eagerly
-        oa.quad_share = k * (float)tv[MT_TUNE_HYBRID_QUAD_SHARE];
-        oa.pool_share = k * (float)tv[MT_TUNE_HYBRID_POOL_SHARE];
-        oa.piece_time1 = (float)tv[MT_TUNE_POOL_PIECE_TIME1];
-        oa.piece_time2 = (float)tv[MT_TUNE_POOL_PIECE_TIME2];
-        oa.cell_factor = (float)tv[MT_TUNE_HYBRID_CELL_FACTOR];
-        oa.form_out = s->d_item_form;
-        oa.starter_share = (float)tv[MT_TUNE_HYBRID_STARTER_SHARE];
-        oa.max_starters = (unsigned)std::min(s->grid_blocks, (int)(0.25 * s->grid_blocks * s->waves_per_block));
-        hipLaunchKernelGGL(order_forecast_kernel<1>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, fa, oa);
-        hipLaunchKernelGGL(order_count_kernel<1>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
-        hipLaunchKernelGGL(order_scatter_kernel<1>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
-      } else {
-        oa.quad_share = quad_share;
-        oa.quad_keep = quad_keep;
-        oa.cell_share = (float)tv[MT_TUNE_SM_CELL_SHARE];
-        // (cells only on MEASURED costs: a re-projected forecast of such a block is a guess -- thirty times a mean block --
-        // that cannot tell the loft's column, 1.4 frames long as quarters, from the room's, 0.87: room panning +0.5 % with
-        // the guess trusted, loft -2 %)
-        oa.new_irr = reproject ? 0 : new_irr;
-        oa.cell_time = (float)tv[MT_TUNE_SM_CELL_TIME];
-        oa.queue_mode = (int)tv[MT_TUNE_XCD_QUEUES];
-        hipLaunchKernelGGL(order_forecast_kernel<0>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, fa, oa);
-        hipLaunchKernelGGL(order_count_kernel<0>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
-        hipLaunchKernelGGL(order_scatter_kernel<0>, dim3(ord_groups), dim3(kOrdThreads), 0, stream, P, oa);
-      }
-    } else {
-      MT_LAUNCH_SD(primary_kernel, s->stats_enabled, grid, block, s->lds_bytes, stream, s->dev, P);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ek[1], stream));
-    if (hybrid) {
-      MT_LAUNCH_SD(hybrid_kernel, s->stats_enabled, grid, block, s->lds_bytes, stream, s->dev, P);
-    } else {
-      MT_LAUNCH_SD(render_kernel, s->stats_enabled, grid, block, s->lds_bytes, stream, s->dev, P);
-    }
   }
+  if (L.engine == 2 || L.history) launch_work_order(s, L, P, stream);
+  else hipLaunchKernelGGL(k.primary[stats], grid, block, s->lds_bytes, stream, s->dev, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ek[1], stream));
+  const SceneKernel *frame = L.engine == 2 ? k.pool : (L.engine == 3 ? k.hybrid : k.render);
+  hipLaunchKernelGGL(frame[stats], grid, block, s->lds_bytes, stream, s->dev, P);
   HIP_TRY(hipEventRecord(ek[2], stream));
   HIP_TRY(hipGetLastError());
-  s->launches_timed++;
-  s->last_P = P;
-  s->last_P_valid = true;
-  s->cost_signature = (d_list != nullptr && list_id == 0) ? 0 : sig;  // the costs now in d_item_cost belong to this geometry and engine
-  s->last_engine = engine;
-  s->cost_sensor = *sensor;
-  if (s->dbg_print_units) {  // -DMT_DEBUG_KNOBS: how many work units did the order have?
+  return MT_OK;
+}
+
+// -DMT_DEBUG_KNOBS facilities, after a launch: the work order's unit count, the per-item cycle dump (d_item), the
+// heartbeat watchdog
+int debug_after_launch(mt_scene *s, const RenderParams &P, const unsigned long long *d_item, hipStream_t stream) {
+  if (s->dbg_print_units) {  // how many work units did the order have?
     if (s->dbg_print_units == 2) {  // without synchronising: kept in a ring, printed every 16th launch
       static unsigned *ring = nullptr;
       static unsigned long long n = 0;
@@ -733,11 +706,10 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
       fprintf(stderr, "[mt units] %u units for %u blocks\n", nw, P.n_items);
     }
   }
-  if (d_item) {  // debug: dump per-item durations (synchronises!)
+  if (d_item) {  // dump per-item durations (synchronises!)
     std::vector<unsigned long long> host((size_t)P.n_items * 16 * 2 * 4);
     HIP_TRY(hipMemcpy(host.data(), d_item, host.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_item));
-    if (FILE *f = fopen(item_dump, "wb")) {
+    if (FILE *f = fopen(s->dbg_item_cycles.c_str(), "wb")) {
       fwrite(host.data(), 8, host.size(), f);
       fclose(f);
     }
@@ -770,6 +742,57 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   return MT_OK;
 }
 
+int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int rx, int ry,
+                  int rw, int rh, int tile_w, int tile_h, int first_tile, int tile_stride,
+                  int n_tiles, int max_depth, uint8_t *d_rgb, mt_debug_px *d_debug,
+                  hipStream_t stream, const int32_t *d_list = nullptr, unsigned long long list_id = 0) {
+  if (max_depth < 0 || max_depth > MT_MAX_RECURSION) {
+    return fail(MT_ERR_ARG, "max_depth %d outside [0, %d]", max_depth, MT_MAX_RECURSION);
+  }
+  RenderParams P{};
+  P.sensor = *sensor;
+  P.image_w = image_w;
+  P.image_h = image_h;
+  P.region_x = rx; P.region_y = ry; P.region_w = rw; P.region_h = rh;
+  P.tile_w = tile_w; P.tile_h = tile_h;
+  P.tiles_x = (rw + tile_w - 1) / tile_w;
+  P.first_tile = first_tile; P.tile_stride = tile_stride; P.n_tiles = n_tiles;
+  P.blocks_x = (tile_w + 7) / 8;
+  P.blocks_y = (tile_h + 7) / 8;
+  P.max_depth = max_depth;
+  const unsigned long long items = (unsigned long long)n_tiles * P.blocks_x * P.blocks_y;
+  if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
+  P.n_items = (unsigned)items;
+  P.out_rgb = d_rgb;
+  P.out_debug = d_debug;
+  P.counters = s->d_counters;
+  P.work_counter = s->d_work;
+  const size_t waves = (size_t)s->grid_blocks * s->waves_per_block;
+  LaunchPlan L;
+  MT_TRY(decide_launch(s, P, sensor, d_debug != nullptr, d_list, list_id, waves, L));
+  P.from_primary = L.history ? 0 : 1;
+  P.from_map = L.from_map ? 1 : 0;
+  MT_TRY(size_buffers(s, L, d_list, waves, P));
+  if (P.n_items == 0) return MT_OK;
+  Buf<unsigned long long> item_cycles;  // -DMT_DEBUG_KNOBS: MT_DEBUG_ITEM_CYCLES
+  if (!s->dbg_item_cycles.empty()) {
+    MT_TRY(item_cycles.ensure((size_t)P.n_items * 16 * 16 * 4));
+    HIP_TRY(hipMemset(item_cycles, 0, (size_t)P.n_items * 16 * 16 * 4));
+    P.item_cycles = item_cycles;
+  }
+  MT_TRY(launch_kernels(s, L, P, d_list, stream));
+  // the scene's bookkeeping.  (A forecast made from the OTHER engine's costs -- the frame after a first frame -- does
+  // not count: the next one starts the running mean with this engine's own measurement.)
+  s->forecasts_in_a_row = (L.history && !L.reproject && !L.from_map && s->last_engine == L.engine) ? s->forecasts_in_a_row + 1 : 0;
+  s->launches_timed++;
+  s->last_P = P;
+  s->last_P_valid = true;
+  s->cost_signature = (d_list != nullptr && list_id == 0) ? 0 : L.sig;  // the costs now in d_item_cost belong to this geometry and engine
+  s->last_engine = L.engine;
+  s->cost_sensor = *sensor;
+  return debug_after_launch(s, P, item_cycles, stream);
+}
+
 int check_status(const unsigned long long *c) {
   if (c[ST_STATUS] == DEV_OK) return MT_OK;
   return fail(MT_ERR_INTERNAL, "device loop bound tripped (code %llu): kernel logic error", c[ST_STATUS]);
@@ -799,6 +822,25 @@ int check_image_args(const mt_scene *s, const mt_sensor *sensor, int image_w, in
   return MT_OK;
 }
 
+// the arguments of a tiled launch: first_tile + k tile_stride, k < n_tiles
+int check_tiling(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int tile_w, int tile_h,
+                 int first_tile, int tile_stride, int n_tiles) {
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  if (tile_w <= 0 || tile_h <= 0 || first_tile < 0 || tile_stride <= 0 || n_tiles < 0) {
+    return fail(MT_ERR_ARG, "bad tiling arguments");
+  }
+  return MT_OK;
+}
+
+// ... and are those tiles of the image?
+int check_tile_selection(int image_w, int image_h, int tile_w, int tile_h, int first_tile, int tile_stride, int n_tiles) {
+  const long long tiles_total = tile_count(image_w, image_h, tile_w, tile_h);
+  if (n_tiles > 0 && (long long)first_tile + (long long)(n_tiles - 1) * tile_stride >= tiles_total) {
+    return fail(MT_ERR_ARG, "tile selection exceeds the %lld tiles of the image", tiles_total);
+  }
+  return MT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -815,43 +857,12 @@ int mt_device_count(void) {
 
 void mt_scene_destroy(mt_scene *s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);
+  (void)hipSetDevice(s->device);  // (the buffers are freed with the scene)
   for (void *p : s->allocs) (void)hipFree(p);
-  if (s->d_pool) (void)hipFree(s->d_pool);
-  if (s->d_frames) (void)hipFree(s->d_frames);
-  if (s->d_hit_prim) (void)hipFree(s->d_hit_prim);
-  if (s->d_hit_t) (void)hipFree(s->d_hit_t);
-  if (s->d_class_list) (void)hipFree(s->d_class_list);
-  if (s->d_item_cost) (void)hipFree(s->d_item_cost);
-  if (s->d_item_forecast) (void)hipFree(s->d_item_forecast);
-  if (s->d_item_forms) (void)hipFree(s->d_item_forms);
-  if (s->d_item_form) (void)hipFree(s->d_item_form);
-  if (s->d_cost_map) (void)hipFree(s->d_cost_map);
-  if (s->d_order_item) (void)hipFree(s->d_order_item);
-  if (s->d_item_cell) (void)hipFree(s->d_item_cell);
-  if (s->d_item_unit) (void)hipFree(s->d_item_unit);
-  if (s->d_order_sub) (void)hipFree(s->d_order_sub);
-  if (s->d_rgb) (void)hipFree(s->d_rgb);
-  if (s->d_debug) (void)hipFree(s->d_debug);
-  if (s->d_lights) (void)hipFree(s->d_lights);
-  if (s->h_stage) (void)hipHostFree(s->h_stage);
   for (hipEvent_t e : s->ev_stage) {
     if (e) (void)hipEventDestroy(e);
   }
-  if (s->h_counters) (void)hipHostFree(s->h_counters);
-  if (s->d_deep) (void)hipFree(s->d_deep);
-  if (s->d_tile_list) (void)hipFree(s->d_tile_list);
-  if (s->d_tile_slot) (void)hipFree(s->d_tile_slot);
-  if (s->d_tile_cost) (void)hipFree(s->d_tile_cost);
-  if (s->d_multi_order) (void)hipFree(s->d_multi_order);
-  if (s->d_multi_list) (void)hipFree(s->d_multi_list);
-  if (s->d_multi_lists) (void)hipFree(s->d_multi_lists);
-  if (s->d_multi_tiles) (void)hipFree(s->d_multi_tiles);
-  if (s->d_multi_map) (void)hipFree(s->d_multi_map);
-  if (s->d_multi_maps) (void)hipFree(s->d_multi_maps);
   if (s->multi_comb_done) (void)hipEventDestroy(s->multi_comb_done);
-  if (s->d_multi_gather) (void)hipFree(s->d_multi_gather);
-  if (s->d_multi_frame) (void)hipFree(s->d_multi_frame);
   if (s->multi_stream) (void)hipStreamDestroy(s->multi_stream);
   if (s->multi_done) (void)hipEventDestroy(s->multi_done);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -1260,41 +1271,26 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   s->dev.tree_depth = max_depth;
   s->dev.force_mode = 0;
   s->dev.scene_regular = regular ? 1 : 0;
-  {
-    // 16-byte traversal stack frames when "first child" and "best triangle + 1"
-    // share one word: a quarter less LDS per wave
-    int tri_bits = 1;
-    while (tri_bits < 31 && ((long long)d->n_tris + 1) > (1ll << tri_bits)) tri_bits++;
-    int node_bits = 1;
-    while (node_bits < 31 && (long long)nn > (1ll << node_bits)) node_bits++;
-    s->dev.pack_shift = (tri_bits + node_bits <= 32) ? tri_bits : 0;  // (MT_TUNE_PACKED_STACK = 0 switches it off)
-  }
+  s->dev.pack_shift = pack_shift_for(d->n_tris, nn);  // (MT_TUNE_PACKED_STACK = 0 switches it off)
   s->dev.n_lights = 0;
   s->dev.lights = nullptr;
-  HIP_TRY(hipMalloc((void **)&s->d_counters, ST_COUNT * sizeof(unsigned long long)));
-  s->allocs.push_back(s->d_counters);
+  MT_TRY(s->d_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc((void **)&s->d_work, 64));
-  s->allocs.push_back(s->d_work);
-  HIP_TRY(hipMalloc((void **)&s->d_queues, kQueueWords * sizeof(unsigned)));
-  s->allocs.push_back(s->d_queues);
-  HIP_TRY(hipMalloc((void **)&s->d_order_ctl, kOrdWords * sizeof(unsigned)));
-  s->allocs.push_back(s->d_order_ctl);
+  MT_TRY(s->d_work.ensure(64));
+  MT_TRY(s->d_queues.ensure(kQueueWords * sizeof(unsigned)));
+  MT_TRY(s->d_order_ctl.ensure(kOrdWords * sizeof(unsigned)));
   HIP_TRY(hipMemset(s->d_order_ctl, 0, kOrdWords * sizeof(unsigned)));
-  HIP_TRY(hipMalloc((void **)&s->d_order_whist, (size_t)kOrdGroupsMax * kOrdKeysMax * sizeof(unsigned)));
-  s->allocs.push_back(s->d_order_whist);
+  MT_TRY(s->d_order_whist.ensure((size_t)kOrdGroupsMax * kOrdKeysMax * sizeof(unsigned)));
   HIP_TRY(hipEventCreate(&s->ev0));
   HIP_TRY(hipEventCreate(&s->ev1));
   if ((rc = mt_scene_set_lights(s, nullptr, 0)) != MT_OK) return rc;
   s->dev.hb = nullptr;
   s->dev.prof = nullptr;
-  HIP_TRY(hipMalloc((void **)&s->d_dev, sizeof(DevScene)));
-  s->allocs.push_back(s->d_dev);
+  MT_TRY(s->d_dev.ensure(sizeof(DevScene)));
   s->dev.self = s->d_dev;
 #ifdef MT_PROF
   // (behind the phase sums: a time line of one wave, -DMT_PROF builds only -- kProfTimeline stamps)
-  HIP_TRY(hipMalloc((void **)&s->d_prof, (PROF_COUNT + 1 + kProfTimeline) * sizeof(unsigned long long)));
-  s->allocs.push_back(s->d_prof);
+  MT_TRY(s->d_prof.ensure((PROF_COUNT + 1 + kProfTimeline) * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(s->d_prof, 0, (PROF_COUNT + 1 + kProfTimeline) * sizeof(unsigned long long)));
   s->dev.prof = s->d_prof;
 #endif
@@ -1307,7 +1303,7 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   const bool heartbeat = false;
 #endif
   if (heartbeat) {
-    HIP_TRY(hipHostMalloc((void **)&s->hb_host, 65536 * sizeof(unsigned long long), hipHostMallocMapped));
+    MT_TRY(s->hb_host.ensure(65536 * sizeof(unsigned long long), hipHostMallocMapped));
     memset(s->hb_host, 0, 65536 * sizeof(unsigned long long));
     void *dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, s->hb_host, 0));
@@ -1333,13 +1329,7 @@ mt_scene *mt_scene_create(const mt_scene_desc *d) {
 int mt_scene_set_lights(mt_scene *s, const mt_light *lights, int n) {
   if (!s || n < 0 || (n > 0 && !lights)) return fail(MT_ERR_ARG, "bad lights argument");
   HIP_TRY(hipSetDevice(s->device));
-  if (n > s->lights_cap || !s->d_lights) {
-    if (s->d_lights) HIP_TRY(hipFree(s->d_lights));
-    s->d_lights = nullptr;
-    const int cap = n > 8 ? n : 8;
-    HIP_TRY(hipMalloc((void **)&s->d_lights, (size_t)cap * sizeof(mt_light)));
-    s->lights_cap = cap;
-  }
+  MT_TRY(s->d_lights.ensure((size_t)(n > 8 ? n : 8) * sizeof(mt_light)));
   // The reference's drivers push the same lights again before every frame (main_local.cc:79-110): what the device
   // holds already is not uploaded again.  Other lights, other costs: the damped forecast starts over (the old costs
   // remain its first guess).
@@ -1425,13 +1415,7 @@ int mt_scene_set_tuning(mt_scene *s, int knob, double value) {
   s->tune.v[knob] = value;
   s->cost_signature = 0;  // other constants, other order: start from a first frame
   if (knob == MT_TUNE_PACKED_STACK || knob == MT_TUNE_BLOCKS_PER_CU || knob == MT_TUNE_DEEP_LAYOUT) {
-    if (knob == MT_TUNE_PACKED_STACK) {
-      int tri_bits = 1;
-      while (tri_bits < 31 && ((long long)s->dev.n_tris + 1) > (1ll << tri_bits)) tri_bits++;
-      int node_bits = 1;
-      while (node_bits < 31 && (long long)s->dev.n_nodes > (1ll << node_bits)) node_bits++;
-      s->dev.pack_shift = (value != 0.0 && tri_bits + node_bits <= 32) ? tri_bits : 0;
-    }
+    if (knob == MT_TUNE_PACKED_STACK) s->dev.pack_shift = value != 0.0 ? pack_shift_for(s->dev.n_tris, s->dev.n_nodes) : 0;
     HIP_TRY(hipSetDevice(s->device));
     return configure_launch(s);
   }
@@ -1461,8 +1445,7 @@ int mt_scene_import_costs_device(mt_scene *s, const void *d_map, int map_w, int 
   if (!s || !d_map || map_w <= 0 || map_h <= 0) return fail(MT_ERR_ARG, "bad cost map arguments");
   HIP_TRY(hipSetDevice(s->device));
   const size_t bytes = (size_t)map_w * (size_t)map_h * sizeof(unsigned);
-  int rc = ensure_bytes((void **)&s->d_cost_map, &s->cost_map_bytes, bytes);
-  if (rc != MT_OK) return rc;
+  MT_TRY(s->d_cost_map.ensure(bytes));
   HIP_TRY(hipMemcpyAsync(s->d_cost_map, d_map, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   s->cost_map_w = map_w;
   s->cost_map_h = map_h;
@@ -1534,8 +1517,7 @@ int mt_scene_kernel_times(mt_scene *s, int max_n, double *primary_ms, double *re
 int mt_render_chunk_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h,
                            int chunk_x, int chunk_y, int chunk_w, int chunk_h, int max_depth,
                            void *d_rgb, void *d_debug, void *stream) {
-  int rc = check_image_args(s, sensor, image_w, image_h);
-  if (rc != MT_OK) return rc;
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
   // WorkChunk::DeserializeInput's constraints, mythtracer.cc:358-371
   if (chunk_x < 0 || chunk_y < 0 || chunk_w <= 0 || chunk_h <= 0 ||
       (long long)chunk_x + chunk_w > image_w || (long long)chunk_y + chunk_h > image_h) {
@@ -1552,16 +1534,8 @@ int mt_render_chunk_device(mt_scene *s, const mt_sensor *sensor, int image_w, in
 int mt_render_tiles_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h,
                            int tile_w, int tile_h, int first_tile, int tile_stride, int n_tiles,
                            int max_depth, void *d_rgb, void *stream) {
-  int rc = check_image_args(s, sensor, image_w, image_h);
-  if (rc != MT_OK) return rc;
-  if (tile_w <= 0 || tile_h <= 0 || first_tile < 0 || tile_stride <= 0 || n_tiles < 0) {
-    return fail(MT_ERR_ARG, "bad tiling arguments");
-  }
-  const long long tiles_total =
-      (long long)((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
-  if (n_tiles > 0 && (long long)first_tile + (long long)(n_tiles - 1) * tile_stride >= tiles_total) {
-    return fail(MT_ERR_ARG, "tile selection exceeds the %lld tiles of the image", tiles_total);
-  }
+  MT_TRY(check_tiling(s, sensor, image_w, image_h, tile_w, tile_h, first_tile, tile_stride, n_tiles));
+  MT_TRY(check_tile_selection(image_w, image_h, tile_w, tile_h, first_tile, tile_stride, n_tiles));
   if (!d_rgb && n_tiles > 0) return fail(MT_ERR_ARG, "d_rgb is NULL");
   HIP_TRY(hipSetDevice(s->device));
   return launch_render(s, sensor, image_w, image_h, 0, 0, image_w, image_h, tile_w, tile_h,
@@ -1576,15 +1550,11 @@ int mt_blit_tiles_device(mt_scene *s, int image_w, int image_h, int tile_w, int 
       first_tile < 0 || tile_stride <= 0 || n_tiles < 0) {
     return fail(MT_ERR_ARG, "bad blit arguments");
   }
-  const int tiles_x = (image_w + tile_w - 1) / tile_w;
-  const long long tiles_total = (long long)tiles_x * ((image_h + tile_h - 1) / tile_h);
-  if (n_tiles > 0 && (long long)first_tile + (long long)(n_tiles - 1) * tile_stride >= tiles_total) {
-    return fail(MT_ERR_ARG, "tile selection exceeds the %lld tiles of the image", tiles_total);
-  }
+  MT_TRY(check_tile_selection(image_w, image_h, tile_w, tile_h, first_tile, tile_stride, n_tiles));
   if (n_tiles == 0) return MT_OK;
   HIP_TRY(hipSetDevice(s->device));
   hipLaunchKernelGGL(blit_tiles_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, image_w,
-                     image_h, tile_w, tile_h, tiles_x, first_tile, tile_stride, n_tiles, (const int32_t *)nullptr,
+                     image_h, tile_w, tile_h, (image_w + tile_w - 1) / tile_w, first_tile, tile_stride, n_tiles, (const int32_t *)nullptr,
                      (const uint8_t *)d_tiles, (uint8_t *)d_image);
   HIP_TRY(hipGetLastError());
   return MT_OK;
@@ -1598,11 +1568,10 @@ int mt_order_tiles_device(mt_scene *s, const void *d_cost_map, int map_w, int ma
   }
   if (map_w < (image_w + 7) / 8 || map_h < (image_h + 7) / 8) return fail(MT_ERR_ARG, "cost map smaller than the image's 8x8 blocks");
   const int tiles_x = (image_w + tile_w - 1) / tile_w;
-  const long long total = (long long)tiles_x * ((image_h + tile_h - 1) / tile_h);
+  const long long total = tile_count(image_w, image_h, tile_w, tile_h);
   if (total > (1ll << 20)) return fail(MT_ERR_ARG, "too many tiles to order (%lld)", total);
   HIP_TRY(hipSetDevice(s->device));
-  int rc = ensure_bytes((void **)&s->d_tile_cost, &s->tile_cost_bytes, (size_t)total * 8);
-  if (rc != MT_OK) return rc;
+  MT_TRY(s->d_tile_cost.ensure((size_t)total * 8));
   const int n = (int)total;
   hipLaunchKernelGGL(tile_cost_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const unsigned *)d_cost_map,
                      map_w, map_h, image_w, image_h, tile_w, tile_h, tiles_x, n, s->d_tile_cost);
@@ -1615,7 +1584,7 @@ int mt_dealt_tile_count(int image_w, int image_h, int tile_w, int tile_h, int wo
   if (image_w <= 0 || image_h <= 0 || tile_w <= 0 || tile_h <= 0 || world < 1 || rank < 0 || rank >= world) {
     return fail(MT_ERR_ARG, "bad tile count arguments");
   }
-  const long long total = (long long)((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
+  const long long total = tile_count(image_w, image_h, tile_w, tile_h);
   if (total > 0x7fffffffll) return fail(MT_ERR_ARG, "too many tiles");
   return dealt_tile_count((int)total, world, rank);
 }
@@ -1625,7 +1594,7 @@ int mt_deal_tiles_device(mt_scene *s, const void *d_order, int image_w, int imag
   if (!s || !d_list) return fail(MT_ERR_ARG, "bad deal arguments");
   const int n = mt_dealt_tile_count(image_w, image_h, tile_w, tile_h, world, rank);
   if (n <= 0) return n;
-  const int total = ((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
+  const int total = (int)tile_count(image_w, image_h, tile_w, tile_h);
   HIP_TRY(hipSetDevice(s->device));
   hipLaunchKernelGGL(deal_tiles_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int32_t *)d_order, total,
                      world, rank, n, (int32_t *)d_list);
@@ -1636,10 +1605,8 @@ int mt_deal_tiles_device(mt_scene *s, const void *d_order, int image_w, int imag
 int mt_render_tile_list_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int tile_w, int tile_h,
                                const void *d_list, int n_tiles, uint64_t list_id, int max_depth, void *d_rgb,
                                void *stream) {
-  int rc = check_image_args(s, sensor, image_w, image_h);
-  if (rc != MT_OK) return rc;
-  if (tile_w <= 0 || tile_h <= 0 || n_tiles < 0) return fail(MT_ERR_ARG, "bad tiling arguments");
-  const long long tiles_total = (long long)((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
+  MT_TRY(check_tiling(s, sensor, image_w, image_h, tile_w, tile_h, 0, 1, n_tiles));
+  const long long tiles_total = tile_count(image_w, image_h, tile_w, tile_h);
   if (n_tiles > tiles_total) return fail(MT_ERR_ARG, "%d tiles listed, the image has %lld", n_tiles, tiles_total);
   if (n_tiles > 0 && (!d_rgb || !d_list)) return fail(MT_ERR_ARG, "d_rgb or d_list is NULL");
   HIP_TRY(hipSetDevice(s->device));
@@ -1671,13 +1638,9 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
   const auto w0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)(chunk_w > 0 ? chunk_w : 0) * (size_t)(chunk_h > 0 ? chunk_h : 0);
-  if ((rc = ensure_bytes((void **)&s->d_rgb, &s->rgb_bytes, npx * 3)) != MT_OK) return rc;
-  if (out_debug) {
-    if ((rc = ensure_bytes((void **)&s->d_debug, &s->debug_bytes, npx * sizeof(mt_debug_px))) != MT_OK) {
-      return rc;
-    }
-  }
-  if (!s->h_counters) HIP_TRY(hipHostMalloc((void **)&s->h_counters, ST_COUNT * sizeof(unsigned long long), hipHostMallocDefault));
+  MT_TRY(s->d_rgb.ensure(npx * 3));
+  if (out_debug) MT_TRY(s->d_debug.ensure(npx * sizeof(mt_debug_px)));
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   // How the frame reaches the caller's (pageable) buffer, measured on the box (scripts/ubench/d2h_paths.hip, 6.2 MB of
   // a 1080p frame / 24.9 MB of a 4K one): plain hipMemcpy 1.17 / 1.22 ms; a page-locked staging buffer + memcpy 0.42 /
   // 1.72 (the memcpy alone 0.30 / 1.28); registering the caller's buffer per call 0.82 / 1.22 (the registration 0.7);
@@ -1685,13 +1648,7 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
   // safe (a vector freed and allocated again at the same address would receive its frame in the OLD pages).  So: the
   // staging buffer, in pieces, every piece's memcpy under the next piece's DMA: about the memcpy's time.
   const size_t out_bytes = npx * 3;
-  if (s->stage_bytes < out_bytes) {
-    if (s->h_stage) HIP_TRY(hipHostFree(s->h_stage));
-    s->h_stage = nullptr;
-    s->stage_bytes = 0;
-    HIP_TRY(hipHostMalloc((void **)&s->h_stage, out_bytes, hipHostMallocDefault));
-    s->stage_bytes = out_bytes;
-  }
+  MT_TRY(s->h_stage.ensure(out_bytes));
   for (hipEvent_t &e : s->ev_stage) {
     if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
@@ -1701,7 +1658,7 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
   const bool counters_were = s->stats_enabled;
   if (stats) s->stats_enabled = true;  // the caller asked for them
   rc = mt_render_chunk_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h,
-                              max_depth, s->d_rgb, out_debug ? s->d_debug : nullptr, stream);
+                              max_depth, s->d_rgb, out_debug ? s->d_debug.p : nullptr, stream);
   s->stats_enabled = counters_were;
   if (rc != MT_OK) return rc;
   HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1769,7 +1726,7 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
   if (rc != MT_OK) return rc;
   if (tile_w <= 0 || tile_h <= 0) return fail(MT_ERR_ARG, "bad tile size");
   const auto w0 = std::chrono::steady_clock::now();
-  const long long tiles_total_ll = (long long)((image_w + tile_w - 1) / tile_w) * ((image_h + tile_h - 1) / tile_h);
+  const long long tiles_total_ll = tile_count(image_w, image_h, tile_w, tile_h);
   if (tiles_total_ll > (1ll << 20)) return fail(MT_ERR_ARG, "too many tiles (%lld)", tiles_total_ll);
   const int tiles_total = (int)tiles_total_ll;
   const size_t slot = (size_t)tile_w * tile_h * 3;
@@ -1786,11 +1743,7 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
   // geometry and replica list?  Then the tiles are dealt out anew by the combined costs of the previous frame -- every
   // replica holds that map and orders it by itself -- unless the camera has been at rest for two frames: from then on
   // the assignment is kept, and with it the per-slot cost history (running means, the blocks' two measured forms).
-  unsigned long long geom = 1469598103934665603ull;
-  for (long long v : {(long long)image_w, (long long)image_h, (long long)tile_w, (long long)tile_h, (long long)max_depth, (long long)n}) {
-    geom = (geom ^ (unsigned long long)v) * 1099511628211ull;
-  }
-  if (geom == 0) geom = 1;
+  const unsigned long long geom = fnv1a({image_w, image_h, tile_w, tile_h, max_depth, n});
   bool same_geom = true;
   for (int r = 0; r < n; r++) {
     same_geom = same_geom && scenes[r]->multi_geom == geom && scenes[r]->multi_rank == r &&
@@ -1803,17 +1756,25 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
   const bool redeal = !same_geom || by_map;
   static std::atomic<unsigned long long> next_list_id{1};
   const unsigned long long list_id = redeal ? next_list_id.fetch_add(1) : root->multi_list_id;
-  auto forget = [&]() {
-    for (int q = 0; q < n; q++) scenes[q]->multi_geom = 0;
-  };
-  auto drain = [&]() {  // let whatever was launched finish before the caller touches its buffers or the scenes again
+  // the one exit of a failure: let whatever was launched finish before the caller touches its buffers or the scenes
+  // again, forget the state of the previous call, report
+  auto failed = [&](int code, const std::string &text) -> int {
     for (int q = 0; q < n; q++) {
       if (scenes[q]->multi_stream) {
         (void)hipSetDevice(scenes[q]->device);
         (void)hipStreamSynchronize(scenes[q]->multi_stream);
       }
+      scenes[q]->multi_geom = 0;
     }
     (void)hipSetDevice(root->device);
+    return fail(code, "%s", text.c_str());
+  };
+  // copy between replicas: over xGMI where the devices differ (or MULTI_FORCE_PEER_COPY), else on the device
+  const bool force_peer = root->tune.v[MT_TUNE_MULTI_FORCE_PEER_COPY] != 0.0;
+  auto copy = [&](void *dst, int dst_device, const void *src, int src_device, size_t bytes, hipStream_t stream) -> int {
+    if (dst_device != src_device || force_peer) HIP_TRY(hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, stream));
+    else HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+    return MT_OK;
   };
 
   // ---- phase 1: every replica renders its tiles
@@ -1827,15 +1788,15 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
         HIP_TRY(hipStreamCreateWithFlags(&s->multi_stream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&s->multi_done, hipEventDisableTiming));
       }
-      int rc2 = ensure_bytes((void **)&s->d_multi_tiles, &s->multi_tiles_bytes, (size_t)n_max * slot);
-      if (rc2 == MT_OK) rc2 = ensure_bytes((void **)&s->d_multi_list, &s->multi_list_bytes, (size_t)n_max * 4);
-      if (rc2 != MT_OK) return rc2;
+      MT_TRY(s->d_multi_tiles.ensure((size_t)n_max * slot));
+      MT_TRY(s->d_multi_list.ensure((size_t)n_max * 4));
+      int rc2;
       if (redeal) {
         const int32_t *order = nullptr;
         if (by_map) {
-          if ((rc2 = ensure_bytes((void **)&s->d_multi_order, &s->multi_order_bytes, (size_t)tiles_total * 4)) != MT_OK) return rc2;
-          if ((rc2 = mt_order_tiles_device(s, s->d_multi_map, map_w, map_h, image_w, image_h, tile_w, tile_h,
-                                           s->d_multi_order, s->multi_stream)) != MT_OK) return rc2;
+          MT_TRY(s->d_multi_order.ensure((size_t)tiles_total * 4));
+          MT_TRY(mt_order_tiles_device(s, s->d_multi_map, map_w, map_h, image_w, image_h, tile_w, tile_h, s->d_multi_order,
+                                       s->multi_stream));
           order = s->d_multi_order;
         }
         if ((rc2 = mt_deal_tiles_device(s, order, image_w, image_h, tile_w, tile_h, n, r, s->d_multi_list, s->multi_stream)) < 0) return rc2;
@@ -1844,14 +1805,14 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
       const bool counters_were = s->stats_enabled;
       if (stats) s->stats_enabled = true;
       rc2 = launch_render(s, sensor, image_w, image_h, 0, 0, image_w, image_h, tile_w, tile_h, 0, 1, tiles_of(r),
-                          max_depth, s->d_multi_tiles, nullptr, s->multi_stream, tiles_of(r) > 0 ? s->d_multi_list : nullptr,
+                          max_depth, s->d_multi_tiles, nullptr, s->multi_stream, tiles_of(r) > 0 ? s->d_multi_list.p : nullptr,
                           list_id);
       s->stats_enabled = counters_were;
       if (rc2 != MT_OK) return rc2;
       if (share_costs) {
-        if ((rc2 = ensure_bytes((void **)&s->d_multi_map, &s->multi_map_bytes, map_bytes)) != MT_OK) return rc2;
+        MT_TRY(s->d_multi_map.ensure(map_bytes));
         HIP_TRY(hipMemsetAsync(s->d_multi_map, 0, map_bytes, s->multi_stream));
-        if (tiles_of(r) > 0 && (rc2 = mt_scene_export_costs_device(s, s->d_multi_map, map_w, map_h, s->multi_stream)) != MT_OK) return rc2;
+        if (tiles_of(r) > 0) MT_TRY(mt_scene_export_costs_device(s, s->d_multi_map, map_w, map_h, s->multi_stream));
       }
       HIP_TRY(hipEventRecord(s->multi_done, s->multi_stream));
       return MT_OK;
@@ -1868,25 +1829,20 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
     for (auto &t : th) t.join();
   }
   for (int r = 0; r < n; r++) {
-    if (rcs[(size_t)r] != MT_OK) {
-      drain();
-      forget();
-      return fail(rcs[(size_t)r], "replica %d: %s", r, errs[(size_t)r].c_str());
-    }
+    if (rcs[(size_t)r] != MT_OK) return failed(rcs[(size_t)r], "replica " + std::to_string(r) + ": " + errs[(size_t)r]);
   }
 
   // ---- phase 2: gather on the first replica's device, blit, one copy to the host.  (One exit: a failure half way
   // must not return while copies into out_rgb or kernels on the replicas' buffers are still queued.)
-  const bool force_peer = root->tune.v[MT_TUNE_MULTI_FORCE_PEER_COPY] != 0.0;
   auto phase2 = [&]() -> int {
     HIP_TRY(hipSetDevice(root->device));
-    int rc2 = ensure_bytes((void **)&root->d_multi_frame, &root->multi_frame_bytes, (size_t)image_w * image_h * 3);
-    if (rc2 == MT_OK) rc2 = ensure_bytes((void **)&root->d_multi_gather, &root->multi_gather_bytes, (size_t)n * (size_t)n_max * slot);
-    if (rc2 == MT_OK) rc2 = ensure_bytes((void **)&root->d_multi_lists, &root->multi_lists_bytes, (size_t)n * (size_t)n_max * 4);
-    if (rc2 != MT_OK) return rc2;
+    MT_TRY(root->d_multi_frame.ensure((size_t)image_w * image_h * 3));
+    MT_TRY(root->d_multi_gather.ensure((size_t)n * (size_t)n_max * slot));
+    MT_TRY(root->d_multi_lists.ensure((size_t)n * (size_t)n_max * 4));
+    int rc2;
     if (redeal) {  // every replica's list, for the blit: the same order, dealt out for every rank
       for (int r = 0; r < n; r++) {
-        if ((rc2 = mt_deal_tiles_device(root, by_map ? root->d_multi_order : nullptr, image_w, image_h, tile_w, tile_h, n, r,
+        if ((rc2 = mt_deal_tiles_device(root, by_map ? root->d_multi_order.p : nullptr, image_w, image_h, tile_w, tile_h, n, r,
                                         root->d_multi_lists + (size_t)r * n_max, root->multi_stream)) < 0) return rc2;
       }
     }
@@ -1913,23 +1869,21 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
           }
         }
         uint8_t *dst = root->d_multi_gather + (size_t)r * (size_t)n_max * slot;
-        HIP_TRY(hipMemcpyPeerAsync(dst, root->device, s->d_multi_tiles, s->device, (size_t)n_r * slot, root->multi_stream));
+        MT_TRY(copy(dst, root->device, s->d_multi_tiles, s->device, (size_t)n_r * slot, root->multi_stream));
         src = dst;
       }
-      if ((rc2 = mt_blit_tile_list_device(root, image_w, image_h, tile_w, tile_h, root->d_multi_lists + (size_t)r * n_max, n_r,
-                                          src, root->d_multi_frame, root->multi_stream)) != MT_OK) return rc2;
+      MT_TRY(mt_blit_tile_list_device(root, image_w, image_h, tile_w, tile_h, root->d_multi_lists + (size_t)r * n_max, n_r,
+                                      src, root->d_multi_frame, root->multi_stream));
     }
     HIP_TRY(hipMemcpyAsync(out_rgb, root->d_multi_frame, (size_t)image_w * image_h * 3, hipMemcpyDeviceToHost, root->multi_stream));
     if (share_costs) {
       // all maps to the first replica's device, element-wise maximum, and back to every replica -- behind the frame's
       // copy on the same streams
-      if ((rc2 = ensure_bytes((void **)&root->d_multi_maps, &root->multi_maps_bytes, (size_t)n * map_bytes)) != MT_OK) return rc2;
+      MT_TRY(root->d_multi_maps.ensure((size_t)n * map_bytes));
       if (!root->multi_comb_done) HIP_TRY(hipEventCreateWithFlags(&root->multi_comb_done, hipEventDisableTiming));
       for (int r = 0; r < n; r++) {
-        mt_scene *s = scenes[r];
-        unsigned *dst = root->d_multi_maps + (size_t)r * map_w * map_h;
-        if (s->device != root->device || force_peer) HIP_TRY(hipMemcpyPeerAsync(dst, root->device, s->d_multi_map, s->device, map_bytes, root->multi_stream));
-        else HIP_TRY(hipMemcpyAsync(dst, s->d_multi_map, map_bytes, hipMemcpyDeviceToDevice, root->multi_stream));
+        MT_TRY(copy(root->d_multi_maps + (size_t)r * map_w * map_h, root->device, scenes[r]->d_multi_map, scenes[r]->device,
+                    map_bytes, root->multi_stream));
       }
       hipLaunchKernelGGL(max_maps_kernel, dim3(256), dim3(256), 0, root->multi_stream, root->d_multi_maps, n, (size_t)map_w * map_h);
       HIP_TRY(hipGetLastError());
@@ -1938,21 +1892,15 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
         mt_scene *s = scenes[r];
         HIP_TRY(hipSetDevice(s->device));
         HIP_TRY(hipStreamWaitEvent(s->multi_stream, root->multi_comb_done, 0));
-        if (s->device != root->device || force_peer) HIP_TRY(hipMemcpyPeerAsync(s->d_multi_map, s->device, root->d_multi_maps, root->device, map_bytes, s->multi_stream));
-        else HIP_TRY(hipMemcpyAsync(s->d_multi_map, root->d_multi_maps, map_bytes, hipMemcpyDeviceToDevice, s->multi_stream));
-        if ((rc2 = mt_scene_import_costs_device(s, s->d_multi_map, map_w, map_h, s->multi_stream)) != MT_OK) return rc2;
+        MT_TRY(copy(s->d_multi_map, s->device, root->d_multi_maps, root->device, map_bytes, s->multi_stream));
+        MT_TRY(mt_scene_import_costs_device(s, s->d_multi_map, map_w, map_h, s->multi_stream));
       }
       HIP_TRY(hipSetDevice(root->device));
     }
     HIP_TRY(hipStreamSynchronize(root->multi_stream));
     return MT_OK;
   };
-  if ((rc = phase2()) != MT_OK) {
-    const std::string text = g_err;
-    drain();
-    forget();
-    return fail(rc, "%s", text.c_str());
-  }
+  if ((rc = phase2()) != MT_OK) return failed(rc, g_err);
   const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   // every replica's launch has completed (the root's stream waited for their events); its device status and counters
   auto phase3 = [&]() -> int {
@@ -1981,12 +1929,7 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n, const mt_sensor *senso
     if (worst != MT_OK) return fail(worst, "%s", text.c_str());
     return MT_OK;
   };
-  if ((rc = phase3()) != MT_OK) {
-    const std::string text = g_err;
-    drain();
-    forget();
-    return fail(rc, "%s", text.c_str());
-  }
+  if ((rc = phase3()) != MT_OK) return failed(rc, g_err);
   for (int r = 0; r < n; r++) {
     scenes[r]->multi_geom = geom;
     scenes[r]->multi_rank = r;
@@ -2005,53 +1948,35 @@ int mt_intersect_rays(mt_scene *s, int n, const double *rays, int32_t *tri, int3
   if (stats) memset(stats, 0, sizeof *stats);
   if (n == 0) return MT_OK;
   HIP_TRY(hipSetDevice(s->device));
-  double *d_rays = nullptr, *d_t = nullptr, *d_point = nullptr;
-  int *d_tri = nullptr, *d_line = nullptr;
-  int rc = MT_OK;
-  auto cleanup = [&]() {
-    (void)hipFree(d_rays); (void)hipFree(d_t); (void)hipFree(d_point);
-    (void)hipFree(d_tri); (void)hipFree(d_line);
-  };
-#define TRY_OR_CLEAN(expr)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cleanup();                                                                             \
-      return fail(MT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                \
-    }                                                                                        \
-  } while (0)
-  TRY_OR_CLEAN(hipMalloc((void **)&d_rays, (size_t)n * 48));
-  TRY_OR_CLEAN(hipMalloc((void **)&d_t, (size_t)n * 8));
-  TRY_OR_CLEAN(hipMalloc((void **)&d_point, (size_t)n * 24));
-  TRY_OR_CLEAN(hipMalloc((void **)&d_tri, (size_t)n * 4));
-  TRY_OR_CLEAN(hipMalloc((void **)&d_line, (size_t)n * 4));
-  TRY_OR_CLEAN(hipMemcpy(d_rays, rays, (size_t)n * 48, hipMemcpyHostToDevice));
-  TRY_OR_CLEAN(hipMemset(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long)));
+  Buf<double> d_rays, d_t, d_point;
+  Buf<int> d_tri, d_line;
+  MT_TRY(d_rays.ensure((size_t)n * 48));
+  MT_TRY(d_t.ensure((size_t)n * 8));
+  MT_TRY(d_point.ensure((size_t)n * 24));
+  MT_TRY(d_tri.ensure((size_t)n * 4));
+  MT_TRY(d_line.ensure((size_t)n * 4));
+  HIP_TRY(hipMemcpy(d_rays, rays, (size_t)n * 48, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long)));
   const int block = s->waves_per_block * 64;
   // (DEEP layout: every wave of a launch has an area of global memory -- batches of at most 128 K rays per launch)
   const int per_launch = s->deep ? (n < (1 << 17) ? n : (1 << 17)) : n;
-  if ((rc = ensure_deep(s, (size_t)((per_launch + block - 1) / block) * s->waves_per_block)) != MT_OK) {
-    cleanup();
-    return rc;
-  }
-  TRY_OR_CLEAN(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, nullptr));
-  TRY_OR_CLEAN(hipEventRecord(s->ev0, nullptr));
+  MT_TRY(ensure_deep(s, (size_t)((per_launch + block - 1) / block) * s->waves_per_block));
+  HIP_TRY(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, nullptr));
+  HIP_TRY(hipEventRecord(s->ev0, nullptr));
   for (int at = 0; at < n; at += per_launch) {
     const int m = n - at < per_launch ? n - at : per_launch;
-    MT_LAUNCH_D(intersect_kernel, dim3((m + block - 1) / block), dim3(block), s->lds_bytes, nullptr, s->dev, m,
-                d_rays + (size_t)at * 6, d_tri + at, d_line + at, d_t + at, d_point + (size_t)at * 3, s->d_counters);
+    hipLaunchKernelGGL(kernels_of(s->deep).intersect, dim3((m + block - 1) / block), dim3(block), s->lds_bytes, nullptr, s->dev,
+                       m, d_rays + (size_t)at * 6, d_tri + at, d_line + at, d_t + at, d_point + (size_t)at * 3, s->d_counters.p);
   }
-  TRY_OR_CLEAN(hipGetLastError());
-  TRY_OR_CLEAN(hipEventRecord(s->ev1, nullptr));
-  TRY_OR_CLEAN(hipDeviceSynchronize());
-  if (tri) TRY_OR_CLEAN(hipMemcpy(tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (line_no) TRY_OR_CLEAN(hipMemcpy(line_no, d_line, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (t) TRY_OR_CLEAN(hipMemcpy(t, d_t, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (point) TRY_OR_CLEAN(hipMemcpy(point, d_point, (size_t)n * 24, hipMemcpyDeviceToHost));
-  cleanup();
-#undef TRY_OR_CLEAN
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(s->ev1, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  if (tri) HIP_TRY(hipMemcpy(tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (line_no) HIP_TRY(hipMemcpy(line_no, d_line, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (t) HIP_TRY(hipMemcpy(t, d_t, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (point) HIP_TRY(hipMemcpy(point, d_point, (size_t)n * 24, hipMemcpyDeviceToHost));
   mt_stats local;
-  if ((rc = mt_scene_read_stats(s, &local)) != MT_OK) return rc;
+  MT_TRY(mt_scene_read_stats(s, &local));
   if (stats) {
     *stats = local;
     float ms = 0;
