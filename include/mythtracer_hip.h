@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MT_ABI_VERSION 4
+#define MT_ABI_VERSION 5
 
 enum {
   MT_OK = 0,
@@ -228,6 +228,41 @@ int mt_render_tile_list_device(mt_scene *scene, const mt_sensor *sensor, int ima
 int mt_blit_tile_list_device(mt_scene *scene, int image_w, int image_h, int tile_w, int tile_h,
                              const void *d_list, int n_tiles, const void *d_tiles, void *d_image,
                              void *stream);
+
+/* Supersampled frames: ss x ss samples per pixel, ss in 1 .. 4, resolved on the GPU.  (No reference counterpart: the
+ * reference's pixel loop traces one ray per pixel, mythtracer.cc:292-305.)  The SAMPLE FRAME of an image_w x image_h
+ * image is the frame of the plain calls at ss image_w x ss image_h for the same camera: Camera::GetSensor
+ * (camera.cc:27-69) for that size puts its rays on an ss x ss grid inside every pixel of the image_w x image_h image.
+ * Output pixel (x, y), channel c = (sum + n / 2) / n in unsigned integer arithmetic, n = ss ss, sum = the n sample
+ * bytes at (ss x + i, ss y + j), 0 <= i, j < ss: the mean of the reference's bytes, rounded to nearest, ties up.
+ * In these calls image_*, chunk_* and tile_* are the OUTPUT geometry, and `sensor` is the sensor OF THE SAMPLE GRID
+ * (ss image_w x ss image_h).  Both sizes of the sample grid must stay within the 100000 the plain calls allow.
+ *   mt_render_chunk_ss: as mt_render_chunk (no debug buffer).  The chunk (ss chunk_x, ss chunk_y, ss chunk_w,
+ *     ss chunk_h) of the sample frame is rendered into a buffer the scene owns (ss ss chunk_w chunk_h 3 bytes, grown on
+ *     demand; MT_ERR_NOMEM when it does not fit: never a lower ss instead) by ONE ordinary launch -- cost history,
+ *     engine choice and forecasts work as for any repeated launch of that geometry -- and resolved; chunk_w chunk_h 3
+ *     bytes come back.  stats counts the sample frame's work (rays_primary = ss ss chunk_w chunk_h); kernel_ms
+ *     includes the resolve.
+ *   mt_render_chunk_ss_device: the same, asynchronous, output left in HBM at d_rgb; stream ordering as for
+ *     mt_render_chunk_device.
+ *   mt_resolve_tiles_device: the building block of a multi-GPU supersampled frame.  A rank renders its tiles of the
+ *     sample frame with mt_render_tiles_device or mt_render_tile_list_device at (ss image_w, ss image_h, ss tile_w,
+ *     ss tile_h) -- the tile numbers are the same, the grid is the same -- into d_samples; this call resolves slot j
+ *     of d_samples (ss ss tile_w tile_h 3 bytes each) into slot j of d_tiles (tile_w tile_h 3 bytes each: what the plain
+ *     tile calls write at the output geometry), and the unchanged gather and blit at (image_w, image_h, tile_w, tile_h)
+ *     finish the frame: the gather carries 1 / (ss ss) of the bytes.  d_list (nullable): the tile of slot j, as
+ *     for mt_blit_tile_list_device; NULL: first_tile + j tile_stride.
+ * ss = 1 is the plain call, through the plain call's path.  Argument checks come before any device call, ss and the
+ * sample grid's size before everything else. */
+int mt_render_chunk_ss(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h, int chunk_x,
+                       int chunk_y, int chunk_w, int chunk_h, int ss, int max_depth, uint8_t *out_rgb,
+                       mt_stats *stats);
+int mt_render_chunk_ss_device(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                              int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int max_depth,
+                              void *d_rgb, void *stream);
+int mt_resolve_tiles_device(mt_scene *scene, int image_w, int image_h, int tile_w, int tile_h,
+                            int first_tile, int tile_stride, const void *d_list, int n_tiles, int ss,
+                            const void *d_samples, void *d_tiles, void *stream);
 
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into

@@ -11,7 +11,7 @@ HIP_LIB = os.path.join(PKG, "lib", "libmythtracer_hip.so")
 HOST_LIB = os.path.join(PKG, "lib", "libmythtracer_host.so")
 
 MT_OK = 0
-MT_ABI_VERSION = 4
+MT_ABI_VERSION = 5
 MT_TEX_RGB8, MT_TEX_F64 = 0, 1
 
 # every symbol include/mythtracer_hip.h declares
@@ -25,6 +25,7 @@ HIP_SYMBOLS = [
     "mt_render_frame_multi", "mt_scene_export_costs_device", "mt_scene_import_costs_device",
     "mt_order_tiles_device", "mt_dealt_tile_count", "mt_deal_tiles_device",
     "mt_render_tile_list_device", "mt_blit_tile_list_device",
+    "mt_render_chunk_ss", "mt_render_chunk_ss_device", "mt_resolve_tiles_device",
 ]
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
@@ -149,6 +150,9 @@ class HipAbi:
         L.mt_deal_tiles_device.argtypes = [vp, vp] + [ci] * 6 + [vp, vp]
         L.mt_render_tile_list_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 4 + [vp, ci, C.c_uint64, ci, vp, vp]
         L.mt_blit_tile_list_device.argtypes = [vp] + [ci] * 4 + [vp, ci, vp, vp, vp]
+        L.mt_render_chunk_ss.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
+        L.mt_render_chunk_ss_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
+        L.mt_resolve_tiles_device.argtypes = [vp] + [ci] * 6 + [vp, ci, ci, vp, vp, vp]
 
     def last_error(self) -> str:
         return self.lib.mt_last_error().decode(errors="replace")
@@ -298,6 +302,27 @@ class HipAbi:
         self.check(self.lib.mt_blit_tile_list_device(h, image_w, image_h, tile_w, tile_h, d_list, n_tiles,
                                                      d_tiles, d_image, stream))
 
+    # ---- supersampled frames (include/mythtracer_hip.h, mt_render_chunk_ss ff.): sensor12 is the sensor of the SAMPLE
+    # grid, ss image_w x ss image_h; image_*, chunk and tile_* are the output geometry
+    def render_chunk_ss(self, h, sensor12, image_w, image_h, ss, chunk=None, max_depth=5):
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        rgb = np.zeros((max(ch, 0), max(cw, 0), 3), dtype=np.uint8)
+        st = mt_stats()
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_chunk_ss(h, C.byref(s), image_w, image_h, cx, cy, cw, ch, ss, max_depth,
+                                               _ptr(rgb), C.addressof(st)))
+        return dict(rgb=rgb, stats=st.as_dict())
+
+    def render_chunk_ss_device(self, h, sensor12, image_w, image_h, chunk, ss, max_depth, d_rgb, stream=None):
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_chunk_ss_device(h, C.byref(s), image_w, image_h, *chunk, ss, max_depth,
+                                                      d_rgb, stream))
+
+    def resolve_tiles_device(self, h, image_w, image_h, tile_w, tile_h, first_tile, tile_stride, d_list, n_tiles,
+                             ss, d_samples, d_tiles, stream=None):
+        self.check(self.lib.mt_resolve_tiles_device(h, image_w, image_h, tile_w, tile_h, first_tile, tile_stride,
+                                                    d_list, n_tiles, ss, d_samples, d_tiles, stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -398,6 +423,8 @@ def host_lib():
     L.mth_set_lights.restype = None
     L.mth_set_max_level.argtypes = [vp, ci]
     L.mth_set_max_level.restype = None
+    L.mth_set_supersampling.argtypes = [vp, ci]
+    L.mth_set_supersampling.restype = None
     L.mth_finalize.argtypes = [vp]
     L.mth_finalize.restype = None
     L.mth_prepare.argtypes = [vp]
@@ -502,6 +529,10 @@ class MythTracer:
 
     def set_max_level(self, level):
         self.L.mth_set_max_level(self.h, level)
+
+    def set_supersampling(self, s):
+        """MythTracer::SetSupersampling: s x s samples per pixel in render / render_image (1 .. 4, default 1)."""
+        self.L.mth_set_supersampling(self.h, int(s))
 
     def finalize(self):
         self.L.mth_finalize(self.h)

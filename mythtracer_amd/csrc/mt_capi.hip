@@ -25,6 +25,7 @@
 // Single translation unit: the kernels are compiled together with their host
 // side so that no relocatable device code is needed.
 #include "mt_render.hip"
+#include "mt_resolve.h"
 
 using namespace mt;
 
@@ -169,6 +170,7 @@ struct mt_scene {
   unsigned long long cost_signature = 0;  // 0 = no history
   bool use_history = true;
   Buf<uint8_t> d_rgb;
+  Buf<uint8_t> d_samples;  // supersampled chunks: the sample frame on its way to resolve_kernel (mt_resolve.h)
   Buf<mt_debug_px> d_debug;
   std::vector<mt_light> lights_host;  // what d_lights holds
   int forecasts_in_a_row = 0;  // launches with this geometry and camera whose work order came from a forecast
@@ -837,6 +839,126 @@ int check_tile_selection(int image_w, int image_h, int tile_w, int tile_h, int f
   const long long tiles_total = tile_count(image_w, image_h, tile_w, tile_h);
   if (n_tiles > 0 && (long long)first_tile + (long long)(n_tiles - 1) * tile_stride >= tiles_total) {
     return fail(MT_ERR_ARG, "tile selection exceeds the %lld tiles of the image", tiles_total);
+  }
+  return MT_OK;
+}
+
+// WorkChunk::DeserializeInput's constraints, mythtracer.cc:358-371
+int check_chunk(int image_w, int image_h, int chunk_x, int chunk_y, int chunk_w, int chunk_h) {
+  if (chunk_x < 0 || chunk_y < 0 || chunk_w <= 0 || chunk_h <= 0 ||
+      (long long)chunk_x + chunk_w > image_w || (long long)chunk_y + chunk_h > image_h) {
+    return fail(MT_ERR_ARG, "chunk %d,%d %dx%d outside image %dx%d", chunk_x, chunk_y, chunk_w,
+                chunk_h, image_w, image_h);
+  }
+  return MT_OK;
+}
+
+// ---- supersampled frames (mt_resolve.h) ----
+// The factor and the sample grid it makes of the OUTPUT image: checked before anything else, the scene included.
+int check_ss(int ss, int image_w, int image_h) {
+  if (ss < 1 || ss > 4) return fail(MT_ERR_ARG, "ss %d outside [1, 4]", ss);
+  if (image_w <= 0 || image_h <= 0 || (long long)ss * image_w > 100000 || (long long)ss * image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d with ss %d: sample grid %lldx%lld out of range", image_w, image_h, ss,
+                (long long)ss * image_w, (long long)ss * image_h);
+  }
+  return MT_OK;
+}
+
+// The scene's sample buffer, grown on demand.  A frame that does not fit fails: never a lower factor instead.
+int ensure_samples(mt_scene *s, size_t bytes) {
+  if (s->d_samples.ensure(bytes) == MT_OK) return MT_OK;
+  (void)hipGetLastError();
+  const std::string why = g_err;
+  return fail(MT_ERR_NOMEM, "no room for the %zu-byte sample buffer: %s", bytes, why.c_str());
+}
+
+// resolve_kernel over n_tiles slots of the OUTPUT image's tile grid (a chunk: its one tile)
+int launch_resolve(int ss, int image_w, int image_h, int tile_w, int tile_h, int first_tile, int tile_stride,
+                   const int32_t *d_list, int n_tiles, const uint8_t *d_samples, uint8_t *d_out, hipStream_t stream) {
+  ResolveArgs A{};
+  A.image_w = image_w; A.image_h = image_h;
+  A.tile_w = tile_w; A.tile_h = tile_h;
+  A.tiles_x = (image_w + tile_w - 1) / tile_w;
+  A.first_tile = first_tile; A.tile_stride = tile_stride; A.n_tiles = n_tiles;
+  A.tile_list = d_list;
+  A.rows = std::min(tile_h, image_h);
+  A.units = std::min(tile_w, image_w) / 4 + 2;
+  A.samples = d_samples;
+  A.out = d_out;
+  const unsigned long long total = (unsigned long long)n_tiles * A.rows * A.units;
+  if (total > 0x7fffffffull) return fail(MT_ERR_ARG, "too many pixels to resolve in one launch (%llu units)", total);
+  if (total == 0) return MT_OK;
+  const dim3 grid((unsigned)std::min<unsigned long long>((total + 255) / 256, 4096)), block(256);
+  switch (ss) {
+    case 2: hipLaunchKernelGGL(resolve_kernel<2>, grid, block, 0, stream, A, (unsigned)total); break;
+    case 3: hipLaunchKernelGGL(resolve_kernel<3>, grid, block, 0, stream, A, (unsigned)total); break;
+    case 4: hipLaunchKernelGGL(resolve_kernel<4>, grid, block, 0, stream, A, (unsigned)total); break;
+    default: return fail(MT_ERR_ARG, "ss %d has no resolve kernel", ss);
+  }
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+// The two halves of a chunk call with host output around its launches.  begin: the scene's buffers for npx pixels,
+// cleared counters, the first event.
+int begin_host_chunk(mt_scene *s, size_t npx, bool debug, hipStream_t stream) {
+  MT_TRY(s->d_rgb.ensure(npx * 3));
+  if (debug) MT_TRY(s->d_debug.ensure(npx * sizeof(mt_debug_px)));
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  MT_TRY(s->h_stage.ensure(npx * 3));
+  for (hipEvent_t &e : s->ev_stage) {
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  return MT_OK;
+}
+
+// finish: the chunk in s->d_rgb (and s->d_debug) reaches the caller, with the counters and times of the launches.
+// How the frame reaches the caller's (pageable) buffer, measured on the box (scripts/ubench/d2h_paths.hip, 6.2 MB of
+// a 1080p frame / 24.9 MB of a 4K one): plain hipMemcpy 1.17 / 1.22 ms; a page-locked staging buffer + memcpy 0.42 /
+// 1.72 (the memcpy alone 0.30 / 1.28); registering the caller's buffer per call 0.82 / 1.22 (the registration 0.7);
+// a copy into memory that IS registered 0.12 / 0.45 -- but keeping a caller's buffer registered across calls is not
+// safe (a vector freed and allocated again at the same address would receive its frame in the OLD pages).  So: the
+// staging buffer, in pieces, every piece's memcpy under the next piece's DMA: about the memcpy's time.
+int finish_host_chunk(mt_scene *s, size_t npx, uint8_t *out_rgb, mt_debug_px *out_debug, mt_stats *stats,
+                      std::chrono::steady_clock::time_point w0, hipStream_t stream) {
+  const size_t out_bytes = npx * 3;
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  // everything that comes back is queued behind the kernels: the counters (device status), the frame in pieces
+  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  const int n_pieces = out_bytes < (1u << 20) ? 1 : (out_bytes < (8u << 20) ? 4 : mt_scene::kStagePieces);
+  const size_t piece = ((out_bytes + n_pieces - 1) / n_pieces + 4095) & ~(size_t)4095;
+  for (int k = 0; k < n_pieces; k++) {
+    const size_t off = (size_t)k * piece;
+    if (off < out_bytes) {
+      HIP_TRY(hipMemcpyAsync(s->h_stage + off, s->d_rgb + off, std::min(piece, out_bytes - off), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipEventRecord(s->ev_stage[k], stream));
+  }
+  if (out_debug) {
+    HIP_TRY(hipMemcpyAsync(out_debug, s->d_debug, npx * sizeof(mt_debug_px), hipMemcpyDeviceToHost, stream));
+  }
+  for (int k = 0; k < n_pieces; k++) {
+    const size_t off = (size_t)k * piece;
+    HIP_TRY(hipEventSynchronize(s->ev_stage[k]));
+    if (k == 0 && check_status(s->h_counters) != MT_OK) {  // (the counters came first: no frame of a failed launch)
+      (void)hipStreamSynchronize(stream);
+      return check_status(s->h_counters);
+    }
+    if (off < out_bytes) memcpy(out_rgb + off, s->h_stage + off, std::min(piece, out_bytes - off));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  MT_TRY(check_status(s->h_counters));
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    fill_stats(s->h_counters, stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   }
   return MT_OK;
 }
@@ -1518,12 +1640,7 @@ int mt_render_chunk_device(mt_scene *s, const mt_sensor *sensor, int image_w, in
                            int chunk_x, int chunk_y, int chunk_w, int chunk_h, int max_depth,
                            void *d_rgb, void *d_debug, void *stream) {
   MT_TRY(check_image_args(s, sensor, image_w, image_h));
-  // WorkChunk::DeserializeInput's constraints, mythtracer.cc:358-371
-  if (chunk_x < 0 || chunk_y < 0 || chunk_w <= 0 || chunk_h <= 0 ||
-      (long long)chunk_x + chunk_w > image_w || (long long)chunk_y + chunk_h > image_h) {
-    return fail(MT_ERR_ARG, "chunk %d,%d %dx%d outside image %dx%d", chunk_x, chunk_y, chunk_w,
-                chunk_h, image_w, image_h);
-  }
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
   if (!d_rgb) return fail(MT_ERR_ARG, "d_rgb is NULL");
   HIP_TRY(hipSetDevice(s->device));
   return launch_render(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, chunk_w,
@@ -1638,65 +1755,15 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
   const auto w0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)(chunk_w > 0 ? chunk_w : 0) * (size_t)(chunk_h > 0 ? chunk_h : 0);
-  MT_TRY(s->d_rgb.ensure(npx * 3));
-  if (out_debug) MT_TRY(s->d_debug.ensure(npx * sizeof(mt_debug_px)));
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
-  // How the frame reaches the caller's (pageable) buffer, measured on the box (scripts/ubench/d2h_paths.hip, 6.2 MB of
-  // a 1080p frame / 24.9 MB of a 4K one): plain hipMemcpy 1.17 / 1.22 ms; a page-locked staging buffer + memcpy 0.42 /
-  // 1.72 (the memcpy alone 0.30 / 1.28); registering the caller's buffer per call 0.82 / 1.22 (the registration 0.7);
-  // a copy into memory that IS registered 0.12 / 0.45 -- but keeping a caller's buffer registered across calls is not
-  // safe (a vector freed and allocated again at the same address would receive its frame in the OLD pages).  So: the
-  // staging buffer, in pieces, every piece's memcpy under the next piece's DMA: about the memcpy's time.
-  const size_t out_bytes = npx * 3;
-  MT_TRY(s->h_stage.ensure(out_bytes));
-  for (hipEvent_t &e : s->ev_stage) {
-    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
   hipStream_t stream = nullptr;
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(s->ev0, stream));
+  MT_TRY(begin_host_chunk(s, npx, out_debug != nullptr, stream));
   const bool counters_were = s->stats_enabled;
   if (stats) s->stats_enabled = true;  // the caller asked for them
   rc = mt_render_chunk_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h,
                               max_depth, s->d_rgb, out_debug ? s->d_debug.p : nullptr, stream);
   s->stats_enabled = counters_were;
   if (rc != MT_OK) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, stream));
-  // everything that comes back is queued behind the kernels: the counters (device status), the frame in pieces
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  const int n_pieces = out_bytes < (1u << 20) ? 1 : (out_bytes < (8u << 20) ? 4 : mt_scene::kStagePieces);
-  const size_t piece = ((out_bytes + n_pieces - 1) / n_pieces + 4095) & ~(size_t)4095;
-  for (int k = 0; k < n_pieces; k++) {
-    const size_t off = (size_t)k * piece;
-    if (off < out_bytes) {
-      HIP_TRY(hipMemcpyAsync(s->h_stage + off, s->d_rgb + off, std::min(piece, out_bytes - off), hipMemcpyDeviceToHost, stream));
-    }
-    HIP_TRY(hipEventRecord(s->ev_stage[k], stream));
-  }
-  if (out_debug) {
-    HIP_TRY(hipMemcpyAsync(out_debug, s->d_debug, npx * sizeof(mt_debug_px), hipMemcpyDeviceToHost, stream));
-  }
-  for (int k = 0; k < n_pieces; k++) {
-    const size_t off = (size_t)k * piece;
-    HIP_TRY(hipEventSynchronize(s->ev_stage[k]));
-    if (k == 0 && check_status(s->h_counters) != MT_OK) {  // (the counters came first: no frame of a failed launch)
-      (void)hipStreamSynchronize(stream);
-      return check_status(s->h_counters);
-    }
-    if (off < out_bytes) memcpy(out_rgb + off, s->h_stage + off, std::min(piece, out_bytes - off));
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  if ((rc = check_status(s->h_counters)) != MT_OK) return rc;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    fill_stats(s->h_counters, stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
+  MT_TRY(finish_host_chunk(s, npx, out_rgb, out_debug, stats, w0, stream));
 #ifdef MT_PROF
   {  // (the phase profile is printed by mt_scene_read_stats)
     mt_stats dummy;
@@ -1704,6 +1771,80 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
   }
 #endif
   return MT_OK;
+}
+
+// ---- supersampled frames: the sample frame is an ordinary launch at ss image_w x ss image_h, resolve_kernel
+// (mt_resolve.h) makes the pixels.  `sensor` is the sensor of the SAMPLE grid. ----
+int mt_render_chunk_ss_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                              int chunk_w, int chunk_h, int ss, int max_depth, void *d_rgb, void *stream) {
+  MT_TRY(check_ss(ss, image_w, image_h));
+  if (ss == 1) {
+    return mt_render_chunk_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, max_depth, d_rgb,
+                                  nullptr, stream);
+  }
+  MT_TRY(check_image_args(s, sensor, ss * image_w, ss * image_h));
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  if (!d_rgb) return fail(MT_ERR_ARG, "d_rgb is NULL");
+  HIP_TRY(hipSetDevice(s->device));
+  MT_TRY(ensure_samples(s, (size_t)chunk_w * chunk_h * 3 * ss * ss));
+  MT_TRY(mt_render_chunk_device(s, sensor, ss * image_w, ss * image_h, ss * chunk_x, ss * chunk_y, ss * chunk_w,
+                                ss * chunk_h, max_depth, s->d_samples, nullptr, stream));
+  return launch_resolve(ss, chunk_w, chunk_h, chunk_w, chunk_h, 0, 1, nullptr, 1, s->d_samples, (uint8_t *)d_rgb,
+                        (hipStream_t)stream);
+}
+
+int mt_render_chunk_ss(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                       int chunk_w, int chunk_h, int ss, int max_depth, uint8_t *out_rgb, mt_stats *stats) {
+  MT_TRY(check_ss(ss, image_w, image_h));
+  if (ss == 1) {
+    return mt_render_chunk(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, max_depth, out_rgb, nullptr,
+                           stats);
+  }
+  MT_TRY(check_image_args(s, sensor, ss * image_w, ss * image_h));
+  if (!out_rgb) return fail(MT_ERR_ARG, "out_rgb is NULL");
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * chunk_h;
+  hipStream_t stream = nullptr;
+  MT_TRY(begin_host_chunk(s, npx, false, stream));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = mt_render_chunk_ss_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss,
+                                           max_depth, s->d_rgb, stream);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  return finish_host_chunk(s, npx, out_rgb, nullptr, stats, w0, stream);
+}
+
+int mt_resolve_tiles_device(mt_scene *s, int image_w, int image_h, int tile_w, int tile_h, int first_tile,
+                            int tile_stride, const void *d_list, int n_tiles, int ss, const void *d_samples,
+                            void *d_tiles, void *stream) {
+  MT_TRY(check_ss(ss, image_w, image_h));
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (tile_w <= 0 || tile_h <= 0 || first_tile < 0 || tile_stride <= 0 || n_tiles < 0) {
+    return fail(MT_ERR_ARG, "bad tiling arguments");
+  }
+  if ((long long)ss * tile_w > 100000 || (long long)ss * tile_h > 100000) {
+    return fail(MT_ERR_ARG, "tile size %dx%d with ss %d out of range", tile_w, tile_h, ss);
+  }
+  if (d_list == nullptr) {
+    MT_TRY(check_tile_selection(image_w, image_h, tile_w, tile_h, first_tile, tile_stride, n_tiles));
+  } else if (n_tiles > tile_count(image_w, image_h, tile_w, tile_h)) {
+    return fail(MT_ERR_ARG, "%d tiles listed, the image has %lld", n_tiles, tile_count(image_w, image_h, tile_w, tile_h));
+  }
+  if (n_tiles == 0) return MT_OK;
+  if (!d_samples || !d_tiles) return fail(MT_ERR_ARG, "d_samples or d_tiles is NULL");
+  if (d_samples == d_tiles) return ss == 1 ? MT_OK : fail(MT_ERR_ARG, "d_samples and d_tiles are the same buffer");
+  HIP_TRY(hipSetDevice(s->device));
+  if (ss == 1) {  // the samples are the pixels
+    HIP_TRY(hipMemcpyAsync(d_tiles, d_samples, (size_t)n_tiles * tile_w * tile_h * 3, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+    return MT_OK;
+  }
+  return launch_resolve(ss, image_w, image_h, tile_w, tile_h, d_list ? 0 : first_tile, d_list ? 1 : tile_stride,
+                        (const int32_t *)d_list, n_tiles, (const uint8_t *)d_samples, (uint8_t *)d_tiles,
+                        (hipStream_t)stream);
 }
 
 // ---- one frame on several GPUs of this process (main_net_master.cc:195-236) --------------------------

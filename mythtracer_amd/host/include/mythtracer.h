@@ -76,6 +76,12 @@ class MythTracer {
   // in one process.  RayTrace(WorkChunk*) -- the unit a worker renders -- stays on the first device.
   void SetDevices(const std::vector<int>& hip_devices);
   void SetMaxRecursionLevel(int level) { max_level_ = level; }  // default MAX_RECURSION_LEVEL
+  // Supersampling: s x s samples per pixel (default 1 = the reference's one ray per pixel), resolved on the GPU:
+  // both RayTrace overloads return the reference's frame at s W x s H, box-filtered s x s (mt_render_chunk_ss).
+  // A factor outside 1 .. 4 makes the next RayTrace fail; so do s > 1 with a non-empty WorkChunk::output_debug (a
+  // debug record belongs to a ray, not to a mean) and, for the W x H overload, s > 1 with more than one device
+  // (SetDevices): a supersampled frame is rendered on one device, never silently so when several were asked for.
+  void SetSupersampling(int s) { supersampling_ = s; }
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);
@@ -99,6 +105,8 @@ class MythTracer {
   int device_ = 0;
   void DropDeviceScenes();
   int max_level_ = MAX_RECURSION_LEVEL;
+  int supersampling_ = 1;
+  bool CheckSupersampling(int image_width, int image_height, bool on_all_devices);
   bool quiet_ = false;
   bool collect_stats_ = true;
   RenderStats stats_;

@@ -205,8 +205,25 @@ bool MythTracer::Prepare() {
   return true;
 }
 
+// The supersampling factor is checked before anything touches a device: a caller without one sees this message too.
+bool MythTracer::CheckSupersampling(int image_width, int image_height, bool on_all_devices) {
+  const int s = supersampling_;
+  if (s < 1 || s > 4) {
+    error_ = "supersampling factor " + std::to_string(s) + " outside 1 .. 4";
+  } else if (s > 1 && on_all_devices && devices_.size() > 1) {
+    error_ = "supersampling is not supported with several devices (SetDevices)";
+  } else if (s > 1 && (image_width <= 0 || image_height <= 0 || image_width > 100000 / s || image_height > 100000 / s)) {
+    error_ = "image size " + std::to_string(image_width) + "x" + std::to_string(image_height) + " out of range for supersampling factor " + std::to_string(s);
+  } else {
+    return true;
+  }
+  fprintf(stderr, "error: %s\n", error_.c_str());
+  return false;
+}
+
 bool MythTracer::RayTrace(int image_width, int image_height, Camera* camera,
                           std::vector<uint8_t>* output_bitmap) {
+  if (!CheckSupersampling(image_width, image_height, true)) return false;
   if (devices_.size() > 1) {
     // the whole frame on all listed GPUs (mt_render_frame_multi); 64x64 tiles, finer than the master's 128x128
     // chunks (main_net_master.cc:24-25): a pixel's cost varies 60-fold across the frame
@@ -263,6 +280,13 @@ bool MythTracer::RayTrace(int image_width, int image_height, Camera* camera,
 }
 
 bool MythTracer::RayTrace(WorkChunk* chunk) {
+  if (!CheckSupersampling(chunk->image_width, chunk->image_height, false)) return false;
+  const int ss = supersampling_;
+  if (ss > 1 && !chunk->output_debug.empty()) {
+    error_ = "WorkChunk::output_debug is not available with supersampling";
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  }
   if (!Prepare()) return false;
   if (!quiet_) puts("Rendering.");
   const auto t0 = std::chrono::steady_clock::now();
@@ -275,7 +299,8 @@ bool MythTracer::RayTrace(WorkChunk* chunk) {
     error_ = mt_last_error();
     return false;
   }
-  const Camera::Sensor sensor = chunk->camera.GetSensor(chunk->image_width, chunk->image_height);
+  // (the sensor of the sample grid: ss x ss rays inside every pixel; ss = 1: the reference's)
+  const Camera::Sensor sensor = chunk->camera.GetSensor(ss * chunk->image_width, ss * chunk->image_height);
   mt_sensor ms;
   memcpy(ms.origin, chunk->camera.origin.v, 24);
   memcpy(ms.start_point, sensor.StartPoint().v, 24);
@@ -300,10 +325,14 @@ bool MythTracer::RayTrace(WorkChunk* chunk) {
   mt_stats st;
   memset(&st, 0, sizeof st);
   (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
-  if (mt_render_chunk(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,
-                      chunk->chunk_y, chunk->chunk_width, chunk->chunk_height, max_level_,
-                      chunk->output_bitmap.data(), want_debug ? dbg.data() : nullptr,
-                      collect_stats_ ? &st : nullptr) != MT_OK) {
+  const int rc = ss > 1 ? mt_render_chunk_ss(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,
+                                             chunk->chunk_y, chunk->chunk_width, chunk->chunk_height, ss, max_level_,
+                                             chunk->output_bitmap.data(), collect_stats_ ? &st : nullptr)
+                        : mt_render_chunk(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,
+                                          chunk->chunk_y, chunk->chunk_width, chunk->chunk_height, max_level_,
+                                          chunk->output_bitmap.data(), want_debug ? dbg.data() : nullptr,
+                                          collect_stats_ ? &st : nullptr);
+  if (rc != MT_OK) {
     error_ = mt_last_error();
     fprintf(stderr, "error: render failed: %s\n", error_.c_str());
     return false;

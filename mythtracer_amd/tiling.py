@@ -98,3 +98,21 @@ def blit_tiles(image: np.ndarray, tiles: np.ndarray, tile_w: int, tile_h: int,
         x0, y0, cw, ch = tile_rect(first_tile + j * tile_stride, image_w, image_h, tile_w, tile_h)
         chunk = flat[j * sb: j * sb + cw * ch * 3].reshape(ch, cw, 3)
         image[y0:y0 + ch, x0:x0 + cw] = chunk
+
+
+def resolve_ss(samples: np.ndarray, s: int) -> np.ndarray:
+    """A supersampled frame from its sample frame (numpy restatement of resolve_kernel, csrc/mt_resolve.h):
+    samples = uint8 [s H][s W][C]; output byte (y, x, c) = (sum + n // 2) // n with n = s * s and sum = the n sample
+    bytes (s y + j, s x + i, c), 0 <= i, j < s -- the rounded mean, ties up, in integer arithmetic."""
+    a = np.asarray(samples)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError("samples must be a uint8 array [height][width][channels]")
+    if not 1 <= int(s) <= 4:
+        raise ValueError("supersampling factor %r outside 1 .. 4" % (s,))
+    s = int(s)
+    sh, sw, c = a.shape
+    if sh % s or sw % s:
+        raise ValueError("sample frame %dx%d is not a multiple of %d" % (sw, sh, s))
+    n = s * s
+    total = a.reshape(sh // s, s, sw // s, s, c).astype(np.uint32).sum(axis=(1, 3))
+    return ((total + n // 2) // n).astype(np.uint8)
