@@ -264,6 +264,42 @@ int mt_resolve_tiles_device(mt_scene *scene, int image_w, int image_h, int tile_
                             int first_tile, int tile_stride, const void *d_list, int n_tiles, int ss,
                             const void *d_samples, void *d_tiles, void *stream);
 
+/* The primary-hit G-buffer of a chunk: what the first call of TraceRayWorker (mythtracer.cc:18-64) knows about a pixel
+ * before it looks at a light, as separate planes.  (No reference counterpart: the reference returns a colour and
+ * PerPixelDebugInfo only.)  Per pixel, with the frame kernels' arithmetic: Sensor::GetRay (camera.cc:65-69),
+ * OctTree::IntersectRay from the camera origin, and on a hit
+ *   depth     the hit distance t along the normalised ray
+ *   point     origin + direction t (primitive_triangle.cc:141; mt_debug_px::point)
+ *   normal    Triangle::GetNormal(point) (primitive_triangle.cc) -- as returned, NOT flipped towards the camera
+ *             (mythtracer.cc:42-45 flips its own copy afterwards)
+ *   uvw       Triangle::GetUVW(point) (primitive_triangle.cc)
+ *   albedo    material.ambient, times Texture::GetColorAt(uvw.x, uvw.y) where the material has a texture
+ *             (mythtracer.cc:58-64): the unlit surface colour
+ *   prim      the AddPrimitive index (mt_scene_desc::tri_id; scenes created without tri_id cannot give this plane)
+ *   line_no   Primitive::debug_line_no (mt_debug_px::line_no)
+ *   material  index into mt_scene_desc::materials, -1 = no material (albedo is then NaN)
+ * depth is 1 double per pixel, point / normal / uvw / albedo 3 interleaved doubles, the others 1 int32; every plane is
+ * chunk-local row-major.  A miss: NaN in the double planes, -1 in the int32 planes.  Every pointer is nullable -- a
+ * plane nobody asked for is neither computed nor written -- but at least one must be set.
+ *   mt_render_gbuffer: `out` holds HOST pointers; stats (nullable): rays_primary = chunk pixels, shaded_hits = hits,
+ *     the traversal's counters, kernel_ms = the kernel by HIP events, total_ms = wall time of the call.
+ *   mt_render_gbuffer_device: `d_out` (a host struct) holds DEVICE pointers on the scene's GPU; asynchronous on
+ *     `stream`; counters as for mt_render_chunk_device.
+ * One kernel next to the frame kernels (mt::gbuffer_kernel).  The calls leave everything a frame launch decides by --
+ * cost history, engine choice, forecasts, mt_scene_kernel_times -- alone: a frame after a G-buffer call is the
+ * repeated launch it would have been without it.  Argument checks come before any device call, in this order: `out`,
+ * image size and chunk (mt_render_chunk's limits and messages), scene, sensor. */
+typedef struct mt_gbuffer {
+  double *depth, *point, *normal, *uvw, *albedo;
+  int32_t *prim, *line_no, *material;
+} mt_gbuffer;
+int mt_render_gbuffer(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                      int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                      const mt_gbuffer *out, mt_stats *stats);
+int mt_render_gbuffer_device(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                             int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                             const mt_gbuffer *d_out, void *stream);
+
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into
  * WorkChunks, every worker renders chunks with the full-image sensor from its

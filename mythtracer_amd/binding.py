@@ -26,6 +26,7 @@ HIP_SYMBOLS = [
     "mt_order_tiles_device", "mt_dealt_tile_count", "mt_deal_tiles_device",
     "mt_render_tile_list_device", "mt_blit_tile_list_device",
     "mt_render_chunk_ss", "mt_render_chunk_ss_device", "mt_resolve_tiles_device",
+    "mt_render_gbuffer", "mt_render_gbuffer_device",
 ]
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
@@ -94,6 +95,29 @@ class mt_scene_desc(C.Structure):
                 ("materials", C.c_void_p), ("textures", C.c_void_p)]
 
 
+class mt_gbuffer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "point", "normal", "uvw", "albedo", "prim", "line_no", "material")]
+
+
+# the planes of mt_gbuffer in declaration order: name -> (dtype, values per pixel); bit i of the facade's
+# GBuffer::channels is plane i
+GBUFFER_PLANES = {"depth": (np.float64, 1), "point": (np.float64, 3), "normal": (np.float64, 3),
+                  "uvw": (np.float64, 3), "albedo": (np.float64, 3), "prim": (np.int32, 1),
+                  "line_no": (np.int32, 1), "material": (np.int32, 1)}
+
+
+def _gbuffer_arrays(channels, cw, ch):
+    names = list(GBUFFER_PLANES) if channels is None else list(channels)
+    for n in names:
+        if n not in GBUFFER_PLANES:
+            raise ValueError("unknown G-buffer plane %r (planes: %s)" % (n, ", ".join(GBUFFER_PLANES)))
+    out = {}
+    for n in names:
+        dt, k = GBUFFER_PLANES[n]
+        out[n] = np.zeros((max(ch, 0), max(cw, 0)) + ((k,) if k > 1 else ()), dtype=dt)
+    return out
+
+
 DEBUG_PX_DTYPE = np.dtype([("line_no", "<i4"), ("reserved", "<i4"), ("point", "<f8", 3)])
 
 
@@ -153,6 +177,8 @@ class HipAbi:
         L.mt_render_chunk_ss.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
         L.mt_render_chunk_ss_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
         L.mt_resolve_tiles_device.argtypes = [vp] + [ci] * 6 + [vp, ci, ci, vp, vp, vp]
+        L.mt_render_gbuffer.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + [C.POINTER(mt_gbuffer), vp]
+        L.mt_render_gbuffer_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + [C.POINTER(mt_gbuffer), vp]
 
     def last_error(self) -> str:
         return self.lib.mt_last_error().decode(errors="replace")
@@ -323,6 +349,30 @@ class HipAbi:
         self.check(self.lib.mt_resolve_tiles_device(h, image_w, image_h, tile_w, tile_h, first_tile, tile_stride,
                                                     d_list, n_tiles, ss, d_samples, d_tiles, stream))
 
+    # ---- the primary-hit G-buffer (include/mythtracer_hip.h, mt_render_gbuffer)
+    def render_gbuffer(self, h, sensor12, image_w, image_h, chunk=None, channels=None):
+        """mt_render_gbuffer: dict plane name -> numpy array of the chunk ((ch, cw) or (ch, cw, 3)) for the planes
+        named in `channels` (None = all of GBUFFER_PLANES), plus "stats"."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        out = _gbuffer_arrays(channels, cw, ch)
+        g = mt_gbuffer(**{n: a.ctypes.data for n, a in out.items()})
+        st = mt_stats()
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_gbuffer(h, C.byref(s), image_w, image_h, cx, cy, cw, ch, C.byref(g),
+                                              C.addressof(st)))
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_gbuffer_device(self, h, sensor12, image_w, image_h, chunk, d_planes, stream=None):
+        """mt_render_gbuffer_device: d_planes = dict plane name -> device pointer (int or c_void_p) of the planes
+        wanted; asynchronous on `stream`."""
+        for n in d_planes:
+            if n not in GBUFFER_PLANES:
+                raise ValueError("unknown G-buffer plane %r" % (n,))
+        g = mt_gbuffer(**{n: (p.value if isinstance(p, C.c_void_p) else p) for n, p in d_planes.items()})
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_gbuffer_device(h, C.byref(s), image_w, image_h, *chunk, C.byref(g), stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -448,6 +498,7 @@ def host_lib():
     L.mth_sensor_ray.restype = None
     L.mth_render_chunk.argtypes = [vp, vp] + [ci] * 6 + [vp] * 5
     L.mth_render_image.argtypes = [vp, vp, ci, ci, vp]
+    L.mth_render_gbuffer.argtypes = [vp, vp] + [ci] * 6 + [C.c_uint, vp, vp, vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mth_chunk_serialize_input.argtypes = [vp, vp]
@@ -632,6 +683,23 @@ class MythTracer:
         return dict(rgb=rgb, line=dl, point=dp,
                     counters=dict(zip(STAT_NAMES, (int(x) for x in st))),
                     kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def gbuffer(self, cam, image_w, image_h, chunk=None, channels=None):
+        """MythTracer::RayTraceGBuffer: dict plane name -> numpy array of the chunk for the planes named in `channels`
+        (None = all of GBUFFER_PLANES), plus counters, kernel_ms, total_ms."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        out = _gbuffer_arrays(channels, cw, ch)
+        names = list(GBUFFER_PLANES)
+        bits = sum(1 << names.index(n) for n in out)
+        planes = (C.c_void_p * 8)(*[out[n].ctypes.data if n in out else None for n in names])
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        cam = _f64(cam)
+        if not self.L.mth_render_gbuffer(self.h, _ptr(cam), image_w, image_h, cx, cy, cw, ch, bits, planes,
+                                         _ptr(st), _ptr(ms)):
+            raise RuntimeError("RayTraceGBuffer failed: " + self.last_error())
+        out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+        return out
 
     def render_image(self, cam, image_w, image_h):
         """MythTracer::RayTrace(int, int, Camera*, vector<uint8_t>*)."""

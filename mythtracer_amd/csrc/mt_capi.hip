@@ -26,6 +26,7 @@
 // side so that no relocatable device code is needed.
 #include "mt_render.hip"
 #include "mt_resolve.h"
+#include "mt_gbuffer.h"
 
 using namespace mt;
 
@@ -219,6 +220,17 @@ struct mt_scene {
   // tile-list launches (mt_render_tile_list_device): the launch's own copy of the list, and tile -> slot
   Buf<int32_t> d_tile_list;
   Buf<int32_t> d_tile_slot;
+  // mt_render_gbuffer (mt_gbuffer.h): stream index -> AddPrimitive index (mt_scene_desc::tri_id; kept OUTSIDE DevScene:
+  // only gbuffer_kernel reads it; uploaded by the first call that wants the `prim` plane, like everything else here
+  // allocated on first use: a scene that never makes a G-buffer has the allocations it had without the feature), the
+  // kernel's work counter, the host call's planes and the events of its staged copies
+  std::vector<int32_t> tri_id_host;
+  Buf<int32_t> d_tri_id;
+  bool have_tri_id = false;
+  Buf<unsigned int> d_gb_work;
+  Buf<double> d_gb_f64[5];
+  Buf<int32_t> d_gb_i32[3];
+  std::vector<hipEvent_t> ev_gb;
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -280,12 +292,13 @@ using SceneKernel = void (*)(DevScene, RenderParams);
 struct LayoutKernels {
   SceneKernel render[2], primary[2], pool[2], hybrid[2], probe;
   void (*intersect)(DevScene, int, const double *, int *, int *, double *, double *, unsigned long long *);
+  void (*gbuffer[2])(DevScene, GBufferArgs);
 };
 template <int D>
 LayoutKernels layout_kernels() {
   return {{render_kernel<false, D>, render_kernel<true, D>}, {primary_kernel<false, D>, primary_kernel<true, D>},
           {pool_kernel<false, D>, pool_kernel<true, D>}, {hybrid_kernel<false, D>, hybrid_kernel<true, D>},
-          probe_kernel<D>, intersect_kernel<D>};
+          probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -318,6 +331,7 @@ int configure_launch(mt_scene *s) {
         }
         HIP_TRY(hipFuncSetAttribute((const void *)k.probe, kLdsAttr, (int)bytes));
         HIP_TRY(hipFuncSetAttribute((const void *)k.intersect, kLdsAttr, (int)bytes));
+        for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)k.gbuffer[st], kLdsAttr, (int)bytes));
       }
       have = bytes;
     }
@@ -984,6 +998,7 @@ void mt_scene_destroy(mt_scene *s) {
   for (hipEvent_t e : s->ev_stage) {
     if (e) (void)hipEventDestroy(e);
   }
+  for (hipEvent_t e : s->ev_gb) (void)hipEventDestroy(e);
   if (s->multi_comb_done) (void)hipEventDestroy(s->multi_comb_done);
   if (s->multi_stream) (void)hipStreamDestroy(s->multi_stream);
   if (s->multi_done) (void)hipEventDestroy(s->multi_done);
@@ -1375,6 +1390,10 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   if ((rc = upload(s, d->tri_uvw, nt * 9, &s->dev.tri_uvw)) != MT_OK) return rc;
   if ((rc = upload(s, d->tri_material, nt, &s->dev.tri_mtl)) != MT_OK) return rc;
   if ((rc = upload(s, d->tri_line_no, nt, &s->dev.tri_line)) != MT_OK) return rc;
+  if (d->tri_id != nullptr) {  // (mt_render_gbuffer's `prim` plane; not part of DevScene)
+    s->tri_id_host.assign(d->tri_id, d->tri_id + nt);
+    s->have_tri_id = true;
+  }
   if ((rc = upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls)) != MT_OK) return rc;
   std::vector<DevTexture> texs((size_t)d->n_textures);
   for (int i = 0; i < d->n_textures; i++) {
@@ -1845,6 +1864,156 @@ int mt_resolve_tiles_device(mt_scene *s, int image_w, int image_h, int tile_w, i
   return launch_resolve(ss, image_w, image_h, tile_w, tile_h, d_list ? 0 : first_tile, d_list ? 1 : tile_stride,
                         (const int32_t *)d_list, n_tiles, (const uint8_t *)d_samples, (uint8_t *)d_tiles,
                         (hipStream_t)stream);
+}
+
+// ---- the primary-hit G-buffer (mt_gbuffer.h): one kernel next to the frame kernels.  Nothing here reads or writes
+// what decide_launch looks at (cost history, signatures, launch counts, events of mt_scene_kernel_times). ----
+namespace {
+
+constexpr int kGbPlanes = 8;
+// the planes of an mt_gbuffer in declaration order, and a pixel's bytes in each
+void gb_planes(const mt_gbuffer &g, void *out[kGbPlanes]) {
+  void *p[kGbPlanes] = {g.depth, g.point, g.normal, g.uvw, g.albedo, g.prim, g.line_no, g.material};
+  for (int i = 0; i < kGbPlanes; i++) out[i] = p[i];
+}
+constexpr size_t kGbPixelBytes[kGbPlanes] = {8, 24, 24, 24, 24, 4, 4, 4};
+
+// Checked before any device call; the order lets a caller without a device reach every message.
+int check_gbuffer_args(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                       int chunk_w, int chunk_h, const mt_gbuffer *out) {
+  if (!out) return fail(MT_ERR_ARG, "the mt_gbuffer is NULL");
+  void *p[kGbPlanes];
+  gb_planes(*out, p);
+  bool any = false;
+  for (void *q : p) any = any || q != nullptr;
+  if (!any) return fail(MT_ERR_ARG, "no plane of the mt_gbuffer is set");
+  if (image_w <= 0 || image_h <= 0 || image_w > 100000 || image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d out of range", image_w, image_h);
+  }
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  if (out->prim != nullptr && !s->have_tri_id) {
+    return fail(MT_ERR_UNSUPPORTED, "the scene was created without mt_scene_desc::tri_id: no prim plane");
+  }
+  return MT_OK;
+}
+
+// gbuffer_kernel over the chunk, planes = device pointers
+int launch_gbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                   const mt_gbuffer &d, hipStream_t stream) {
+  GBufferArgs A{};
+  A.sensor = *sensor;
+  A.chunk_x = chunk_x; A.chunk_y = chunk_y; A.chunk_w = chunk_w; A.chunk_h = chunk_h;
+  A.blocks_x = (chunk_w + 7) / 8;
+  const unsigned long long items = (unsigned long long)A.blocks_x * (unsigned long long)((chunk_h + 7) / 8);
+  if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
+  A.n_items = (unsigned)items;
+  A.depth = d.depth; A.point = d.point; A.normal = d.normal; A.uvw = d.uvw; A.albedo = d.albedo;
+  A.prim = d.prim; A.line_no = d.line_no; A.material = d.material;
+  if (d.prim != nullptr && s->d_tri_id == nullptr) {  // first use (synchronous, once per scene)
+    MT_TRY(s->d_tri_id.ensure(s->tri_id_host.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(s->d_tri_id, s->tri_id_host.data(), s->tri_id_host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  MT_TRY(s->d_gb_work.ensure(64));
+  A.tri_id = s->d_tri_id;
+  A.counters = s->d_counters;
+  A.work_counter = s->d_gb_work;
+  MT_TRY(ensure_deep(s, (size_t)s->grid_blocks * s->waves_per_block));
+  if (!s->dev_uploaded_valid || memcmp(&s->dev_uploaded, &s->dev, sizeof(DevScene)) != 0) {  // (as launch_kernels)
+    HIP_TRY(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, stream));
+    memcpy(&s->dev_uploaded, &s->dev, sizeof(DevScene));
+    s->dev_uploaded_valid = true;
+  }
+  HIP_TRY(hipMemsetAsync(s->d_gb_work, 0, sizeof(unsigned), stream));
+  const unsigned grid = (unsigned)std::min<unsigned long long>((unsigned long long)s->grid_blocks,
+                                                               (items + s->waves_per_block - 1) / s->waves_per_block);
+  hipLaunchKernelGGL(kernels_of(s->deep).gbuffer[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
+                     s->lds_bytes, stream, s->dev, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_render_gbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                             int chunk_w, int chunk_h, const mt_gbuffer *d_out, void *stream) {
+  MT_TRY(check_gbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, d_out));
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_gbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, *d_out, (hipStream_t)stream);
+}
+
+// The host call: the requested planes in buffers the scene owns, then to the caller through the page-locked staging
+// buffer in pieces, every piece's memcpy under the next piece's DMA (finish_host_chunk's path).
+int mt_render_gbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                      int chunk_w, int chunk_h, const mt_gbuffer *out, mt_stats *stats) {
+  MT_TRY(check_gbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, out));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  hipStream_t stream = nullptr;
+  void *host[kGbPlanes], *dev[kGbPlanes] = {};
+  gb_planes(*out, host);
+  size_t total = 0;
+  for (int i = 0; i < kGbPlanes; i++) {
+    if (!host[i]) continue;
+    if (i < 5) { MT_TRY(s->d_gb_f64[i].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_f64[i].p; }
+    else { MT_TRY(s->d_gb_i32[i - 5].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_i32[i - 5].p; }
+    total += (npx * kGbPixelBytes[i] + 4095) & ~(size_t)4095;
+  }
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  MT_TRY(s->h_stage.ensure(total));
+  const mt_gbuffer d{(double *)dev[0], (double *)dev[1], (double *)dev[2], (double *)dev[3], (double *)dev[4],
+                     (int32_t *)dev[5], (int32_t *)dev[6], (int32_t *)dev[7]};
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = launch_gbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d, stream);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  // pieces of at most 4 MB: (caller's address, staging offset, bytes), queued in plane order
+  struct Piece { uint8_t *dst; size_t off, bytes; };
+  std::vector<Piece> pieces;
+  constexpr size_t kPiece = 4u << 20;
+  size_t at = 0;
+  for (int i = 0; i < kGbPlanes; i++) {
+    if (!host[i]) continue;
+    const size_t bytes = npx * kGbPixelBytes[i];
+    for (size_t o = 0; o < bytes; o += kPiece) {
+      const size_t n = std::min(kPiece, bytes - o);
+      HIP_TRY(hipMemcpyAsync(s->h_stage + at + o, (const uint8_t *)dev[i] + o, n, hipMemcpyDeviceToHost, stream));
+      while (s->ev_gb.size() <= pieces.size()) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        s->ev_gb.push_back(e);
+      }
+      HIP_TRY(hipEventRecord(s->ev_gb[pieces.size()], stream));
+      pieces.push_back({(uint8_t *)host[i] + o, at + o, n});
+    }
+    at += (bytes + 4095) & ~(size_t)4095;
+  }
+  for (size_t k = 0; k < pieces.size(); k++) {
+    HIP_TRY(hipEventSynchronize(s->ev_gb[k]));
+    if (k == 0 && check_status(s->h_counters) != MT_OK) {  // (the counters came first: no planes of a failed launch)
+      (void)hipStreamSynchronize(stream);
+      return check_status(s->h_counters);
+    }
+    memcpy(pieces[k].dst, s->h_stage + pieces[k].off, pieces[k].bytes);
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  MT_TRY(check_status(s->h_counters));
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    fill_stats(s->h_counters, stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
+  return MT_OK;
 }
 
 // ---- one frame on several GPUs of this process (main_net_master.cc:195-236) --------------------------

@@ -52,6 +52,23 @@ struct RenderStats {
   double kernel_ms = 0, total_ms = 0;
 };
 
+// The primary-hit G-buffer of a frame or chunk (extension; mt_render_gbuffer in mythtracer_hip.h): per pixel the first
+// hit's distance, point, Triangle::GetNormal (as returned: not flipped towards the camera), Triangle::GetUVW, unlit
+// surface colour (material ambient x texture), AddPrimitive index, .obj line and material.  `channels` says which planes
+// RayTraceGBuffer fills (the others are left empty and cost nothing); every plane is chunk-local row-major, the V3D
+// planes three doubles per pixel.  A miss: NaN / -1.  material = the triangle's material in order of first use by the
+// octree's triangle stream (FlatScene::materials), -1 = none (albedo is then NaN).
+struct GBuffer {
+  enum : unsigned {
+    kDepth = 1u, kPoint = 2u, kNormal = 4u, kUvw = 8u, kAlbedo = 16u, kPrim = 32u, kLineNo = 64u, kMaterial = 128u,
+    kAll = 255u
+  };
+  unsigned channels = kAll;
+  int width = 0, height = 0;  // of the chunk the planes describe
+  std::vector<double> depth, point, normal, uvw, albedo;
+  std::vector<int32_t> prim, line_no, material;
+};
+
 class MythTracer {
  public:
   MythTracer();
@@ -82,6 +99,14 @@ class MythTracer {
   // debug record belongs to a ray, not to a mean) and, for the W x H overload, s > 1 with more than one device
   // (SetDevices): a supersampled frame is rendered on one device, never silently so when several were asked for.
   void SetSupersampling(int s) { supersampling_ = s; }
+  // The primary-hit G-buffer of a W x H frame, or of chunk->chunk_* (its camera and image size; output_bitmap and
+  // output_debug are not touched).  No reference counterpart: the reference returns a colour and PerPixelDebugInfo.
+  // One kernel launch next to the frame's (mt_render_gbuffer); the frames' cost history is left alone.
+  // SetSupersampling does NOT apply: a G-buffer value belongs to one ray, the pixel's, never to a mean -- the call
+  // ignores the factor.  With more than one device (SetDevices) the call is refused with a message: there is no
+  // multi-GPU G-buffer, and it is never silently rendered on the first device.  LastStats() describes the call.
+  bool RayTraceGBuffer(int image_width, int image_height, Camera* camera, GBuffer* out);
+  bool RayTraceGBuffer(WorkChunk* chunk, GBuffer* out);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

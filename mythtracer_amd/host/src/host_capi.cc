@@ -291,6 +291,36 @@ int mth_render_chunk(void* p, const double* cam7, int iw, int ih, int cx, int cy
   return 1;
 }
 
+// MythTracer::RayTraceGBuffer(WorkChunk*, GBuffer*).  channels = GBuffer::k* bits; planes[8] = depth, point, normal,
+// uvw, albedo (doubles), prim, line_no, material (int32), each NULL or sized for the chunk.
+int mth_render_gbuffer(void* p, const double* cam7, int iw, int ih, int cx, int cy, int cw, int ch, unsigned channels,
+                       void* const* planes, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  WorkChunk chunk{iw, ih, cx, cy, cw, ch, MakeCamera(cam7), {}, {}};
+  raytracer::GBuffer g;
+  g.channels = channels;
+  if (!h->mt.RayTraceGBuffer(&chunk, &g)) return 0;
+  const std::vector<double>* f[5] = {&g.depth, &g.point, &g.normal, &g.uvw, &g.albedo};
+  const std::vector<int32_t>* i32[3] = {&g.prim, &g.line_no, &g.material};
+  for (int k = 0; k < 5; k++) {
+    if (planes[k] && !f[k]->empty()) memcpy(planes[k], f[k]->data(), f[k]->size() * 8);
+  }
+  for (int k = 0; k < 3; k++) {
+    if (planes[5 + k] && !i32[k]->empty()) memcpy(planes[5 + k], i32[k]->data(), i32[k]->size() * 4);
+  }
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::RayTrace(int, int, Camera*, vector*)
 int mth_render_image(void* p, const double* cam7, int iw, int ih, uint8_t* rgb) {
   Handle* h = static_cast<Handle*>(p);

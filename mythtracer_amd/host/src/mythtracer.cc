@@ -359,6 +359,68 @@ bool MythTracer::RayTrace(WorkChunk* chunk) {
   return true;
 }
 
+bool MythTracer::RayTraceGBuffer(int image_width, int image_height, Camera* camera, GBuffer* out) {
+  WorkChunk chunk{image_width, image_height, 0, 0, image_width, image_height, *camera, {}, {}};
+  return RayTraceGBuffer(&chunk, out);
+}
+
+bool MythTracer::RayTraceGBuffer(WorkChunk* chunk, GBuffer* out) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device: a caller without one sees these messages too)
+  if (out == nullptr) return refuse("GBuffer is NULL");
+  if (devices_.size() > 1) return refuse("the G-buffer is not supported with several devices (SetDevices)");
+  if ((out->channels & GBuffer::kAll) == 0) return refuse("GBuffer::channels selects no plane");
+  if (chunk->chunk_width <= 0 || chunk->chunk_height <= 0) return refuse("empty chunk");
+  if (!Prepare()) return false;
+  // (the reference's sensor of the image: one ray per pixel, whatever SetSupersampling says)
+  const Camera::Sensor sensor = chunk->camera.GetSensor(chunk->image_width, chunk->image_height);
+  mt_sensor ms;
+  memcpy(ms.origin, chunk->camera.origin.v, 24);
+  memcpy(ms.start_point, sensor.StartPoint().v, 24);
+  memcpy(ms.delta_scanline, sensor.DeltaScanline().v, 24);
+  memcpy(ms.delta_pixel, sensor.DeltaPixel().v, 24);
+  const size_t npx = (size_t)chunk->chunk_width * (size_t)chunk->chunk_height;
+  const unsigned c = out->channels;
+  auto sized = [&](auto& v, unsigned bit, size_t per_px) -> decltype(v.data()) {
+    v.clear();
+    if (!(c & bit)) return nullptr;
+    v.resize(npx * per_px);
+    return v.data();
+  };
+  mt_gbuffer g;
+  g.depth = sized(out->depth, GBuffer::kDepth, 1);
+  g.point = sized(out->point, GBuffer::kPoint, 3);
+  g.normal = sized(out->normal, GBuffer::kNormal, 3);
+  g.uvw = sized(out->uvw, GBuffer::kUvw, 3);
+  g.albedo = sized(out->albedo, GBuffer::kAlbedo, 3);
+  g.prim = sized(out->prim, GBuffer::kPrim, 1);
+  g.line_no = sized(out->line_no, GBuffer::kLineNo, 1);
+  g.material = sized(out->material, GBuffer::kMaterial, 1);
+  out->width = chunk->chunk_width;
+  out->height = chunk->chunk_height;
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_render_gbuffer(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x, chunk->chunk_y,
+                        chunk->chunk_width, chunk->chunk_height, &g, &st) != MT_OK) {
+    return refuse(std::string("G-buffer failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_primary = st.rays_primary;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.shaded_hits = st.shaded_hits;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
 // ---- wire format of a chunk (mythtracer.cc:314-429): six little-endian u32
 // in, u32 byte count + RGB bytes out.
 
