@@ -300,6 +300,77 @@ int mt_render_gbuffer_device(mt_scene *scene, const mt_sensor *sensor, int image
                              int chunk_x, int chunk_y, int chunk_w, int chunk_h,
                              const mt_gbuffer *d_out, void *stream);
 
+/* The direct-light buffer of a chunk and the deferred relight pass: the direct term of TraceRayWorker
+ * (mythtracer.cc:38-177) cut where geometry ends and light colours begin.  (No reference counterpart.)
+ *
+ * mt_render_lightbuffer runs, for every pixel of the chunk and every light of the scene (mt_scene_set_lights, in light
+ * order), the shadow loop of mythtracer.cc:90-156 -- from the primary hit towards the light, through every transparent
+ * occluder -- with the frame kernels' arithmetic, and stores what the loop leaves behind:
+ *   power      [n_lights][chunk_h][chunk_w][3] doubles: light_power when the loop of that light ends, BEFORE
+ *              mythtracer.cc:159-161 raise it to light.ambient
+ *   in_shadow  [n_lights][chunk_h][chunk_w] bytes: 0 = lit, 1 = in_shadow, 255 = no light loop ran for this pixel
+ * Pixels for which the reference never enters the light loop -- a miss (:23-31) or a hit on a triangle without a
+ * material (:49-52) -- get NaN in power and 255 in in_shadow.  An OCCLUDER without a material counts as opaque, as in
+ * the frame kernels (the reference dereferences its NULL mtl, :121).  Both planes depend on geometry, materials and the
+ * lights' POSITIONS only: not on any light's ambient, diffuse or specular.  Each pointer of `lb` is nullable -- a plane
+ * nobody asked for is not written -- but at least one must be set.  `gb` (nullable, and each of its pointers too): the
+ * G-buffer planes requested through it are written by the same launch from the same primary trace, with the bits
+ * mt_render_gbuffer gives: one call delivers everything a relight needs.  With zero lights set the light-buffer planes
+ * are empty (nothing is written through `lb`) and the call is valid only if a plane of `gb` is requested: MT_ERR_ARG
+ * otherwise.
+ *   mt_render_lightbuffer: host pointers; stats (nullable): rays_primary = chunk pixels, rays_shadow = iterations of
+ *     the shadow loops, shaded_hits = primary hits, the traversal's counters, kernel_ms = the kernel by HIP events,
+ *     total_ms = wall time of the call.
+ *   mt_render_lightbuffer_device: `d_gb` / `d_lb` (host structs) hold DEVICE pointers on the scene's GPU; asynchronous
+ *     on `stream`; counters as for mt_render_chunk_device.
+ * One kernel next to the frame kernels (mt::lightbuffer_kernel).  Like the G-buffer calls these leave everything a frame
+ * launch decides by -- cost history, engine choice, forecasts, mt_scene_kernel_times -- alone.
+ *
+ * mt_shade_direct evaluates mythtracer.cc:38-177 per pixel from stored planes, without any traversal, in the
+ * reference's order of operations: the pixel's ray from `sensor` (Sensor::GetRay); towards_camera and the normal flip of
+ * :40-45 applied to the stored (unflipped) normal; the grey of :49-52 where material == -1 on a hit; black for a miss
+ * (a miss <=> point[0] is NaN); reflected_direction (:68-69); then per light, in the order of `lights`:
+ * light_direction = Norm(position - point); colour += ambient * albedo; lp = max(power, ambient) per channel;
+ * colour += material.diffuse * albedo * dot(light_direction, normal) * diffuse * lp; and, where in_shadow == 0 and
+ * dot(reflected_direction, towards_camera) > 0, the specular term of :169-177; finally V3DtoRGB (:235-241).  Material
+ * constants come from the scene.  It needs the point, normal, albedo and material planes of the G-buffer and both planes
+ * of the light buffer, all of the same chunk of the same image for the same sensor.
+ * `lights` (a HOST array in both forms; the scene's own lights are neither read nor changed) may differ from the lights
+ * the light buffer was made with in ambient, diffuse and specular ONLY: the count and every position must be the same.
+ * Neither is checked -- the calls are stateless, the planes carry no record of their lights -- and a MOVED light needs a
+ * new light buffer.  A value of the material plane outside the scene's materials (planes of another scene) is shaded as
+ * "no material".
+ * CONTRACT: for unchanged positions the bitmap is byte-identical to mt_render_chunk(..., max_depth = 0, ...) after
+ * mt_scene_set_lights(lights, n_lights).
+ *   mt_shade_direct_device: device pointers in `d_gb`, `d_lb` and `d_rgb` (chunk_w * chunk_h * 3 bytes); asynchronous
+ *     on `stream`.  Up to 8 lights travel with the launch; a longer `lights` array is copied by the stream, into a buffer
+ *     the scene owns, and must stay unchanged until the stream has reached the call.
+ * As for every call on an mt_scene, one call may be in flight per scene at a time: the *_device forms of one scene go to
+ * ONE stream (or are ordered by the caller) -- they share the scene's work counter, statistics and that light buffer.
+ *   mt_shade_direct: host pointers; stats (nullable): kernel_ms = mt::shade_direct_kernel by HIP events, total_ms =
+ *     wall time of the call with its copies; the work counters are zero (no ray is traced).
+ *
+ * Argument checks come before any device call, in this order: the `lb` and `gb` pointers (and, for mt_shade_direct, the
+ * bitmap), image size and chunk (mt_render_chunk's limits and messages), scene, sensor, lights. */
+typedef struct mt_lightbuffer {
+  double *power;
+  uint8_t *in_shadow;
+} mt_lightbuffer;
+int mt_render_lightbuffer(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                          int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                          const mt_gbuffer *gb, const mt_lightbuffer *lb, mt_stats *stats);
+int mt_render_lightbuffer_device(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                                 int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                                 const mt_gbuffer *d_gb, const mt_lightbuffer *d_lb, void *stream);
+int mt_shade_direct(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                    int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                    const mt_gbuffer *gb, const mt_lightbuffer *lb, const mt_light *lights, int n_lights,
+                    uint8_t *out_rgb, mt_stats *stats);
+int mt_shade_direct_device(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                           int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                           const mt_gbuffer *d_gb, const mt_lightbuffer *d_lb, const mt_light *lights,
+                           int n_lights, void *d_rgb, void *stream);
+
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into
  * WorkChunks, every worker renders chunks with the full-image sensor from its

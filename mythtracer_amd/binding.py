@@ -27,6 +27,7 @@ HIP_SYMBOLS = [
     "mt_render_tile_list_device", "mt_blit_tile_list_device",
     "mt_render_chunk_ss", "mt_render_chunk_ss_device", "mt_resolve_tiles_device",
     "mt_render_gbuffer", "mt_render_gbuffer_device",
+    "mt_render_lightbuffer", "mt_render_lightbuffer_device", "mt_shade_direct", "mt_shade_direct_device",
 ]
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
@@ -118,6 +119,49 @@ def _gbuffer_arrays(channels, cw, ch):
     return out
 
 
+class mt_lightbuffer(C.Structure):
+    _fields_ = [("power", C.c_void_p), ("in_shadow", C.c_void_p)]
+
+
+# the planes of mt_lightbuffer: name -> (dtype, values per pixel and light); arrays are (n_lights, ch, cw[, 3])
+LIGHTBUFFER_PLANES = {"power": (np.float64, 3), "in_shadow": (np.uint8, 1)}
+# what a relight reads of the G-buffer
+RELIGHT_GBUFFER_PLANES = ("point", "normal", "albedo", "material")
+
+
+def _lightbuffer_arrays(channels, n_lights, cw, ch):
+    names = list(LIGHTBUFFER_PLANES) if channels is None else list(channels)
+    for n in names:
+        if n not in LIGHTBUFFER_PLANES:
+            raise ValueError("unknown light-buffer plane %r (planes: %s)" % (n, ", ".join(LIGHTBUFFER_PLANES)))
+    out = {}
+    for n in names:
+        dt, k = LIGHTBUFFER_PLANES[n]
+        out[n] = np.zeros((n_lights, max(ch, 0), max(cw, 0)) + ((k,) if k > 1 else ()), dtype=dt)
+    return out
+
+
+def _relight_planes(gbuffer, lightbuffer, cw, ch):
+    """The six planes of a relight as contiguous arrays of the right type and shape; n_lights from `power`."""
+    g = {}
+    for n in RELIGHT_GBUFFER_PLANES:
+        if n not in gbuffer:
+            raise ValueError("the relight pass needs the G-buffer plane %r" % n)
+        dt, k = GBUFFER_PLANES[n]
+        g[n] = np.ascontiguousarray(gbuffer[n], dtype=dt)
+        if g[n].shape != (ch, cw) + ((k,) if k > 1 else ()):
+            raise ValueError("G-buffer plane %r has shape %s, not that of the %dx%d chunk" % (n, g[n].shape, cw, ch))
+    for n in LIGHTBUFFER_PLANES:
+        if n not in lightbuffer:
+            raise ValueError("the relight pass needs the light-buffer plane %r" % n)
+    power = np.ascontiguousarray(lightbuffer["power"], dtype=np.float64)
+    shadow = np.ascontiguousarray(lightbuffer["in_shadow"], dtype=np.uint8)
+    n_l = power.shape[0]
+    if power.shape != (n_l, ch, cw, 3) or shadow.shape != (n_l, ch, cw):
+        raise ValueError("light-buffer planes of shape %s / %s do not fit the %dx%d chunk" % (power.shape, shadow.shape, cw, ch))
+    return g, dict(power=power, in_shadow=shadow), n_l
+
+
 DEBUG_PX_DTYPE = np.dtype([("line_no", "<i4"), ("reserved", "<i4"), ("point", "<f8", 3)])
 
 
@@ -179,6 +223,11 @@ class HipAbi:
         L.mt_resolve_tiles_device.argtypes = [vp] + [ci] * 6 + [vp, ci, ci, vp, vp, vp]
         L.mt_render_gbuffer.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + [C.POINTER(mt_gbuffer), vp]
         L.mt_render_gbuffer_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + [C.POINTER(mt_gbuffer), vp]
+        gl = [C.POINTER(mt_gbuffer), C.POINTER(mt_lightbuffer)]
+        L.mt_render_lightbuffer.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp]
+        L.mt_render_lightbuffer_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp]
+        L.mt_shade_direct.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp, ci, vp, vp]
+        L.mt_shade_direct_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp, ci, vp, vp]
 
     def last_error(self) -> str:
         return self.lib.mt_last_error().decode(errors="replace")
@@ -373,6 +422,69 @@ class HipAbi:
         s = self.make_sensor(sensor12)
         self.check(self.lib.mt_render_gbuffer_device(h, C.byref(s), image_w, image_h, *chunk, C.byref(g), stream))
 
+    # ---- the direct-light buffer and the relight pass (include/mythtracer_hip.h, mt_render_lightbuffer)
+    def render_lightbuffer(self, h, sensor12, image_w, image_h, n_lights, chunk=None, channels=None,
+                           gbuffer_channels=()):
+        """mt_render_lightbuffer for a scene whose n_lights lights are set: dict with the light-buffer planes named in
+        `channels` (None = both; (n_lights, ch, cw, 3) float64 `power`, (n_lights, ch, cw) uint8 `in_shadow`), the
+        G-buffer planes named in `gbuffer_channels` (None = all, default none) from the same launch, and "stats"."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        out = _lightbuffer_arrays(channels, n_lights, cw, ch)
+        lb = mt_lightbuffer(**{n: a.ctypes.data for n, a in out.items()})
+        planes = _gbuffer_arrays(gbuffer_channels, cw, ch)
+        g = mt_gbuffer(**{n: a.ctypes.data for n, a in planes.items()})
+        st = mt_stats()
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_lightbuffer(h, C.byref(s), image_w, image_h, cx, cy, cw, ch,
+                                                  C.byref(g) if planes else None, C.byref(lb), C.addressof(st)))
+        out.update(planes)
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_lightbuffer_device(self, h, sensor12, image_w, image_h, chunk, d_lb_planes, d_gb_planes=None, stream=None):
+        """mt_render_lightbuffer_device: dicts plane name -> device pointer; asynchronous on `stream`."""
+        for n in d_lb_planes:
+            if n not in LIGHTBUFFER_PLANES:
+                raise ValueError("unknown light-buffer plane %r" % (n,))
+        for n in d_gb_planes or {}:
+            if n not in GBUFFER_PLANES:
+                raise ValueError("unknown G-buffer plane %r" % (n,))
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p  # noqa: E731
+        lb = mt_lightbuffer(**{n: val(p) for n, p in d_lb_planes.items()})
+        g = mt_gbuffer(**{n: val(p) for n, p in (d_gb_planes or {}).items()})
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_render_lightbuffer_device(h, C.byref(s), image_w, image_h, *chunk,
+                                                         C.byref(g) if d_gb_planes else None, C.byref(lb), stream))
+
+    def shade_direct(self, h, sensor12, image_w, image_h, gbuffer, lightbuffer, lights, chunk=None):
+        """mt_shade_direct: the frame of the direct term from the planes of render_gbuffer / render_lightbuffer (dicts
+        of numpy arrays of the chunk) under `lights` (n x 12: position, ambient, diffuse, specular -- positions and
+        count as when the light buffer was made).  Returns dict(rgb, stats)."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        gp, lp, n_l = _relight_planes(gbuffer, lightbuffer, cw, ch)
+        l = _f64(lights).reshape(-1, 12)
+        if l.shape[0] != n_l:
+            raise ValueError("%d lights for a light buffer of %d" % (l.shape[0], n_l))
+        g = mt_gbuffer(**{n: a.ctypes.data for n, a in gp.items()})
+        lb = mt_lightbuffer(**{n: a.ctypes.data for n, a in lp.items()})
+        rgb = np.zeros((ch, cw, 3), dtype=np.uint8)
+        st = mt_stats()
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_shade_direct(h, C.byref(s), image_w, image_h, cx, cy, cw, ch, C.byref(g), C.byref(lb),
+                                            _ptr(l), n_l, _ptr(rgb), C.addressof(st)))
+        return dict(rgb=rgb, stats=st.as_dict())
+
+    def shade_direct_device(self, h, sensor12, image_w, image_h, chunk, d_gb_planes, d_lb_planes, lights, d_rgb,
+                            stream=None):
+        """mt_shade_direct_device: dicts plane name -> device pointer, `lights` a host array (n x 12)."""
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p  # noqa: E731
+        g = mt_gbuffer(**{n: val(p) for n, p in d_gb_planes.items()})
+        lb = mt_lightbuffer(**{n: val(p) for n, p in d_lb_planes.items()})
+        l = _f64(lights).reshape(-1, 12)
+        s = self.make_sensor(sensor12)
+        self.check(self.lib.mt_shade_direct_device(h, C.byref(s), image_w, image_h, *chunk, C.byref(g), C.byref(lb),
+                                                   _ptr(l), l.shape[0], d_rgb, stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -499,6 +611,9 @@ def host_lib():
     L.mth_render_chunk.argtypes = [vp, vp] + [ci] * 6 + [vp] * 5
     L.mth_render_image.argtypes = [vp, vp, ci, ci, vp]
     L.mth_render_gbuffer.argtypes = [vp, vp] + [ci] * 6 + [C.c_uint, vp, vp, vp]
+    L.mth_render_lightbuffer.argtypes = [vp, vp] + [ci] * 6 + [C.c_uint, vp, C.c_uint, vp, ci, vp, vp]
+    L.mth_shade_direct.argtypes = [vp, vp] + [ci] * 6 + [vp, ci, vp, vp, vp]
+    L.mth_num_lights.argtypes = [vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mth_chunk_serialize_input.argtypes = [vp, vp]
@@ -700,6 +815,50 @@ class MythTracer:
             raise RuntimeError("RayTraceGBuffer failed: " + self.last_error())
         out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
         return out
+
+    def lightbuffer(self, cam, image_w, image_h, chunk=None, channels=None, gbuffer_channels=None):
+        """MythTracer::RayTraceLightBuffer under the lights of set_lights: dict with the light-buffer planes named in
+        `channels` (None = both: `power` (n_lights, ch, cw, 3) float64, `in_shadow` (n_lights, ch, cw) uint8), the
+        G-buffer planes named in `gbuffer_channels` from the same launch (None = the four a relight reads; () = none),
+        plus counters, kernel_ms, total_ms."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        n_l = self.L.mth_num_lights(self.h)
+        out = _lightbuffer_arrays(channels, n_l, cw, ch)
+        planes = _gbuffer_arrays(RELIGHT_GBUFFER_PLANES if gbuffer_channels is None else gbuffer_channels, cw, ch)
+        names = list(GBUFFER_PLANES)
+        gbits = sum(1 << names.index(n) for n in planes)
+        gptrs = (C.c_void_p * 8)(*[planes[n].ctypes.data if n in planes else None for n in names])
+        lnames = list(LIGHTBUFFER_PLANES)
+        lbits = sum(1 << lnames.index(n) for n in out)
+        lptrs = (C.c_void_p * 2)(*[out[n].ctypes.data if n in out else None for n in lnames])
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        cam = _f64(cam)
+        if not self.L.mth_render_lightbuffer(self.h, _ptr(cam), image_w, image_h, cx, cy, cw, ch, gbits, gptrs, lbits,
+                                             lptrs, n_l, _ptr(st), _ptr(ms)):
+            raise RuntimeError("RayTraceLightBuffer failed: " + self.last_error())
+        out.update(planes)
+        out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+        return out
+
+    def relight(self, cam, image_w, image_h, gbuffer, lightbuffer, lights=None, chunk=None):
+        """MythTracer::ShadeDirect: the frame of the direct term (what render gives at max level 0) from stored planes,
+        without tracing a ray.  `lights` (n x 12) replaces the facade's lights first, as set_lights does; None keeps
+        them.  They may differ from the lights the light buffer was made with in their colours only: a moved light
+        needs a new light buffer.  Returns dict(rgb, kernel_ms, total_ms)."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        if lights is not None:
+            self.set_lights(lights)
+        gp, lp, n_l = _relight_planes(gbuffer, lightbuffer, cw, ch)
+        gptrs = (C.c_void_p * 4)(*[gp[n].ctypes.data for n in RELIGHT_GBUFFER_PLANES])
+        lptrs = (C.c_void_p * 2)(lp["power"].ctypes.data, lp["in_shadow"].ctypes.data)
+        rgb = np.zeros((ch, cw, 3), dtype=np.uint8)
+        ms = np.zeros(2)
+        cam = _f64(cam)
+        if not self.L.mth_shade_direct(self.h, _ptr(cam), image_w, image_h, cx, cy, cw, ch, gptrs, n_l, lptrs,
+                                       _ptr(rgb), _ptr(ms)):
+            raise RuntimeError("ShadeDirect failed: " + self.last_error())
+        return dict(rgb=rgb, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
 
     def render_image(self, cam, image_w, image_h):
         """MythTracer::RayTrace(int, int, Camera*, vector<uint8_t>*)."""

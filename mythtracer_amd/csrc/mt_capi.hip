@@ -27,6 +27,7 @@
 #include "mt_render.hip"
 #include "mt_resolve.h"
 #include "mt_gbuffer.h"
+#include "mt_lightbuffer.h"
 
 using namespace mt;
 
@@ -231,6 +232,12 @@ struct mt_scene {
   Buf<double> d_gb_f64[5];
   Buf<int32_t> d_gb_i32[3];
   std::vector<hipEvent_t> ev_gb;
+  // mt_render_lightbuffer / mt_shade_direct (mt_lightbuffer.h), allocated on first use: the host calls' light-buffer
+  // planes, and the lights of a relight with more than kShadeArgLights of them
+  Buf<double> d_lb_power;
+  Buf<uint8_t> d_lb_shadow;
+  Buf<mt_light> d_shade_lights;
+  int n_materials = 0;  // of dev.mtls (shade_direct_kernel checks the caller's material plane against it)
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -293,12 +300,14 @@ struct LayoutKernels {
   SceneKernel render[2], primary[2], pool[2], hybrid[2], probe;
   void (*intersect)(DevScene, int, const double *, int *, int *, double *, double *, unsigned long long *);
   void (*gbuffer[2])(DevScene, GBufferArgs);
+  void (*lightbuffer[2])(DevScene, LightBufferArgs);
 };
 template <int D>
 LayoutKernels layout_kernels() {
   return {{render_kernel<false, D>, render_kernel<true, D>}, {primary_kernel<false, D>, primary_kernel<true, D>},
           {pool_kernel<false, D>, pool_kernel<true, D>}, {hybrid_kernel<false, D>, hybrid_kernel<true, D>},
-          probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>}};
+          probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>},
+          {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -332,6 +341,7 @@ int configure_launch(mt_scene *s) {
         HIP_TRY(hipFuncSetAttribute((const void *)k.probe, kLdsAttr, (int)bytes));
         HIP_TRY(hipFuncSetAttribute((const void *)k.intersect, kLdsAttr, (int)bytes));
         for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)k.gbuffer[st], kLdsAttr, (int)bytes));
+        for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)k.lightbuffer[st], kLdsAttr, (int)bytes));
       }
       have = bytes;
     }
@@ -1395,6 +1405,7 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
     s->have_tri_id = true;
   }
   if ((rc = upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls)) != MT_OK) return rc;
+  s->n_materials = d->n_materials;
   std::vector<DevTexture> texs((size_t)d->n_textures);
   for (int i = 0; i < d->n_textures; i++) {
     const mt_texture &t = d->textures[i];
@@ -1898,24 +1909,29 @@ int check_gbuffer_args(const mt_scene *s, const mt_sensor *sensor, int image_w, 
   return MT_OK;
 }
 
-// gbuffer_kernel over the chunk, planes = device pointers
-int launch_gbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
-                   const mt_gbuffer &d, hipStream_t stream) {
-  GBufferArgs A{};
+// What gbuffer_kernel and lightbuffer_kernel share on the host: the chunk's blocks, the device-side planes (`d`
+// nullable: none), the work counter, the DEEP areas and the scene description of the launch.  Args = GBufferArgs or
+// LightBufferArgs.  Returns the grid in *grid.
+extern "C++" {  // (this file's functions sit inside one extern "C" block; a template needs C++ linkage)
+template <typename Args>
+int prepare_block_launch(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                         const mt_gbuffer *d, Args &A, unsigned *grid, hipStream_t stream) {
   A.sensor = *sensor;
   A.chunk_x = chunk_x; A.chunk_y = chunk_y; A.chunk_w = chunk_w; A.chunk_h = chunk_h;
   A.blocks_x = (chunk_w + 7) / 8;
   const unsigned long long items = (unsigned long long)A.blocks_x * (unsigned long long)((chunk_h + 7) / 8);
   if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
   A.n_items = (unsigned)items;
-  A.depth = d.depth; A.point = d.point; A.normal = d.normal; A.uvw = d.uvw; A.albedo = d.albedo;
-  A.prim = d.prim; A.line_no = d.line_no; A.material = d.material;
-  if (d.prim != nullptr && s->d_tri_id == nullptr) {  // first use (synchronous, once per scene)
-    MT_TRY(s->d_tri_id.ensure(s->tri_id_host.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(s->d_tri_id, s->tri_id_host.data(), s->tri_id_host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (d != nullptr) {
+    A.planes.depth = d->depth; A.planes.point = d->point; A.planes.normal = d->normal; A.planes.uvw = d->uvw;
+    A.planes.albedo = d->albedo; A.planes.prim = d->prim; A.planes.line_no = d->line_no; A.planes.material = d->material;
+    if (d->prim != nullptr && s->d_tri_id == nullptr) {  // first use (synchronous, once per scene)
+      MT_TRY(s->d_tri_id.ensure(s->tri_id_host.size() * sizeof(int32_t)));
+      HIP_TRY(hipMemcpy(s->d_tri_id, s->tri_id_host.data(), s->tri_id_host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
   }
   MT_TRY(s->d_gb_work.ensure(64));
-  A.tri_id = s->d_tri_id;
+  A.planes.tri_id = s->d_tri_id;
   A.counters = s->d_counters;
   A.work_counter = s->d_gb_work;
   MT_TRY(ensure_deep(s, (size_t)s->grid_blocks * s->waves_per_block));
@@ -1925,11 +1941,92 @@ int launch_gbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_
     s->dev_uploaded_valid = true;
   }
   HIP_TRY(hipMemsetAsync(s->d_gb_work, 0, sizeof(unsigned), stream));
-  const unsigned grid = (unsigned)std::min<unsigned long long>((unsigned long long)s->grid_blocks,
-                                                               (items + s->waves_per_block - 1) / s->waves_per_block);
+  *grid = (unsigned)std::min<unsigned long long>((unsigned long long)s->grid_blocks,
+                                                 (items + s->waves_per_block - 1) / s->waves_per_block);
+  return MT_OK;
+}
+}  // extern "C++"
+
+// gbuffer_kernel over the chunk, planes = device pointers
+int launch_gbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                   const mt_gbuffer &d, hipStream_t stream) {
+  GBufferArgs A{};
+  unsigned grid = 0;
+  MT_TRY(prepare_block_launch(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, &d, A, &grid, stream));
   hipLaunchKernelGGL(kernels_of(s->deep).gbuffer[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
                      s->lds_bytes, stream, s->dev, A);
   HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+// The host calls' way back: planes in device buffers reach the caller through the page-locked staging buffer in
+// pieces of at most 4 MB, every piece's memcpy under the next piece's DMA (finish_host_chunk's path).  The counters
+// travel first: no planes of a failed launch.  h_stage must hold staged_bytes(planes); ends with the stream idle.
+struct PlaneCopy { void *host; const void *dev; size_t bytes; };
+
+size_t staged_bytes(const std::vector<PlaneCopy> &planes) {
+  size_t total = 0;
+  for (const PlaneCopy &p : planes) total += (p.bytes + 4095) & ~(size_t)4095;
+  return total;
+}
+
+int planes_to_host(mt_scene *s, const std::vector<PlaneCopy> &planes, hipStream_t stream) {
+  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  struct Piece { uint8_t *dst; size_t off, bytes; };
+  std::vector<Piece> pieces;
+  constexpr size_t kPiece = 4u << 20;
+  size_t at = 0;
+  for (const PlaneCopy &p : planes) {
+    for (size_t o = 0; o < p.bytes; o += kPiece) {
+      const size_t n = std::min(kPiece, p.bytes - o);
+      HIP_TRY(hipMemcpyAsync(s->h_stage + at + o, (const uint8_t *)p.dev + o, n, hipMemcpyDeviceToHost, stream));
+      while (s->ev_gb.size() <= pieces.size()) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        s->ev_gb.push_back(e);
+      }
+      HIP_TRY(hipEventRecord(s->ev_gb[pieces.size()], stream));
+      pieces.push_back({(uint8_t *)p.host + o, at + o, n});
+    }
+    at += (p.bytes + 4095) & ~(size_t)4095;
+  }
+  for (size_t k = 0; k < pieces.size(); k++) {
+    HIP_TRY(hipEventSynchronize(s->ev_gb[k]));
+    if (k == 0 && check_status(s->h_counters) != MT_OK) {
+      (void)hipStreamSynchronize(stream);
+      return check_status(s->h_counters);
+    }
+    memcpy(pieces[k].dst, s->h_stage + pieces[k].off, pieces[k].bytes);
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  return check_status(s->h_counters);
+}
+
+// Scene-owned device buffers for the planes of `host` that are set (the host calls): the device-side mt_gbuffer in
+// *d, and one PlaneCopy per plane appended to *copies.
+int scene_planes(mt_scene *s, const mt_gbuffer &host_gb, size_t npx, mt_gbuffer *d, std::vector<PlaneCopy> *copies) {
+  void *host[kGbPlanes], *dev[kGbPlanes] = {};
+  gb_planes(host_gb, host);
+  for (int i = 0; i < kGbPlanes; i++) {
+    if (!host[i]) continue;
+    if (i < 5) { MT_TRY(s->d_gb_f64[i].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_f64[i].p; }
+    else { MT_TRY(s->d_gb_i32[i - 5].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_i32[i - 5].p; }
+    copies->push_back({host[i], dev[i], npx * kGbPixelBytes[i]});
+  }
+  *d = mt_gbuffer{(double *)dev[0], (double *)dev[1], (double *)dev[2], (double *)dev[3], (double *)dev[4],
+                  (int32_t *)dev[5], (int32_t *)dev[6], (int32_t *)dev[7]};
+  return MT_OK;
+}
+
+// kernel_ms between the scene's two events, total_ms since w0, the counters the launch left in h_counters
+int fill_call_stats(mt_scene *s, mt_stats *stats, std::chrono::steady_clock::time_point w0) {
+  memset(stats, 0, sizeof *stats);
+  fill_stats(s->h_counters, stats);
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  stats->kernel_ms = ms;
+  stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   return MT_OK;
 }
 
@@ -1942,8 +2039,7 @@ int mt_render_gbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, 
   return launch_gbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, *d_out, (hipStream_t)stream);
 }
 
-// The host call: the requested planes in buffers the scene owns, then to the caller through the page-locked staging
-// buffer in pieces, every piece's memcpy under the next piece's DMA (finish_host_chunk's path).
+// The host call: the requested planes in buffers the scene owns, then to the caller (planes_to_host).
 int mt_render_gbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
                       int chunk_w, int chunk_h, const mt_gbuffer *out, mt_stats *stats) {
   MT_TRY(check_gbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, out));
@@ -1951,19 +2047,11 @@ int mt_render_gbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int ima
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
   hipStream_t stream = nullptr;
-  void *host[kGbPlanes], *dev[kGbPlanes] = {};
-  gb_planes(*out, host);
-  size_t total = 0;
-  for (int i = 0; i < kGbPlanes; i++) {
-    if (!host[i]) continue;
-    if (i < 5) { MT_TRY(s->d_gb_f64[i].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_f64[i].p; }
-    else { MT_TRY(s->d_gb_i32[i - 5].ensure(npx * kGbPixelBytes[i])); dev[i] = s->d_gb_i32[i - 5].p; }
-    total += (npx * kGbPixelBytes[i] + 4095) & ~(size_t)4095;
-  }
+  std::vector<PlaneCopy> copies;
+  mt_gbuffer d{};
+  MT_TRY(scene_planes(s, *out, npx, &d, &copies));
   MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
-  MT_TRY(s->h_stage.ensure(total));
-  const mt_gbuffer d{(double *)dev[0], (double *)dev[1], (double *)dev[2], (double *)dev[3], (double *)dev[4],
-                     (int32_t *)dev[5], (int32_t *)dev[6], (int32_t *)dev[7]};
+  MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
   HIP_TRY(hipEventRecord(s->ev0, stream));
   const bool counters_were = s->stats_enabled;
@@ -1972,42 +2060,200 @@ int mt_render_gbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int ima
   s->stats_enabled = counters_were;
   if (rc != MT_OK) return rc;
   HIP_TRY(hipEventRecord(s->ev1, stream));
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  MT_TRY(planes_to_host(s, copies, stream));
+  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
+  return MT_OK;
+}
+
+// ---- the direct-light buffer and the relight pass (mt_lightbuffer.h).  Like the G-buffer calls, nothing here reads
+// or writes what decide_launch looks at. ----
+namespace {
+
+bool any_gb_plane(const mt_gbuffer *g) {
+  if (!g) return false;
+  void *p[kGbPlanes];
+  gb_planes(*g, p);
+  for (void *q : p) {
+    if (q != nullptr) return true;
+  }
+  return false;
+}
+
+// Checked before any device call, in the order of the header: lb / gb pointers, image and chunk, scene, sensor, lights.
+int check_lightbuffer_args(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                           int chunk_w, int chunk_h, const mt_gbuffer *gb, const mt_lightbuffer *lb) {
+  if (!lb) return fail(MT_ERR_ARG, "the mt_lightbuffer is NULL");
+  if (!lb->power && !lb->in_shadow) return fail(MT_ERR_ARG, "no plane of the mt_lightbuffer is set");
+  if (image_w <= 0 || image_h <= 0 || image_w > 100000 || image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d out of range", image_w, image_h);
+  }
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  if (s->dev.n_lights == 0 && !any_gb_plane(gb)) {
+    return fail(MT_ERR_ARG, "no lights are set and no G-buffer plane is requested: nothing to render");
+  }
+  if (gb && gb->prim != nullptr && !s->have_tri_id) {
+    return fail(MT_ERR_UNSUPPORTED, "the scene was created without mt_scene_desc::tri_id: no prim plane");
+  }
+  return MT_OK;
+}
+
+// lightbuffer_kernel over the chunk, planes = device pointers
+int launch_lightbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                       const mt_gbuffer *d_gb, const mt_lightbuffer &d_lb, hipStream_t stream) {
+  LightBufferArgs A{};
+  unsigned grid = 0;
+  MT_TRY(prepare_block_launch(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d_gb, A, &grid, stream));
+  A.power = d_lb.power;
+  A.in_shadow = d_lb.in_shadow;
+  hipLaunchKernelGGL(kernels_of(s->deep).lightbuffer[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
+                     s->lds_bytes, stream, s->dev, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+int check_shade_args(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                     int chunk_w, int chunk_h, const mt_gbuffer *gb, const mt_lightbuffer *lb, const mt_light *lights,
+                     int n_lights, const void *rgb) {
+  if (!lb) return fail(MT_ERR_ARG, "the mt_lightbuffer is NULL");
+  if (!lb->power || !lb->in_shadow) return fail(MT_ERR_ARG, "the relight pass needs both planes of the mt_lightbuffer");
+  if (!gb) return fail(MT_ERR_ARG, "the mt_gbuffer is NULL");
+  if (!gb->point || !gb->normal || !gb->albedo || !gb->material) {
+    return fail(MT_ERR_ARG, "the relight pass needs the point, normal, albedo and material planes of the mt_gbuffer");
+  }
+  if (!rgb) return fail(MT_ERR_ARG, "the output bitmap is NULL");
+  if (image_w <= 0 || image_h <= 0 || image_w > 100000 || image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d out of range", image_w, image_h);
+  }
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  if (n_lights < 0 || (n_lights > 0 && !lights)) return fail(MT_ERR_ARG, "bad lights argument");
+  return MT_OK;
+}
+
+// shade_direct_kernel over the chunk, everything but `lights` = device pointers
+int launch_shade_direct(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                        const mt_gbuffer &d_gb, const mt_lightbuffer &d_lb, const mt_light *lights, int n_lights,
+                        uint8_t *d_rgb, hipStream_t stream) {
+  ShadeDirectArgs A{};
+  A.sensor = *sensor;
+  A.chunk_x = chunk_x; A.chunk_y = chunk_y; A.chunk_w = chunk_w; A.chunk_h = chunk_h;
+  A.point = d_gb.point; A.normal = d_gb.normal; A.albedo = d_gb.albedo; A.material = d_gb.material;
+  A.power = d_lb.power; A.in_shadow = d_lb.in_shadow;
+  A.mtls = s->dev.mtls;
+  A.n_materials = s->n_materials;
+  A.n_lights = n_lights;
+  A.out_rgb = d_rgb;
+  const bool in_args = n_lights <= kShadeArgLights;
+  if (in_args) {
+    for (int i = 0; i < n_lights; i++) A.lights[i] = lights[i];
+  } else {
+    MT_TRY(s->d_shade_lights.ensure((size_t)n_lights * sizeof(mt_light)));
+    HIP_TRY(hipMemcpyAsync(s->d_shade_lights, lights, (size_t)n_lights * sizeof(mt_light), hipMemcpyHostToDevice, stream));
+    A.d_lights = s->d_shade_lights;
+  }
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  const size_t blocks = (npx + 255) / 256;
+  if (blocks > 0x7fffffffull) return fail(MT_ERR_ARG, "too many pixels (%zu)", npx);
+  hipLaunchKernelGGL(in_args ? shade_direct_kernel<true> : shade_direct_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
+                     stream, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_render_lightbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                                 int chunk_w, int chunk_h, const mt_gbuffer *d_gb, const mt_lightbuffer *d_lb,
+                                 void *stream) {
+  MT_TRY(check_lightbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, d_gb, d_lb));
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_lightbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d_gb, *d_lb, (hipStream_t)stream);
+}
+
+int mt_render_lightbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                          int chunk_w, int chunk_h, const mt_gbuffer *gb, const mt_lightbuffer *lb, mt_stats *stats) {
+  MT_TRY(check_lightbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, gb, lb));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  const size_t n_l = (size_t)s->dev.n_lights;
+  hipStream_t stream = nullptr;
+  std::vector<PlaneCopy> copies;
+  mt_gbuffer d{};
+  if (gb) MT_TRY(scene_planes(s, *gb, npx, &d, &copies));
+  mt_lightbuffer dl{};
+  if (lb->power && n_l > 0) {
+    MT_TRY(s->d_lb_power.ensure(n_l * npx * 24));
+    dl.power = s->d_lb_power;
+    copies.push_back({lb->power, dl.power, n_l * npx * 24});
+  }
+  if (lb->in_shadow && n_l > 0) {
+    MT_TRY(s->d_lb_shadow.ensure(n_l * npx));
+    dl.in_shadow = s->d_lb_shadow;
+    copies.push_back({lb->in_shadow, dl.in_shadow, n_l * npx});
+  }
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  // pieces of at most 4 MB: (caller's address, staging offset, bytes), queued in plane order
-  struct Piece { uint8_t *dst; size_t off, bytes; };
-  std::vector<Piece> pieces;
-  constexpr size_t kPiece = 4u << 20;
-  size_t at = 0;
-  for (int i = 0; i < kGbPlanes; i++) {
-    if (!host[i]) continue;
-    const size_t bytes = npx * kGbPixelBytes[i];
-    for (size_t o = 0; o < bytes; o += kPiece) {
-      const size_t n = std::min(kPiece, bytes - o);
-      HIP_TRY(hipMemcpyAsync(s->h_stage + at + o, (const uint8_t *)dev[i] + o, n, hipMemcpyDeviceToHost, stream));
-      while (s->ev_gb.size() <= pieces.size()) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s->ev_gb.push_back(e);
-      }
-      HIP_TRY(hipEventRecord(s->ev_gb[pieces.size()], stream));
-      pieces.push_back({(uint8_t *)host[i] + o, at + o, n});
-    }
-    at += (bytes + 4095) & ~(size_t)4095;
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = launch_lightbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, gb ? &d : nullptr, dl, stream);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  MT_TRY(planes_to_host(s, copies, stream));
+  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
+  return MT_OK;
+}
+
+int mt_shade_direct_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                           int chunk_w, int chunk_h, const mt_gbuffer *d_gb, const mt_lightbuffer *d_lb,
+                           const mt_light *lights, int n_lights, void *d_rgb, void *stream) {
+  MT_TRY(check_shade_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, d_gb, d_lb, lights, n_lights,
+                          d_rgb));
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_shade_direct(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, *d_gb, *d_lb, lights, n_lights,
+                             (uint8_t *)d_rgb, (hipStream_t)stream);
+}
+
+// The host form: the six planes go up into buffers the scene owns, the bitmap comes back.
+int mt_shade_direct(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                    int chunk_w, int chunk_h, const mt_gbuffer *gb, const mt_lightbuffer *lb, const mt_light *lights,
+                    int n_lights, uint8_t *out_rgb, mt_stats *stats) {
+  MT_TRY(check_shade_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, gb, lb, lights, n_lights,
+                          out_rgb));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  const size_t n_l = (size_t)n_lights;
+  hipStream_t stream = nullptr;
+  MT_TRY(s->d_gb_f64[1].ensure(npx * 24));
+  MT_TRY(s->d_gb_f64[2].ensure(npx * 24));
+  MT_TRY(s->d_gb_f64[4].ensure(npx * 24));
+  MT_TRY(s->d_gb_i32[2].ensure(npx * 4));
+  MT_TRY(s->d_lb_power.ensure(n_l * npx * 24));
+  MT_TRY(s->d_lb_shadow.ensure(n_l * npx));
+  MT_TRY(s->d_rgb.ensure(npx * 3));
+  mt_gbuffer d{};
+  d.point = s->d_gb_f64[1]; d.normal = s->d_gb_f64[2]; d.albedo = s->d_gb_f64[4]; d.material = s->d_gb_i32[2];
+  const mt_lightbuffer dl{s->d_lb_power, s->d_lb_shadow};
+  HIP_TRY(hipMemcpyAsync(d.point, gb->point, npx * 24, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d.normal, gb->normal, npx * 24, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d.albedo, gb->albedo, npx * 24, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d.material, gb->material, npx * 4, hipMemcpyHostToDevice, stream));
+  if (n_l > 0) {
+    HIP_TRY(hipMemcpyAsync(dl.power, lb->power, n_l * npx * 24, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(dl.in_shadow, lb->in_shadow, n_l * npx, hipMemcpyHostToDevice, stream));
   }
-  for (size_t k = 0; k < pieces.size(); k++) {
-    HIP_TRY(hipEventSynchronize(s->ev_gb[k]));
-    if (k == 0 && check_status(s->h_counters) != MT_OK) {  // (the counters came first: no planes of a failed launch)
-      (void)hipStreamSynchronize(stream);
-      return check_status(s->h_counters);
-    }
-    memcpy(pieces[k].dst, s->h_stage + pieces[k].off, pieces[k].bytes);
-  }
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  MT_TRY(launch_shade_direct(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d, dl, lights, n_lights, s->d_rgb, stream));
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  HIP_TRY(hipMemcpyAsync(out_rgb, s->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  MT_TRY(check_status(s->h_counters));
   if (stats) {
     memset(stats, 0, sizeof *stats);
-    fill_stats(s->h_counters, stats);
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     stats->kernel_ms = ms;

@@ -28,14 +28,19 @@
 
 namespace mt {
 
+// The planes, all optional; `tri_id` (stream index -> AddPrimitive index) is read for `prim` only.
+struct GBufferPlanes {
+  double *depth, *point, *normal, *uvw, *albedo;  // 1, 3, 3, 3, 3 doubles per pixel
+  int32_t *prim, *line_no, *material;
+  const int32_t *tri_id;
+};
+
 struct GBufferArgs {
   mt_sensor sensor;
   int32_t chunk_x, chunk_y, chunk_w, chunk_h;  // in image coordinates; the planes are chunk-local row-major
   int32_t blocks_x;                            // 8x8 blocks per row of the chunk
   uint32_t n_items;                            // blocks of the chunk
-  double *depth, *point, *normal, *uvw, *albedo;  // 1, 3, 3, 3, 3 doubles per pixel
-  int32_t *prim, *line_no, *material;
-  const int32_t *tri_id;                       // stream index -> AddPrimitive index (read for `prim` only)
+  GBufferPlanes planes;
   unsigned long long *counters;                // ST_COUNT
   unsigned int *work_counter;                  // zero at launch
 };
@@ -45,6 +50,64 @@ __device__ __forceinline__ void store3(double *plane, size_t px, V3 v) {
   o[0] = v.x; o[1] = v.y; o[2] = v.z;
 }
 
+// What a pixel's primary trace found, as far as a caller of write_gbuffer_planes asked for it
+struct PrimaryHit {
+  V3 point;  // origin + direction t (NaN on a miss, or when neither a plane nor the caller needs it)
+  int mtl;   // the triangle's material, -1 = none / miss / not needed
+};
+
+// One pixel's planes from its primary trace `to` (ray origin + rd t): the part of the G-buffer after the trace, shared
+// by gbuffer_kernel and lightbuffer_kernel (mt_lightbuffer.h).  What no requested plane needs is not computed;
+// need_hit: the caller wants point and material whatever the planes say.
+template <bool STATS>
+__device__ __forceinline__ PrimaryHit write_gbuffer_planes(const DevScene &S, const GBufferPlanes &A, size_t px, V3 origin,
+                                                           V3 rd, const TraceOut &to, LaneStats &st, bool need_hit) {
+  const MT_CONST mt_material *mtls = as_const(S.mtls);
+  // which intermediate values does some requested plane need?  (wave-uniform)
+  const bool want_albedo = A.albedo != nullptr;
+  const bool want_mtl = A.material != nullptr || want_albedo || need_hit;
+  const bool want_uvw = A.uvw != nullptr;
+  const bool want_bary = A.normal != nullptr || want_uvw || want_albedo;  // (albedo: textured materials only, per lane)
+  const V3 nan3 = v3(__builtin_nan(""), __builtin_nan(""), __builtin_nan(""));
+  const int prim = to.prim;
+  const bool hit = prim >= 0;
+  if (STATS) {
+    st.v[ST_RAYS_PRIMARY]++;
+    if (hit) st.v[ST_SHADED_HITS]++;
+  }
+  if (A.depth) A.depth[px] = hit ? to.t : __builtin_nan("");
+  if (A.line_no) A.line_no[px] = hit ? S.tri_line[prim] : -1;
+  if (A.prim) A.prim[px] = hit ? A.tri_id[prim] : -1;
+  V3 Pt = nan3, Nn = nan3, uvw = nan3, surf = nan3;
+  int mtl = -1;
+  if (hit) {
+    if (A.point != nullptr || want_bary || need_hit) Pt = origin + rd * to.t;  // primitive_triangle.cc:141
+    if (want_mtl) mtl = S.tri_mtl[prim];
+    const bool textured = want_albedo && mtl >= 0 && mtls[mtl].tex >= 0;
+    if (A.normal != nullptr || want_uvw || textured) {
+      const Bary w = barycentric(S.tri_vertex + (size_t)prim * 9, Pt);
+      if (A.normal) Nn = interpolate(S.tri_normal + (size_t)prim * 9, w);  // GetNormal; no flip
+      if (want_uvw || textured) uvw = interpolate(S.tri_uvw + (size_t)prim * 9, w);
+      if (STATS) st.v[ST_BYTES_VECTOR] += 72u + (A.normal ? 72u : 0u) + ((want_uvw || textured) ? 72u : 0u);
+    }
+    if (want_albedo && mtl >= 0) {  // mythtracer.cc:58-64
+      const MT_CONST mt_material *m = mtls + mtl;
+      surf = v3(m->ambient[0], m->ambient[1], m->ambient[2]);
+      if (textured) surf = surf * texture_color_at(S.texs[m->tex], uvw.x, uvw.y);
+    }
+  }
+  if (A.point) store3(A.point, px, Pt);
+  if (A.normal) store3(A.normal, px, Nn);
+  if (A.uvw) store3(A.uvw, px, uvw);
+  if (A.albedo) store3(A.albedo, px, surf);
+  if (A.material) A.material[px] = mtl;
+  if (STATS) {
+    st.v[ST_BYTES_VECTOR] += (A.depth ? 8u : 0u) + (A.point ? 24u : 0u) + (A.normal ? 24u : 0u) + (A.uvw ? 24u : 0u) +
+                             (A.albedo ? 24u : 0u) + (A.prim ? 4u : 0u) + (A.line_no ? 4u : 0u) + (A.material ? 4u : 0u);
+  }
+  return PrimaryHit{Pt, mtl};
+}
+
 template <bool STATS, int DEEP>
 __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void gbuffer_kernel(DevScene S, GBufferArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -52,19 +115,12 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void gbuffer_kernel(DevScen
   const int wave_in_block = threadIdx.x >> 6;
   WaveStack stk;
   stk.bind(smem, wave_in_block, S.tree_depth, S.pack_shift, DEEP != 0);
-  const MT_CONST mt_material *mtls = as_const(S.mtls);
   LaneStats st;
   st.clear();
   const V3 cam_origin = v3_load(A.sensor.origin);
   const V3 s_start = v3_load(A.sensor.start_point);
   const V3 s_ds = v3_load(A.sensor.delta_scanline);
   const V3 s_dp = v3_load(A.sensor.delta_pixel);
-  // which intermediate values does some requested plane need?  (wave-uniform)
-  const bool want_albedo = A.albedo != nullptr;
-  const bool want_mtl = A.material != nullptr || want_albedo;
-  const bool want_uvw = A.uvw != nullptr;
-  const bool want_bary = A.normal != nullptr || want_uvw || want_albedo;  // (albedo: textured materials only, per lane)
-  const V3 nan3 = v3(__builtin_nan(""), __builtin_nan(""), __builtin_nan(""));
   for (;;) {
     const unsigned item = fetch_work(A.work_counter, lane);
     if (item >= A.n_items) break;
@@ -84,44 +140,7 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void gbuffer_kernel(DevScen
       if (lane == 0) atomicMax(A.counters + ST_STATUS, (unsigned long long)to.status);
       break;
     }
-    if (want) {
-      const int prim = to.prim;
-      const bool hit = prim >= 0;
-      if (STATS) {
-        st.v[ST_RAYS_PRIMARY]++;
-        if (hit) st.v[ST_SHADED_HITS]++;
-      }
-      if (A.depth) A.depth[px] = hit ? to.t : __builtin_nan("");
-      if (A.line_no) A.line_no[px] = hit ? S.tri_line[prim] : -1;
-      if (A.prim) A.prim[px] = hit ? A.tri_id[prim] : -1;
-      V3 Pt = nan3, Nn = nan3, uvw = nan3, surf = nan3;
-      int mtl = -1;
-      if (hit) {
-        if (A.point != nullptr || want_bary) Pt = cam_origin + rd * to.t;  // primitive_triangle.cc:141
-        if (want_mtl) mtl = S.tri_mtl[prim];
-        const bool textured = want_albedo && mtl >= 0 && mtls[mtl].tex >= 0;
-        if (A.normal != nullptr || want_uvw || textured) {
-          const Bary w = barycentric(S.tri_vertex + (size_t)prim * 9, Pt);
-          if (A.normal) Nn = interpolate(S.tri_normal + (size_t)prim * 9, w);  // GetNormal; no flip
-          if (want_uvw || textured) uvw = interpolate(S.tri_uvw + (size_t)prim * 9, w);
-          if (STATS) st.v[ST_BYTES_VECTOR] += 72u + (A.normal ? 72u : 0u) + ((want_uvw || textured) ? 72u : 0u);
-        }
-        if (want_albedo && mtl >= 0) {  // mythtracer.cc:58-64
-          const MT_CONST mt_material *m = mtls + mtl;
-          surf = v3(m->ambient[0], m->ambient[1], m->ambient[2]);
-          if (textured) surf = surf * texture_color_at(S.texs[m->tex], uvw.x, uvw.y);
-        }
-      }
-      if (A.point) store3(A.point, px, Pt);
-      if (A.normal) store3(A.normal, px, Nn);
-      if (A.uvw) store3(A.uvw, px, uvw);
-      if (A.albedo) store3(A.albedo, px, surf);
-      if (A.material) A.material[px] = mtl;
-      if (STATS) {
-        st.v[ST_BYTES_VECTOR] += (A.depth ? 8u : 0u) + (A.point ? 24u : 0u) + (A.normal ? 24u : 0u) + (A.uvw ? 24u : 0u) +
-                                 (A.albedo ? 24u : 0u) + (A.prim ? 4u : 0u) + (A.line_no ? 4u : 0u) + (A.material ? 4u : 0u);
-      }
-    }
+    if (want) (void)write_gbuffer_planes<STATS>(S, A.planes, px, cam_origin, rd, to, st, false);
     flush_item_stats<STATS>(st, A.counters, lane);
   }
 }

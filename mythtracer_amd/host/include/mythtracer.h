@@ -69,6 +69,20 @@ struct GBuffer {
   std::vector<int32_t> prim, line_no, material;
 };
 
+// The direct-light buffer of a frame or chunk (extension; mt_render_lightbuffer in mythtracer_hip.h): per light (in the
+// order of Scene::lights) and pixel, what the shadow loop of TraceRayWorker leaves behind -- light_power before it is
+// raised to the light's ambient, three doubles, and in_shadow, one byte: 0 lit, 1 in shadow, 255 = no light loop ran for
+// the pixel (a miss or a hit without a material; power is NaN there).  The plane of light l starts l * width * height
+// pixels into the vector.  With the point, normal, albedo and material planes of a GBuffer it holds everything
+// ShadeDirect needs.  It depends on the lights' positions, not on their colours.
+struct LightBuffer {
+  enum : unsigned { kPower = 1u, kInShadow = 2u, kAll = 3u };
+  unsigned channels = kAll;
+  int width = 0, height = 0, n_lights = 0;
+  std::vector<double> power;
+  std::vector<uint8_t> in_shadow;
+};
+
 class MythTracer {
  public:
   MythTracer();
@@ -107,6 +121,18 @@ class MythTracer {
   // multi-GPU G-buffer, and it is never silently rendered on the first device.  LastStats() describes the call.
   bool RayTraceGBuffer(int image_width, int image_height, Camera* camera, GBuffer* out);
   bool RayTraceGBuffer(WorkChunk* chunk, GBuffer* out);
+  // The direct-light buffer under GetScene()->lights, and in the same launch, from the same primary rays, the planes
+  // `gbuffer->channels` selects (gbuffer may be NULL: none).  Everything said about RayTraceGBuffer applies.
+  bool RayTraceLightBuffer(int image_width, int image_height, Camera* camera, GBuffer* gbuffer, LightBuffer* out);
+  bool RayTraceLightBuffer(WorkChunk* chunk, GBuffer* gbuffer, LightBuffer* out);
+  // The frame of the direct term -- what RayTrace gives with SetMaxRecursionLevel(0) -- from stored planes and
+  // GetScene()->lights, without tracing a ray (mt_shade_direct): for lights whose ambient, diffuse or specular were
+  // edited since the light buffer was made.  Their count and positions must be the light buffer's: a moved light needs
+  // a new RayTraceLightBuffer.  `gbuffer` must hold point, normal, albedo and material, `lightbuffer` both planes, all
+  // of this frame (or chunk->chunk_*) and camera.  output_bitmap is resized to width x height x 3.
+  bool ShadeDirect(int image_width, int image_height, Camera* camera, const GBuffer& gbuffer,
+                   const LightBuffer& lightbuffer, std::vector<uint8_t>* output_bitmap);
+  bool ShadeDirect(WorkChunk* chunk, const GBuffer& gbuffer, const LightBuffer& lightbuffer);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

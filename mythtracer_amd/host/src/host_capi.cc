@@ -31,6 +31,7 @@ struct Handle {
   std::vector<Material*> mtl_by_index;   // programmatic materials
   std::vector<Texture*> tex_by_index;
   std::string error;
+  std::string shim_error;  // a refusal of a shim function itself (the facade was not asked, or succeeded)
 };
 
 Camera MakeCamera(const double* c) { return Camera{{c[0], c[1], c[2]}, c[3], c[4], c[5], c[6]}; }
@@ -54,7 +55,8 @@ void mth_set_devices(void* p, const int* devices, int n) {
 
 const char* mth_last_error(void* p) {
   Handle* h = static_cast<Handle*>(p);
-  h->error = h->mt.LastError();
+  h->error = h->shim_error.empty() ? h->mt.LastError() : h->shim_error;
+  h->shim_error.clear();
   return h->error.c_str();
 }
 
@@ -317,6 +319,80 @@ int mth_render_gbuffer(void* p, const double* cam7, int iw, int ih, int cx, int 
   if (ms2) {
     ms2[0] = s.kernel_ms;
     ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
+int mth_num_lights(void* p) { return (int)static_cast<Handle*>(p)->mt.GetScene()->lights.size(); }
+
+// MythTracer::RayTraceLightBuffer(WorkChunk*, GBuffer*, LightBuffer*).  gb_channels / gb_planes[8] as in
+// mth_render_gbuffer (0 = no GBuffer); lb_channels = LightBuffer::k* bits, lb_planes[2] = power (doubles), in_shadow
+// (bytes), each NULL or sized for n_lights x the chunk; n_lights = what the caller sized them for.
+int mth_render_lightbuffer(void* p, const double* cam7, int iw, int ih, int cx, int cy, int cw, int ch,
+                           unsigned gb_channels, void* const* gb_planes, unsigned lb_channels, void* const* lb_planes,
+                           int n_lights, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  WorkChunk chunk{iw, ih, cx, cy, cw, ch, MakeCamera(cam7), {}, {}};
+  raytracer::GBuffer g;
+  g.channels = gb_channels;
+  raytracer::LightBuffer lb;
+  lb.channels = lb_channels;
+  if ((int)h->mt.GetScene()->lights.size() != n_lights) {  // (checked first: nothing may be copied into planes of another size)
+    h->shim_error = "the planes were sized for " + std::to_string(n_lights) + " lights, the scene has " +
+                    std::to_string(h->mt.GetScene()->lights.size());
+    return 0;
+  }
+  if (!h->mt.RayTraceLightBuffer(&chunk, gb_channels ? &g : nullptr, &lb)) return 0;
+  const std::vector<double>* f[5] = {&g.depth, &g.point, &g.normal, &g.uvw, &g.albedo};
+  const std::vector<int32_t>* i32[3] = {&g.prim, &g.line_no, &g.material};
+  for (int k = 0; k < 5; k++) {
+    if (gb_planes[k] && !f[k]->empty()) memcpy(gb_planes[k], f[k]->data(), f[k]->size() * 8);
+  }
+  for (int k = 0; k < 3; k++) {
+    if (gb_planes[5 + k] && !i32[k]->empty()) memcpy(gb_planes[5 + k], i32[k]->data(), i32[k]->size() * 4);
+  }
+  if (lb_planes[0] && !lb.power.empty()) memcpy(lb_planes[0], lb.power.data(), lb.power.size() * 8);
+  if (lb_planes[1] && !lb.in_shadow.empty()) memcpy(lb_planes[1], lb.in_shadow.data(), lb.in_shadow.size());
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
+// MythTracer::ShadeDirect(WorkChunk*, GBuffer, LightBuffer) under the facade's lights.  gb_planes[4] = point, normal,
+// albedo (doubles), material (int32) of the chunk; lb_planes[2] = power, in_shadow for n_lights lights.
+int mth_shade_direct(void* p, const double* cam7, int iw, int ih, int cx, int cy, int cw, int ch,
+                     void* const* gb_planes, int n_lights, void* const* lb_planes, uint8_t* rgb, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  WorkChunk chunk{iw, ih, cx, cy, cw, ch, MakeCamera(cam7), {}, {}};
+  const size_t npx = (size_t)(cw > 0 ? cw : 0) * (size_t)(ch > 0 ? ch : 0);
+  const size_t n_l = (size_t)(n_lights > 0 ? n_lights : 0);
+  raytracer::GBuffer g;
+  g.width = cw;
+  g.height = ch;
+  const double* f[3] = {(const double*)gb_planes[0], (const double*)gb_planes[1], (const double*)gb_planes[2]};
+  g.point.assign(f[0], f[0] + npx * 3);
+  g.normal.assign(f[1], f[1] + npx * 3);
+  g.albedo.assign(f[2], f[2] + npx * 3);
+  g.material.assign((const int32_t*)gb_planes[3], (const int32_t*)gb_planes[3] + npx);
+  raytracer::LightBuffer lb;
+  lb.width = cw;
+  lb.height = ch;
+  lb.n_lights = n_lights;
+  lb.power.assign((const double*)lb_planes[0], (const double*)lb_planes[0] + n_l * npx * 3);
+  lb.in_shadow.assign((const uint8_t*)lb_planes[1], (const uint8_t*)lb_planes[1] + n_l * npx);
+  if (!h->mt.ShadeDirect(&chunk, g, lb)) return 0;
+  memcpy(rgb, chunk.output_bitmap.data(), npx * 3);
+  if (ms2) {
+    ms2[0] = h->mt.LastStats().kernel_ms;
+    ms2[1] = h->mt.LastStats().total_ms;
   }
   return 1;
 }

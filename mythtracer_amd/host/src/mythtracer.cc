@@ -421,6 +421,161 @@ bool MythTracer::RayTraceGBuffer(WorkChunk* chunk, GBuffer* out) {
   return true;
 }
 
+namespace {
+
+mt_sensor SensorOf(const WorkChunk& chunk) {
+  const Camera::Sensor sensor = chunk.camera.GetSensor(chunk.image_width, chunk.image_height);
+  mt_sensor ms;
+  memcpy(ms.origin, chunk.camera.origin.v, 24);
+  memcpy(ms.start_point, sensor.StartPoint().v, 24);
+  memcpy(ms.delta_scanline, sensor.DeltaScanline().v, 24);
+  memcpy(ms.delta_pixel, sensor.DeltaPixel().v, 24);
+  return ms;
+}
+
+}  // namespace
+
+bool MythTracer::RayTraceLightBuffer(int image_width, int image_height, Camera* camera, GBuffer* gbuffer,
+                                     LightBuffer* out) {
+  WorkChunk chunk{image_width, image_height, 0, 0, image_width, image_height, *camera, {}, {}};
+  return RayTraceLightBuffer(&chunk, gbuffer, out);
+}
+
+bool MythTracer::RayTraceLightBuffer(WorkChunk* chunk, GBuffer* gbuffer, LightBuffer* out) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device, as in RayTraceGBuffer)
+  if (out == nullptr) return refuse("LightBuffer is NULL");
+  if (devices_.size() > 1) return refuse("the light buffer is not supported with several devices (SetDevices)");
+  if ((out->channels & LightBuffer::kAll) == 0) return refuse("LightBuffer::channels selects no plane");
+  if (chunk->chunk_width <= 0 || chunk->chunk_height <= 0) return refuse("empty chunk");
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("light buffer failed: ") + mt_last_error());
+  }
+  const mt_sensor ms = SensorOf(*chunk);
+  const size_t npx = (size_t)chunk->chunk_width * (size_t)chunk->chunk_height;
+  const size_t n_l = scene.lights.size();
+  const unsigned c = gbuffer ? gbuffer->channels : 0u;
+  auto sized = [&](auto& v, unsigned bit, size_t per_px) -> decltype(v.data()) {
+    v.clear();
+    if (!(c & bit)) return nullptr;
+    v.resize(npx * per_px);
+    return v.data();
+  };
+  mt_gbuffer g{};
+  if (gbuffer) {
+    g.depth = sized(gbuffer->depth, GBuffer::kDepth, 1);
+    g.point = sized(gbuffer->point, GBuffer::kPoint, 3);
+    g.normal = sized(gbuffer->normal, GBuffer::kNormal, 3);
+    g.uvw = sized(gbuffer->uvw, GBuffer::kUvw, 3);
+    g.albedo = sized(gbuffer->albedo, GBuffer::kAlbedo, 3);
+    g.prim = sized(gbuffer->prim, GBuffer::kPrim, 1);
+    g.line_no = sized(gbuffer->line_no, GBuffer::kLineNo, 1);
+    g.material = sized(gbuffer->material, GBuffer::kMaterial, 1);
+    gbuffer->width = chunk->chunk_width;
+    gbuffer->height = chunk->chunk_height;
+  }
+  // (zero lights: the planes are empty and nothing is written, but a pointer must still say "wanted")
+  double no_power = 0;
+  uint8_t no_shadow = 0;
+  out->power.clear();
+  out->in_shadow.clear();
+  mt_lightbuffer lb{};
+  if (out->channels & LightBuffer::kPower) {
+    out->power.resize(n_l * npx * 3);
+    lb.power = n_l ? out->power.data() : &no_power;
+  }
+  if (out->channels & LightBuffer::kInShadow) {
+    out->in_shadow.resize(n_l * npx);
+    lb.in_shadow = n_l ? out->in_shadow.data() : &no_shadow;
+  }
+  out->width = chunk->chunk_width;
+  out->height = chunk->chunk_height;
+  out->n_lights = (int)n_l;
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_render_lightbuffer(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x, chunk->chunk_y,
+                            chunk->chunk_width, chunk->chunk_height, gbuffer ? &g : nullptr, &lb, &st) != MT_OK) {
+    return refuse(std::string("light buffer failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_primary = st.rays_primary;
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.shaded_hits = st.shaded_hits;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
+bool MythTracer::ShadeDirect(int image_width, int image_height, Camera* camera, const GBuffer& gbuffer,
+                             const LightBuffer& lightbuffer, std::vector<uint8_t>* output_bitmap) {
+  WorkChunk chunk{image_width, image_height, 0, 0, image_width, image_height, *camera, {}, {}};
+  chunk.output_bitmap.swap(*output_bitmap);  // (reuses the caller's allocation)
+  const bool ok = ShadeDirect(&chunk, gbuffer, lightbuffer);
+  chunk.output_bitmap.swap(*output_bitmap);
+  return ok;
+}
+
+bool MythTracer::ShadeDirect(WorkChunk* chunk, const GBuffer& gbuffer, const LightBuffer& lightbuffer) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (devices_.size() > 1) return refuse("the relight pass is not supported with several devices (SetDevices)");
+  if (chunk->chunk_width <= 0 || chunk->chunk_height <= 0) return refuse("empty chunk");
+  const size_t npx = (size_t)chunk->chunk_width * (size_t)chunk->chunk_height;
+  const size_t n_l = scene.lights.size();
+  if (gbuffer.width != chunk->chunk_width || gbuffer.height != chunk->chunk_height ||
+      lightbuffer.width != chunk->chunk_width || lightbuffer.height != chunk->chunk_height) {
+    return refuse("the GBuffer and the LightBuffer must describe the chunk");
+  }
+  if (gbuffer.point.size() != npx * 3 || gbuffer.normal.size() != npx * 3 || gbuffer.albedo.size() != npx * 3 ||
+      gbuffer.material.size() != npx) {
+    return refuse("ShadeDirect needs the point, normal, albedo and material planes of the GBuffer");
+  }
+  if ((size_t)lightbuffer.n_lights != n_l) {
+    return refuse("the LightBuffer was made with another number of lights: a new RayTraceLightBuffer is needed");
+  }
+  if (lightbuffer.power.size() != n_l * npx * 3 || lightbuffer.in_shadow.size() != n_l * npx) {
+    return refuse("ShadeDirect needs both planes of the LightBuffer");
+  }
+  if (!Prepare()) return false;
+  const mt_sensor ms = SensorOf(*chunk);
+  chunk->output_bitmap.resize(npx * 3);
+  mt_gbuffer g{};
+  g.point = const_cast<double*>(gbuffer.point.data());
+  g.normal = const_cast<double*>(gbuffer.normal.data());
+  g.albedo = const_cast<double*>(gbuffer.albedo.data());
+  g.material = const_cast<int32_t*>(gbuffer.material.data());
+  // (zero lights: empty planes, but the pointers must be set)
+  double no_power = 0;
+  uint8_t no_shadow = 0;
+  mt_lightbuffer lb{n_l ? const_cast<double*>(lightbuffer.power.data()) : &no_power,
+                    n_l ? const_cast<uint8_t*>(lightbuffer.in_shadow.data()) : &no_shadow};
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  if (mt_shade_direct(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x, chunk->chunk_y,
+                      chunk->chunk_width, chunk->chunk_height, &g, &lb,
+                      reinterpret_cast<const mt_light*>(scene.lights.data()), (int)n_l, chunk->output_bitmap.data(),
+                      &st) != MT_OK) {
+    return refuse(std::string("relight failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
 // ---- wire format of a chunk (mythtracer.cc:314-429): six little-endian u32
 // in, u32 byte count + RGB bytes out.
 
