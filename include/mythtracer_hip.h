@@ -337,8 +337,9 @@ int mt_render_gbuffer_device(mt_scene *scene, const mt_sensor *sensor, int image
  * of the light buffer, all of the same chunk of the same image for the same sensor.
  * `lights` (a HOST array in both forms; the scene's own lights are neither read nor changed) may differ from the lights
  * the light buffer was made with in ambient, diffuse and specular ONLY: the count and every position must be the same.
- * Neither is checked -- the calls are stateless, the planes carry no record of their lights -- and a MOVED light needs a
- * new light buffer.  A value of the material plane outside the scene's materials (planes of another scene) is shaded as
+ * Neither is checked -- the calls are stateless, the planes carry no record of their lights.  A MOVED light needs new
+ * planes: mt_update_lightbuffer (below) traces those of the moved lights again from the stored G-buffer and leaves the
+ * others alone.  A value of the material plane outside the scene's materials (planes of another scene) is shaded as
  * "no material".
  * CONTRACT: for unchanged positions the bitmap is byte-identical to mt_render_chunk(..., max_depth = 0, ...) after
  * mt_scene_set_lights(lights, n_lights).
@@ -370,6 +371,42 @@ int mt_shade_direct_device(mt_scene *scene, const mt_sensor *sensor, int image_w
                            int chunk_x, int chunk_y, int chunk_w, int chunk_h,
                            const mt_gbuffer *d_gb, const mt_lightbuffer *d_lb, const mt_light *lights,
                            int n_lights, void *d_rgb, void *stream);
+
+/* The light-buffer planes of the LISTED lights again, after those lights have MOVED: the shadow loop depends on the
+ * primary hit point, on whether the hit has a material and on the light's position only, and the first two are stored
+ * bit for bit in the G-buffer's `point` and `material` planes.  No sensor, no image geometry: nothing here depends on
+ * the camera once the point is stored, and no primary ray is traced.
+ *   gb   read, not written: `point` (3 doubles per pixel) and `material` (int32) of the chunk; other planes ignored.
+ *   lb   mt_render_lightbuffer's layout for the scene's CURRENT lights (mt_scene_set_lights):
+ *        [n_lights][chunk_h][chunk_w]; each pointer nullable, at least one set.
+ *   light_idx, n_idx   the lights to trace again (indices into the scene's lights, each at most once, any order): a
+ *        HOST array in both forms.
+ * For every listed light l and every pixel with point[0] not NaN and 0 <= material < the scene's material count, the
+ * shadow loop runs exactly as for mt_render_lightbuffer (the same operations in the same order) under the scene's light l, and
+ * power / in_shadow are stored in plane l.  Every other pixel gets NaN and 255 in plane l -- a material index outside
+ * the scene's materials included, as for mt_shade_direct.  Planes of unlisted lights are not written, not one byte; in
+ * the host form their host memory is not written (or read) either.
+ * CONTRACT: after mt_scene_set_lights(B), planes made under lights A -- same count, positions different at the listed
+ * indices only -- updated from the same chunk's point and material are bit-identical to mt_render_lightbuffer under B
+ * (power with NaN = NaN, in_shadow byte for byte).
+ *   mt_update_lightbuffer: host pointers; stats (nullable): rays_primary = shaded_hits = rays_secondary = 0,
+ *     rays_shadow = loop iterations of the listed lights, the traversal's counters, kernel_ms = the kernel by HIP
+ *     events, total_ms = wall time of the call.
+ *   mt_update_lightbuffer_device: device pointers in `d_gb` / `d_lb`; asynchronous on `stream`; counters as for
+ *     mt_render_chunk_device.  Up to 8 indices travel with the launch; a longer list is copied by the stream into a
+ *     buffer the scene owns and must stay unchanged until the stream has reached the call.  One call in flight per
+ *     scene, as for its siblings (they share the work counter and the statistics).
+ * One kernel next to the frame kernels (mt::lightbuffer_update_kernel; a work item is an 8x8 block of the chunk x one
+ * listed light); cost history, engine choice, forecasts and mt_scene_kernel_times are left alone.
+ * Argument checks come before any device call, in this order: `lb` (NULL, no plane), `gb` (NULL, point or material
+ * missing), chunk_w and chunk_h in 1 .. 100000, scene, the list (n_idx <= 0 or NULL), an index outside
+ * 0 .. n_lights - 1, an index listed twice. */
+int mt_update_lightbuffer(mt_scene *scene, int chunk_w, int chunk_h,
+                          const mt_gbuffer *gb, const int32_t *light_idx, int n_idx,
+                          const mt_lightbuffer *lb, mt_stats *stats);
+int mt_update_lightbuffer_device(mt_scene *scene, int chunk_w, int chunk_h,
+                                 const mt_gbuffer *d_gb, const int32_t *light_idx, int n_idx,
+                                 const mt_lightbuffer *d_lb, void *stream);
 
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into

@@ -28,6 +28,7 @@ HIP_SYMBOLS = [
     "mt_render_chunk_ss", "mt_render_chunk_ss_device", "mt_resolve_tiles_device",
     "mt_render_gbuffer", "mt_render_gbuffer_device",
     "mt_render_lightbuffer", "mt_render_lightbuffer_device", "mt_shade_direct", "mt_shade_direct_device",
+    "mt_update_lightbuffer", "mt_update_lightbuffer_device",
 ]
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
@@ -162,6 +163,44 @@ def _relight_planes(gbuffer, lightbuffer, cw, ch):
     return g, dict(power=power, in_shadow=shadow), n_l
 
 
+# what a light-buffer update reads of the G-buffer
+UPDATE_GBUFFER_PLANES = ("point", "material")
+
+
+def _update_planes(gbuffer, lightbuffer):
+    """The planes of a light-buffer update, checked: the two G-buffer planes as contiguous arrays, the light-buffer
+    planes present (at least one) AS THEY ARE -- they are updated in place, so they must be C-contiguous numpy arrays of
+    the plane's dtype.  Returns (g, lb, n_lights, cw, ch)."""
+    g = {}
+    for n in UPDATE_GBUFFER_PLANES:
+        if n not in gbuffer:
+            raise ValueError("the light-buffer update needs the G-buffer plane %r" % n)
+        dt, k = GBUFFER_PLANES[n]
+        a = np.asarray(gbuffer[n])
+        if a.dtype != dt:
+            raise ValueError("G-buffer plane %r has dtype %s, not %s" % (n, a.dtype, np.dtype(dt)))
+        g[n] = np.ascontiguousarray(a)
+    if g["material"].ndim != 2:
+        raise ValueError("G-buffer plane 'material' has shape %s, not (rows, columns)" % (g["material"].shape,))
+    ch, cw = g["material"].shape
+    if g["point"].shape != (ch, cw, 3):
+        raise ValueError("G-buffer plane 'point' has shape %s, not that of the %dx%d chunk" % (g["point"].shape, cw, ch))
+    lb = {n: lightbuffer[n] for n in LIGHTBUFFER_PLANES if n in lightbuffer}
+    if not lb:
+        raise ValueError("the light-buffer update needs a light-buffer plane (%s)" % ", ".join(LIGHTBUFFER_PLANES))
+    n_l = None
+    for n, a in lb.items():
+        dt, k = LIGHTBUFFER_PLANES[n]
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("light-buffer plane %r must be a writeable C-contiguous numpy array of dtype %s (it is "
+                             "updated in place)" % (n, np.dtype(dt)))
+        if n_l is None:
+            n_l = a.shape[0] if a.ndim else -1
+        if a.shape != (n_l, ch, cw) + ((k,) if k > 1 else ()):
+            raise ValueError("light-buffer plane %r of shape %s does not fit the %dx%d chunk" % (n, a.shape, cw, ch))
+    return g, lb, n_l, cw, ch
+
+
 DEBUG_PX_DTYPE = np.dtype([("line_no", "<i4"), ("reserved", "<i4"), ("point", "<f8", 3)])
 
 
@@ -228,6 +267,8 @@ class HipAbi:
         L.mt_render_lightbuffer_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp]
         L.mt_shade_direct.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp, ci, vp, vp]
         L.mt_shade_direct_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp, ci, vp, vp]
+        L.mt_update_lightbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp, ci, C.POINTER(mt_lightbuffer), vp]
+        L.mt_update_lightbuffer_device.argtypes = L.mt_update_lightbuffer.argtypes
 
     def last_error(self) -> str:
         return self.lib.mt_last_error().decode(errors="replace")
@@ -485,6 +526,37 @@ class HipAbi:
         self.check(self.lib.mt_shade_direct_device(h, C.byref(s), image_w, image_h, *chunk, C.byref(g), C.byref(lb),
                                                    _ptr(l), l.shape[0], d_rgb, stream))
 
+    def update_lightbuffer(self, h, gbuffer, lightbuffer, light_indices):
+        """mt_update_lightbuffer after set_lights(the moved lights): the planes of the lights in `light_indices` of
+        `lightbuffer` (dict with `power` and / or `in_shadow`, numpy arrays of the chunk for the scene's current number
+        of lights) traced again from the `point` and `material` planes of `gbuffer`.  The arrays are updated IN PLACE
+        -- the planes of the other lights are neither read nor written.  Returns dict(those arrays, stats)."""
+        g, lb, n_l, cw, ch = _update_planes(gbuffer, lightbuffer)
+        idx = _i32(light_indices).reshape(-1)
+        gs = mt_gbuffer(**{n: a.ctypes.data for n, a in g.items()})
+        ls = mt_lightbuffer(**{n: a.ctypes.data for n, a in lb.items()})
+        st = mt_stats()
+        self.check(self.lib.mt_update_lightbuffer(h, cw, ch, C.byref(gs), _ptr(idx), len(idx), C.byref(ls),
+                                                  C.addressof(st)))
+        out = dict(lb)
+        out["stats"] = st.as_dict()
+        return out
+
+    def update_lightbuffer_device(self, h, chunk_w, chunk_h, d_gb_planes, d_lb_planes, light_indices, stream=None):
+        """mt_update_lightbuffer_device: dicts plane name -> device pointer, `light_indices` a host list."""
+        for n in d_lb_planes:
+            if n not in LIGHTBUFFER_PLANES:
+                raise ValueError("unknown light-buffer plane %r" % (n,))
+        for n in d_gb_planes:
+            if n not in GBUFFER_PLANES:
+                raise ValueError("unknown G-buffer plane %r" % (n,))
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p  # noqa: E731
+        g = mt_gbuffer(**{n: val(p) for n, p in d_gb_planes.items()})
+        lb = mt_lightbuffer(**{n: val(p) for n, p in d_lb_planes.items()})
+        idx = _i32(light_indices).reshape(-1)
+        self.check(self.lib.mt_update_lightbuffer_device(h, chunk_w, chunk_h, C.byref(g), _ptr(idx), len(idx),
+                                                         C.byref(lb), stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -613,6 +685,7 @@ def host_lib():
     L.mth_render_gbuffer.argtypes = [vp, vp] + [ci] * 6 + [C.c_uint, vp, vp, vp]
     L.mth_render_lightbuffer.argtypes = [vp, vp] + [ci] * 6 + [C.c_uint, vp, C.c_uint, vp, ci, vp, vp]
     L.mth_shade_direct.argtypes = [vp, vp] + [ci] * 6 + [vp, ci, vp, vp, vp]
+    L.mth_update_lightbuffer.argtypes = [vp, ci, ci, vp, vp, ci, C.c_uint, vp, ci, vp, vp]
     L.mth_num_lights.argtypes = [vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
@@ -844,8 +917,8 @@ class MythTracer:
     def relight(self, cam, image_w, image_h, gbuffer, lightbuffer, lights=None, chunk=None):
         """MythTracer::ShadeDirect: the frame of the direct term (what render gives at max level 0) from stored planes,
         without tracing a ray.  `lights` (n x 12) replaces the facade's lights first, as set_lights does; None keeps
-        them.  They may differ from the lights the light buffer was made with in their colours only: a moved light
-        needs a new light buffer.  Returns dict(rgb, kernel_ms, total_ms)."""
+        them.  They may differ from the lights the light buffer was made with in their colours only: after a light has
+        moved, update_lightbuffer first.  Returns dict(rgb, kernel_ms, total_ms)."""
         cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
         if lights is not None:
             self.set_lights(lights)
@@ -859,6 +932,27 @@ class MythTracer:
                                        _ptr(rgb), _ptr(ms)):
             raise RuntimeError("ShadeDirect failed: " + self.last_error())
         return dict(rgb=rgb, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def update_lightbuffer(self, gbuffer, lightbuffer, light_indices):
+        """MythTracer::UpdateLightBuffer under the lights of set_lights (the moved ones among them): the planes of the
+        lights in `light_indices` of `lightbuffer` traced again from the `point` and `material` planes of `gbuffer`
+        (dicts as lightbuffer() returns them).  Returns a NEW dict with the updated light-buffer planes (the planes of
+        the other lights copied as they were) plus counters, kernel_ms, total_ms; the arguments are not changed."""
+        g, lb, n_l, cw, ch = _update_planes(gbuffer, {n: np.array(a) for n, a in lightbuffer.items()
+                                                      if n in LIGHTBUFFER_PLANES})
+        idx = _i32(light_indices).reshape(-1)
+        gptrs = (C.c_void_p * 2)(*[g[n].ctypes.data for n in UPDATE_GBUFFER_PLANES])
+        lnames = list(LIGHTBUFFER_PLANES)
+        lbits = sum(1 << lnames.index(n) for n in lb)
+        lptrs = (C.c_void_p * 2)(*[lb[n].ctypes.data if n in lb else None for n in lnames])
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        if not self.L.mth_update_lightbuffer(self.h, cw, ch, gptrs, _ptr(idx), len(idx), lbits, lptrs, n_l,
+                                             _ptr(st), _ptr(ms)):
+            raise RuntimeError("UpdateLightBuffer failed: " + self.last_error())
+        out = dict(lb)
+        out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+        return out
 
     def render_image(self, cam, image_w, image_h):
         """MythTracer::RayTrace(int, int, Camera*, vector<uint8_t>*)."""

@@ -237,6 +237,7 @@ struct mt_scene {
   Buf<double> d_lb_power;
   Buf<uint8_t> d_lb_shadow;
   Buf<mt_light> d_shade_lights;
+  Buf<int32_t> d_update_idx;  // mt_update_lightbuffer: a list of more than kUpdateArgLights light indices
   int n_materials = 0;  // of dev.mtls (shade_direct_kernel checks the caller's material plane against it)
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
@@ -301,13 +302,15 @@ struct LayoutKernels {
   void (*intersect)(DevScene, int, const double *, int *, int *, double *, double *, unsigned long long *);
   void (*gbuffer[2])(DevScene, GBufferArgs);
   void (*lightbuffer[2])(DevScene, LightBufferArgs);
+  void (*lightbuffer_update[2])(DevScene, LightUpdateArgs);
 };
 template <int D>
 LayoutKernels layout_kernels() {
   return {{render_kernel<false, D>, render_kernel<true, D>}, {primary_kernel<false, D>, primary_kernel<true, D>},
           {pool_kernel<false, D>, pool_kernel<true, D>}, {hybrid_kernel<false, D>, hybrid_kernel<true, D>},
           probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>},
-          {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>}};
+          {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>},
+          {lightbuffer_update_kernel<false, D>, lightbuffer_update_kernel<true, D>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -342,6 +345,9 @@ int configure_launch(mt_scene *s) {
         HIP_TRY(hipFuncSetAttribute((const void *)k.intersect, kLdsAttr, (int)bytes));
         for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)k.gbuffer[st], kLdsAttr, (int)bytes));
         for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)k.lightbuffer[st], kLdsAttr, (int)bytes));
+        for (int st = 0; st < 2; st++) {
+          HIP_TRY(hipFuncSetAttribute((const void *)k.lightbuffer_update[st], kLdsAttr, (int)bytes));
+        }
       }
       have = bytes;
     }
@@ -1909,9 +1915,24 @@ int check_gbuffer_args(const mt_scene *s, const mt_sensor *sensor, int image_w, 
   return MT_OK;
 }
 
+// What every kernel of persistent waves next to the frame kernels needs before its launch of `items` work items: the
+// work counter (zeroed by the stream), the DEEP areas, the scene description on the device.  Returns the grid in *grid.
+int prepare_persistent_launch(mt_scene *s, unsigned long long items, unsigned *grid, hipStream_t stream) {
+  MT_TRY(s->d_gb_work.ensure(64));
+  MT_TRY(ensure_deep(s, (size_t)s->grid_blocks * s->waves_per_block));
+  if (!s->dev_uploaded_valid || memcmp(&s->dev_uploaded, &s->dev, sizeof(DevScene)) != 0) {  // (as launch_kernels)
+    HIP_TRY(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, stream));
+    memcpy(&s->dev_uploaded, &s->dev, sizeof(DevScene));
+    s->dev_uploaded_valid = true;
+  }
+  HIP_TRY(hipMemsetAsync(s->d_gb_work, 0, sizeof(unsigned), stream));
+  *grid = (unsigned)std::min<unsigned long long>((unsigned long long)s->grid_blocks,
+                                                 (items + s->waves_per_block - 1) / s->waves_per_block);
+  return MT_OK;
+}
+
 // What gbuffer_kernel and lightbuffer_kernel share on the host: the chunk's blocks, the device-side planes (`d`
-// nullable: none), the work counter, the DEEP areas and the scene description of the launch.  Args = GBufferArgs or
-// LightBufferArgs.  Returns the grid in *grid.
+// nullable: none), and prepare_persistent_launch.  Args = GBufferArgs or LightBufferArgs.  Returns the grid in *grid.
 extern "C++" {  // (this file's functions sit inside one extern "C" block; a template needs C++ linkage)
 template <typename Args>
 int prepare_block_launch(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
@@ -1930,19 +1951,10 @@ int prepare_block_launch(mt_scene *s, const mt_sensor *sensor, int chunk_x, int 
       HIP_TRY(hipMemcpy(s->d_tri_id, s->tri_id_host.data(), s->tri_id_host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   }
-  MT_TRY(s->d_gb_work.ensure(64));
+  MT_TRY(prepare_persistent_launch(s, items, grid, stream));
   A.planes.tri_id = s->d_tri_id;
   A.counters = s->d_counters;
   A.work_counter = s->d_gb_work;
-  MT_TRY(ensure_deep(s, (size_t)s->grid_blocks * s->waves_per_block));
-  if (!s->dev_uploaded_valid || memcmp(&s->dev_uploaded, &s->dev, sizeof(DevScene)) != 0) {  // (as launch_kernels)
-    HIP_TRY(hipMemcpyAsync(s->d_dev, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, stream));
-    memcpy(&s->dev_uploaded, &s->dev, sizeof(DevScene));
-    s->dev_uploaded_valid = true;
-  }
-  HIP_TRY(hipMemsetAsync(s->d_gb_work, 0, sizeof(unsigned), stream));
-  *grid = (unsigned)std::min<unsigned long long>((unsigned long long)s->grid_blocks,
-                                                 (items + s->waves_per_block - 1) / s->waves_per_block);
   return MT_OK;
 }
 }  // extern "C++"
@@ -2161,6 +2173,65 @@ int launch_shade_direct(mt_scene *s, const mt_sensor *sensor, int chunk_x, int c
   return MT_OK;
 }
 
+// mt_update_lightbuffer[_device]: checked before any device call, in the order of the header.
+int check_update_args(const mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb, const int32_t *light_idx,
+                      int n_idx, const mt_lightbuffer *lb) {
+  if (!lb) return fail(MT_ERR_ARG, "the mt_lightbuffer is NULL");
+  if (!lb->power && !lb->in_shadow) return fail(MT_ERR_ARG, "no plane of the mt_lightbuffer is set");
+  if (!gb) return fail(MT_ERR_ARG, "the mt_gbuffer is NULL");
+  if (!gb->point || !gb->material) {
+    return fail(MT_ERR_ARG, "the light-buffer update needs the point and material planes of the mt_gbuffer");
+  }
+  if (chunk_w <= 0 || chunk_h <= 0 || chunk_w > 100000 || chunk_h > 100000) {
+    return fail(MT_ERR_ARG, "chunk size %dx%d out of range", chunk_w, chunk_h);
+  }
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (n_idx <= 0 || !light_idx) return fail(MT_ERR_ARG, "bad light index list");
+  for (int i = 0; i < n_idx; i++) {
+    if (light_idx[i] < 0 || light_idx[i] >= s->dev.n_lights) {
+      return fail(MT_ERR_ARG, "light index %d outside the scene's %d lights", light_idx[i], s->dev.n_lights);
+    }
+  }
+  // (no index is listed twice: at most n_lights entries are compared)
+  std::vector<bool> seen((size_t)s->dev.n_lights, false);
+  for (int i = 0; i < n_idx; i++) {
+    if (seen[(size_t)light_idx[i]]) return fail(MT_ERR_ARG, "light index %d is listed twice", light_idx[i]);
+    seen[(size_t)light_idx[i]] = true;
+  }
+  return MT_OK;
+}
+
+// lightbuffer_update_kernel over the chunk x the listed lights; planes = device pointers, light_idx = host array
+int launch_lightbuffer_update(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer &d_gb, const int32_t *light_idx,
+                              int n_idx, const mt_lightbuffer &d_lb, hipStream_t stream) {
+  LightUpdateArgs A{};
+  A.chunk_w = chunk_w; A.chunk_h = chunk_h;
+  A.blocks_x = (chunk_w + 7) / 8;
+  const unsigned long long blocks = (unsigned long long)A.blocks_x * (unsigned long long)((chunk_h + 7) / 8);
+  const unsigned long long items = blocks * (unsigned long long)n_idx;
+  if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
+  A.n_blocks = (unsigned)blocks;
+  A.n_items = (unsigned)items;
+  A.point = d_gb.point; A.material = d_gb.material;
+  A.n_materials = s->n_materials;
+  A.power = d_lb.power; A.in_shadow = d_lb.in_shadow;
+  if (n_idx <= kUpdateArgLights) {
+    for (int i = 0; i < n_idx; i++) A.idx[i] = light_idx[i];
+  } else {
+    MT_TRY(s->d_update_idx.ensure((size_t)n_idx * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(s->d_update_idx, light_idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    A.d_idx = s->d_update_idx;
+  }
+  unsigned grid = 0;
+  MT_TRY(prepare_persistent_launch(s, items, &grid, stream));
+  A.counters = s->d_counters;
+  A.work_counter = s->d_gb_work;
+  hipLaunchKernelGGL(kernels_of(s->deep).lightbuffer_update[s->stats_enabled ? 1 : 0], dim3(grid),
+                     dim3(s->waves_per_block * 64), s->lds_bytes, stream, s->dev, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
 }  // namespace
 
 int mt_render_lightbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
@@ -2259,6 +2330,60 @@ int mt_shade_direct(mt_scene *s, const mt_sensor *sensor, int image_w, int image
     stats->kernel_ms = ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   }
+  return MT_OK;
+}
+
+int mt_update_lightbuffer_device(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *d_gb, const int32_t *light_idx,
+                                 int n_idx, const mt_lightbuffer *d_lb, void *stream) {
+  MT_TRY(check_update_args(s, chunk_w, chunk_h, d_gb, light_idx, n_idx, d_lb));
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_lightbuffer_update(s, chunk_w, chunk_h, *d_gb, light_idx, n_idx, *d_lb, (hipStream_t)stream);
+}
+
+// The host form: point and material go up into the scene's G-buffer buffers; the planes of the LISTED lights are
+// computed at their places in the scene's light-buffer buffers and only they come back (planes_to_host) -- nothing of
+// the caller's other planes travels in either direction.
+int mt_update_lightbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb, const int32_t *light_idx, int n_idx,
+                          const mt_lightbuffer *lb, mt_stats *stats) {
+  MT_TRY(check_update_args(s, chunk_w, chunk_h, gb, light_idx, n_idx, lb));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  const size_t n_l = (size_t)s->dev.n_lights;
+  hipStream_t stream = nullptr;
+  MT_TRY(s->d_gb_f64[1].ensure(npx * 24));
+  MT_TRY(s->d_gb_i32[2].ensure(npx * 4));
+  mt_gbuffer d{};
+  d.point = s->d_gb_f64[1]; d.material = s->d_gb_i32[2];
+  mt_lightbuffer dl{};
+  std::vector<PlaneCopy> copies;
+  if (lb->power) {
+    MT_TRY(s->d_lb_power.ensure(n_l * npx * 24));
+    dl.power = s->d_lb_power;
+  }
+  if (lb->in_shadow) {
+    MT_TRY(s->d_lb_shadow.ensure(n_l * npx));
+    dl.in_shadow = s->d_lb_shadow;
+  }
+  for (int i = 0; i < n_idx; i++) {
+    const size_t l = (size_t)light_idx[i];
+    if (lb->power) copies.push_back({lb->power + l * npx * 3, dl.power + l * npx * 3, npx * 24});
+    if (lb->in_shadow) copies.push_back({lb->in_shadow + l * npx, dl.in_shadow + l * npx, npx});
+  }
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
+  HIP_TRY(hipMemcpyAsync(d.point, gb->point, npx * 24, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d.material, gb->material, npx * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = launch_lightbuffer_update(s, chunk_w, chunk_h, d, light_idx, n_idx, dl, stream);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  MT_TRY(planes_to_host(s, copies, stream));
+  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
   return MT_OK;
 }
 

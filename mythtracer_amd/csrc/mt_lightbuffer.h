@@ -17,6 +17,9 @@
 // lane wants.  start point, light power and the traversing flag live in registers: there is no recursion, so nothing
 // is parked.
 //
+// lightbuffer_update_kernel: the same loops for a LIST of lights from a stored G-buffer's point and material planes,
+// without the primary trace: what a moved light costs.  The loop body is restated there, lightbuffer_kernel is as it was.
+//
 // shade_direct_kernel: mythtracer.cc:38-177 for one pixel from the stored planes -- point, unflipped normal, albedo,
 // material (G-buffer), power and in_shadow (light buffer) -- and a list of lights whose colours may have changed
 // since: no traversal, one thread per pixel, fp64 in the reference's order of operations (this translation unit is
@@ -163,6 +166,144 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void lightbuffer_kernel(Dev
   }
 }
 
+// lightbuffer_update_kernel: the planes of the LISTED lights again, from the stored primary hits -- the G-buffer's
+// `point` and `material` planes hold, bit for bit, the two things a shadow loop takes from the primary trace.  No
+// sensor, no primary trace_wave; the planes of the other lights are not touched.  A work item is one 8x8 block of the
+// chunk x one listed light (item = k n_blocks + block: neighbouring items are neighbouring blocks of one light), so
+// that one light on a small chunk still fills the chip.  A pixel's loop runs when point[0] is not NaN and
+// 0 <= material < n_materials (the plane is the caller's; the index itself is never read with); every other pixel
+// of the chunk gets NaN / 255.  Lit pixels are NOT compacted across blocks: the walk is wave-synchronous and lives on
+// the coherence of an 8x8 block's rays.
+constexpr int kUpdateArgLights = 8;  // indices that travel with the launch; more in device memory
+
+struct LightUpdateArgs {
+  int32_t chunk_w, chunk_h;
+  int32_t blocks_x;
+  uint32_t n_blocks;                 // 8x8 blocks of the chunk
+  uint32_t n_items;                  // n_blocks x listed lights
+  const double *point;               // G-buffer planes of the chunk
+  const int32_t *material;
+  int32_t n_materials;
+  double *power;                     // optional; [n_lights][chunk_h][chunk_w][3], plane l written for listed l only
+  uint8_t *in_shadow;                // optional
+  const int32_t *d_idx;              // the list when it has more than kUpdateArgLights entries, else nullptr
+  int32_t idx[kUpdateArgLights];
+  unsigned long long *counters;      // ST_COUNT
+  unsigned int *work_counter;        // zero at launch
+};
+
+template <bool STATS, int DEEP>
+__global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void lightbuffer_update_kernel(DevScene S, LightUpdateArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave_in_block = threadIdx.x >> 6;
+  WaveStack stk;
+  stk.bind(smem, wave_in_block, S.tree_depth, S.pack_shift, DEEP != 0);
+  const MT_CONST mt_material *mtls = as_const(S.mtls);
+  const MT_CONST mt_light *lights = as_const(S.lights);
+  LaneStats st;
+  st.clear();
+  const size_t npx = (size_t)A.chunk_w * (size_t)A.chunk_h;
+  const int iteration_bound = S.n_tris + 2;
+  bool failed = false;
+  for (;;) {
+    const unsigned item = fetch_work(A.work_counter, lane);
+    if (item >= A.n_items) break;
+    const unsigned k = item / A.n_blocks, block = item % A.n_blocks;  // (wave-uniform)
+    const int li = A.d_idx != nullptr ? A.d_idx[k] : A.idx[k];
+    const int lx = (int)(block % (unsigned)A.blocks_x) * 8 + (lane & 7);
+    const int ly = (int)(block / (unsigned)A.blocks_x) * 8 + (lane >> 3);
+    const bool want = lx < A.chunk_w && ly < A.chunk_h;
+    const size_t px = (size_t)ly * (size_t)A.chunk_w + (size_t)lx;
+    V3 Pt = v3(0, 0, 0);
+    bool lit = false;
+    if (want) {
+      const V3 p = v3_load(A.point + px * 3);
+      const int mtl = A.material[px];
+      lit = p.x == p.x && mtl >= 0 && mtl < A.n_materials;
+      if (lit) Pt = p;
+      if (STATS) st.v[ST_BYTES_VECTOR] += 24u + 4u;
+    }
+    const MT_CONST mt_light *lt = lights + li;
+    const V3 lpos = v3(lt->position[0], lt->position[1], lt->position[2]);
+    // from here to the stores: lightbuffer_kernel's light loop body, the same operations in the same order
+    V3 start = Pt, lp = v3(1.0, 1.0, 1.0);  // :90, :94
+    bool in_shadow = false, traversing = false, running = lit;
+    V3 ro = Pt, ld = v3(0, 0, 1);
+    if (lit) {
+      ld = normalized(lpos - Pt);  // light_direction, :79-80
+      ro = Pt + (ld * 0.00001);    // :95-99
+    }
+    int iterations = 0;
+    while (__ballot(running) != 0ull) {
+      const TraceOut so = trace_wave<STATS, DEEP>(S.self, stk.base, lane, running, ro.x, ro.y, ro.z, ld.x, ld.y, ld.z);
+      add_trace_stats<STATS>(st, so);
+      if (so.status != DEV_OK || ++iterations > iteration_bound) {
+        if (lane == 0) {
+          atomicMax(A.counters + ST_STATUS, (unsigned long long)(so.status != DEV_OK ? so.status : DEV_ERR_PIXEL_BOUND));
+        }
+        failed = true;
+        break;
+      }
+      if (running) {  // one iteration of the shadow loop, mythtracer.cc:94-156 (as mt_render.hip states it)
+        if (STATS) {
+          st.v[ST_RAYS_SHADOW]++;
+          st.v[ST_BYTES_VECTOR] += 96u + 4u + 32u;  // light, occluder's material index and transparency
+        }
+        const int prim = so.prim;
+        const double t = so.t;
+        if (prim < 0) {
+          running = false;  // :109-112
+        } else {
+          const double light_distance = distance(start, lpos);  // :101-102
+          if (t > light_distance) {
+            running = false;  // :115-118
+          } else {
+            // :121 dereferences shadow_primitive->mtl unconditionally; defined as opaque (mt_render.hip)
+            const int sm = S.tri_mtl[prim];
+            const double s_tr = sm >= 0 ? mtls[sm].transparency : 0.0;
+            if (s_tr == 0.0) {
+              lp = v3(0, 0, 0);
+              in_shadow = true;
+              running = false;
+            } else {
+              if (!traversing) {  // :129-132
+                const MT_CONST mt_material *smm = mtls + sm;
+                const V3 tf = v3(smm->transmission_filter[0], smm->transmission_filter[1],
+                                 smm->transmission_filter[2]);
+                lp = lp * (tf * s_tr);
+              }
+              traversing = !traversing;
+              const V3 sp = ro + ld * t;
+              start = sp + (ld * 0.0000001);  // :137
+              if (sqr_distance(Pt, start) > sqr_distance(Pt, lpos)) {
+                running = false;  // :141-145
+              } else if (lp.x <= 0.001 && lp.y <= 0.001 && lp.z <= 0.001) {
+                lp = v3(0, 0, 0);  // :149-155
+                in_shadow = true;
+                running = false;
+              } else {
+                ro = start + (ld * 0.00001);  // next iteration, :95-99
+              }
+            }
+          }
+        }
+      }
+    }
+    if (failed) break;
+    if (want) {
+      const size_t at = (size_t)li * npx + px;
+      if (A.power) {
+        const double nan = __builtin_nan("");
+        store3(A.power, at, lit ? lp : v3(nan, nan, nan));
+      }
+      if (A.in_shadow) A.in_shadow[at] = lit ? (in_shadow ? 1 : 0) : 255;
+      if (STATS) st.v[ST_BYTES_VECTOR] += (A.power ? 24u : 0u) + (A.in_shadow ? 1u : 0u);
+    }
+    flush_item_stats<STATS>(st, A.counters, lane);
+  }
+}
+
 // The lights of a relight: up to kShadeArgLights travel as a kernel argument, more in device memory.
 constexpr int kShadeArgLights = 8;
 
@@ -243,7 +384,9 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(ShadeDirectArgs A) {
 
 #define MT_INSTANTIATE_LB(DEEP_)                                                         \
   template __global__ void lightbuffer_kernel<true, DEEP_>(DevScene, LightBufferArgs);   \
-  template __global__ void lightbuffer_kernel<false, DEEP_>(DevScene, LightBufferArgs);
+  template __global__ void lightbuffer_kernel<false, DEEP_>(DevScene, LightBufferArgs);  \
+  template __global__ void lightbuffer_update_kernel<true, DEEP_>(DevScene, LightUpdateArgs);   \
+  template __global__ void lightbuffer_update_kernel<false, DEEP_>(DevScene, LightUpdateArgs);
 MT_INSTANTIATE_LB(0)
 MT_INSTANTIATE_LB(1)
 MT_INSTANTIATE_LB(2)

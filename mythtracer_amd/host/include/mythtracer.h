@@ -128,11 +128,18 @@ class MythTracer {
   // The frame of the direct term -- what RayTrace gives with SetMaxRecursionLevel(0) -- from stored planes and
   // GetScene()->lights, without tracing a ray (mt_shade_direct): for lights whose ambient, diffuse or specular were
   // edited since the light buffer was made.  Their count and positions must be the light buffer's: a moved light needs
-  // a new RayTraceLightBuffer.  `gbuffer` must hold point, normal, albedo and material, `lightbuffer` both planes, all
+  // UpdateLightBuffer first.  `gbuffer` must hold point, normal, albedo and material, `lightbuffer` both planes, all
   // of this frame (or chunk->chunk_*) and camera.  output_bitmap is resized to width x height x 3.
   bool ShadeDirect(int image_width, int image_height, Camera* camera, const GBuffer& gbuffer,
                    const LightBuffer& lightbuffer, std::vector<uint8_t>* output_bitmap);
   bool ShadeDirect(WorkChunk* chunk, const GBuffer& gbuffer, const LightBuffer& lightbuffer);
+  // After lights have MOVED: the planes of the lights listed in `lights` (indices into GetScene()->lights, each at most
+  // once) of `lightbuffer` traced again under GetScene()->lights from the point and material planes of `gbuffer`, without
+  // a primary ray (mt_update_lightbuffer); the planes of the other lights are not touched.  Both structs must describe
+  // the same chunk, `lightbuffer` as many lights as the scene has now; the planes `lightbuffer->channels` selects are
+  // updated.  The result is what a new RayTraceLightBuffer gives if only the listed lights moved since the planes were
+  // made.  Refused with several devices, like its siblings; LastStats() describes the call.
+  bool UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

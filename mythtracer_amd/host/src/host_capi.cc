@@ -397,6 +397,52 @@ int mth_shade_direct(void* p, const double* cam7, int iw, int ih, int cx, int cy
   return 1;
 }
 
+// MythTracer::UpdateLightBuffer(GBuffer, lights, LightBuffer*) under the facade's lights.  gb_planes[2] = point
+// (doubles), material (int32) of the cw x ch chunk; lb_channels = LightBuffer::k* bits, lb_planes[2] = power, in_shadow
+// for n_lights lights (each NULL or sized for them), updated in place: the planes of the listed lights only.
+int mth_update_lightbuffer(void* p, int cw, int ch, void* const* gb_planes, const int* light_idx, int n_idx,
+                           unsigned lb_channels, void* const* lb_planes, int n_lights, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  const size_t npx = (size_t)(cw > 0 ? cw : 0) * (size_t)(ch > 0 ? ch : 0);
+  const size_t n_l = (size_t)(n_lights > 0 ? n_lights : 0);
+  raytracer::GBuffer g;
+  g.width = cw;
+  g.height = ch;
+  if (gb_planes && gb_planes[0] && gb_planes[1]) {  // (else the facade refuses: the planes are missing)
+    g.point.assign((const double*)gb_planes[0], (const double*)gb_planes[0] + npx * 3);
+    g.material.assign((const int32_t*)gb_planes[1], (const int32_t*)gb_planes[1] + npx);
+  }
+  raytracer::LightBuffer lb;
+  lb.channels = lb_channels;
+  lb.width = cw;
+  lb.height = ch;
+  lb.n_lights = n_lights;
+  const bool power = (lb_channels & raytracer::LightBuffer::kPower) && lb_planes && lb_planes[0];
+  const bool shadow = (lb_channels & raytracer::LightBuffer::kInShadow) && lb_planes && lb_planes[1];
+  // The update reads nothing of the old planes and writes the listed ones only: the caller's planes are not copied
+  // in, and only the listed planes are copied back (the list is valid once the call has succeeded).
+  if (power) lb.power.resize(n_l * npx * 3);
+  if (shadow) lb.in_shadow.resize(n_l * npx);
+  const std::vector<int> lights(light_idx, light_idx + (light_idx && n_idx > 0 ? n_idx : 0));
+  if (!h->mt.UpdateLightBuffer(g, lights, &lb)) return 0;
+  for (int l : lights) {
+    const size_t at = (size_t)l * npx;
+    if (power) memcpy((double*)lb_planes[0] + at * 3, lb.power.data() + at * 3, npx * 3 * sizeof(double));
+    if (shadow) memcpy((uint8_t*)lb_planes[1] + at, lb.in_shadow.data() + at, npx);
+  }
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::RayTrace(int, int, Camera*, vector*)
 int mth_render_image(void* p, const double* cam7, int iw, int ih, uint8_t* rgb) {
   Handle* h = static_cast<Handle*>(p);

@@ -576,6 +576,61 @@ bool MythTracer::ShadeDirect(WorkChunk* chunk, const GBuffer& gbuffer, const Lig
   return true;
 }
 
+bool MythTracer::UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device, as in RayTraceLightBuffer)
+  if (lightbuffer == nullptr) return refuse("LightBuffer is NULL");
+  if (devices_.size() > 1) return refuse("the light-buffer update is not supported with several devices (SetDevices)");
+  if ((lightbuffer->channels & LightBuffer::kAll) == 0) return refuse("LightBuffer::channels selects no plane");
+  if (lightbuffer->width <= 0 || lightbuffer->height <= 0) return refuse("empty chunk");
+  const size_t npx = (size_t)lightbuffer->width * (size_t)lightbuffer->height;
+  const size_t n_l = scene.lights.size();
+  if (gbuffer.width != lightbuffer->width || gbuffer.height != lightbuffer->height) {
+    return refuse("the GBuffer and the LightBuffer must describe the same chunk");
+  }
+  if (gbuffer.point.size() != npx * 3 || gbuffer.material.size() != npx) {
+    return refuse("UpdateLightBuffer needs the point and material planes of the GBuffer");
+  }
+  if ((size_t)lightbuffer->n_lights != n_l) {
+    return refuse("the LightBuffer was made with another number of lights: a new RayTraceLightBuffer is needed");
+  }
+  const bool power = (lightbuffer->channels & LightBuffer::kPower) != 0;
+  const bool shadow = (lightbuffer->channels & LightBuffer::kInShadow) != 0;
+  if ((power && lightbuffer->power.size() != n_l * npx * 3) || (shadow && lightbuffer->in_shadow.size() != n_l * npx)) {
+    return refuse("the planes LightBuffer::channels selects do not have the size of n_lights x the chunk");
+  }
+  if (lights.empty()) return refuse("no light is listed");
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)n_l) != MT_OK) {
+    return refuse(std::string("light-buffer update failed: ") + mt_last_error());
+  }
+  mt_gbuffer g{};
+  g.point = const_cast<double*>(gbuffer.point.data());
+  g.material = const_cast<int32_t*>(gbuffer.material.data());
+  mt_lightbuffer lb{power ? lightbuffer->power.data() : nullptr, shadow ? lightbuffer->in_shadow.data() : nullptr};
+  std::vector<int32_t> idx(lights.begin(), lights.end());
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_update_lightbuffer(dev_, lightbuffer->width, lightbuffer->height, &g, idx.data(), (int)idx.size(), &lb, &st) !=
+      MT_OK) {
+    return refuse(std::string("light-buffer update failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
 // ---- wire format of a chunk (mythtracer.cc:314-429): six little-endian u32
 // in, u32 byte count + RGB bytes out.
 
