@@ -264,6 +264,62 @@ int mt_resolve_tiles_device(mt_scene *scene, int image_w, int image_h, int tile_
                             int first_tile, int tile_stride, const void *d_list, int n_tiles, int ss,
                             const void *d_samples, void *d_tiles, void *stream);
 
+/* Adaptive supersampling (Whitted's): one ray per pixel first, ss x ss samples only where neighbouring pixels differ.
+ * (No reference counterpart.)  Everything is integer arithmetic on bytes the calls above already make:
+ *   BLOCKS are the 8 x 8 grid of the IMAGE (not of the chunk): block (bx, by) covers [8 bx, 8 bx + 8) x [8 by, 8 by + 8)
+ *     clipped to the image; its tile number is by ceil(image_w / 8) + bx -- the number the tile calls use at (image_w,
+ *     image_h, 8, 8) and at (ss image_w, ss image_h, 8 ss, 8 ss).  The blocks OF A CHUNK are those with a chunk pixel:
+ *     mask_x0 = chunk_x / 8, mask_w = (chunk_x + chunk_w - 1) / 8 - mask_x0 + 1, likewise in y; n_blocks = mask_w mask_h,
+ *     row-major.
+ *   CONTRAST: F = the chunk's plain frame (mt_render_chunk's bytes).  Two horizontal or vertical neighbours that BOTH
+ *     lie in the chunk are a pair; a pair is contrasty when max over the channels of |F[p][c] - F[q][c]| > threshold
+ *     (0 .. 255).  A block is REFINED iff a pixel of a contrasty pair lies in it: a pair across a block border refines
+ *     both blocks.  Threshold 255 refines nothing.
+ *   OUTPUT: the chunk's pixels in refined blocks are mt_render_chunk_ss's bytes (same ss, sensor_ss = the sensor of the
+ *     sample grid), all others mt_render_chunk's (sensor = the sensor of the output grid).
+ * Pairs across the chunk's border do not exist, so an adaptive chunk is THE ONE RESULT OF THIS LIBRARY THAT DEPENDS ON
+ * HOW THE IMAGE WAS CUT INTO CHUNKS: chunks blitted together are not the adaptive frame of the whole image.
+ *   mt_refine_mask_device: the building block, for a chunk bitmap already in HBM at d_rgb: d_mask (nullable) gets the
+ *     n_blocks flags (0 / 1), d_list (int32, capacity n_blocks) the refined blocks' tile numbers IN ASCENDING ORDER -- an
+ *     order-preserving compaction: the same bitmap gives the same list --, d_count (uint32) their number.  Asynchronous.
+ *   mt_render_chunk_adaptive: (1) the plain launch into the output bitmap, exactly mt_render_chunk's; (2) mask and
+ *     list; (3) the count and a hash of the list come back to the host: ONE STREAM SYNCHRONISATION in the middle of
+ *     the call, because a launch sizes its buffers from a host-known number of tiles; (4) the scene's sample buffer is
+ *     grown to n_refined 64 ss ss 3 bytes (MT_ERR_NOMEM when it does not fit: never a lower ss); (5) the refined blocks
+ *     are rendered whole -- pixels outside the chunk included -- by one tile-list launch at (ss image_w, ss image_h,
+ *     8 ss, 8 ss) with sensor_ss; (6) and resolved over the output bitmap.  Without refined blocks (4) - (6) do not run.
+ *     The two launches keep SEPARATE cost histories: after the call the scene's history is what mt_render_chunk with
+ *     the same arguments would have left (a following plain frame, mt_scene_export_costs_device and the next adaptive
+ *     call's plain launch see that); the refinement launch runs on measured costs when the previous refinement of the
+ *     same geometry had the same list (list_id = hash | 1), else it is a launch without history.
+ *     mt_scene_set_scheduling, mt_scene_set_engine and mt_scene_set_tuning forget both histories.
+ *     out_mask (nullable): n_blocks bytes.  stats: the work counters are the sums of both launches -- rays_primary =
+ *     chunk_w chunk_h + ss ss (sum of area(refined block within the image)) --, kernel_ms all kernels of the call by
+ *     events (the synchronisation's idle time excluded), total_ms the wall time.  mt_scene_kernel_times reports the
+ *     plain launch and then the refinement launch, TWO entries (one without refined blocks).
+ *   mt_render_chunk_adaptive_device: the same with d_rgb / d_mask in HBM and no stats.  NOT fully asynchronous: it
+ *     synchronises `stream` once (step 3) and returns with steps (5) - (6) queued.
+ * ss = 1 is the plain call through the plain call's path: an all-zero mask, n_refined 0.  Argument checks come before
+ * any device call, in this order: ss and the sample grid, threshold, the output pointer, image and chunk, the scene,
+ * the sensors (sensor_ss may be NULL with ss = 1 only). */
+typedef struct mt_adaptive_info {
+  int32_t n_blocks;        /* blocks of the chunk (mask_w * mask_h) */
+  int32_t n_refined;       /* of them refined */
+  int32_t plain_history;   /* 1: the plain launch took its work order from measured costs */
+  int32_t refine_history;  /* the same for the refinement launch; 0 also when n_refined == 0 */
+} mt_adaptive_info;
+int mt_refine_mask_device(mt_scene *scene, int image_w, int image_h, int chunk_x, int chunk_y, int chunk_w,
+                          int chunk_h, int threshold, const void *d_rgb, void *d_mask, void *d_list,
+                          void *d_count, void *stream);
+int mt_render_chunk_adaptive(mt_scene *scene, const mt_sensor *sensor, const mt_sensor *sensor_ss, int image_w,
+                             int image_h, int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int threshold,
+                             int max_depth, uint8_t *out_rgb, uint8_t *out_mask, mt_adaptive_info *info,
+                             mt_stats *stats);
+int mt_render_chunk_adaptive_device(mt_scene *scene, const mt_sensor *sensor, const mt_sensor *sensor_ss,
+                                    int image_w, int image_h, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                                    int ss, int threshold, int max_depth, void *d_rgb, void *d_mask,
+                                    mt_adaptive_info *info, void *stream);
+
 /* The primary-hit G-buffer of a chunk: what the first call of TraceRayWorker (mythtracer.cc:18-64) knows about a pixel
  * before it looks at a light, as separate planes.  (No reference counterpart: the reference returns a colour and
  * PerPixelDebugInfo only.)  Per pixel, with the frame kernels' arithmetic: Sensor::GetRay (camera.cc:65-69),

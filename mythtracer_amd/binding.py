@@ -29,6 +29,7 @@ HIP_SYMBOLS = [
     "mt_render_gbuffer", "mt_render_gbuffer_device",
     "mt_render_lightbuffer", "mt_render_lightbuffer_device", "mt_shade_direct", "mt_shade_direct_device",
     "mt_update_lightbuffer", "mt_update_lightbuffer_device",
+    "mt_refine_mask_device", "mt_render_chunk_adaptive", "mt_render_chunk_adaptive_device",
 ]
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
@@ -80,6 +81,13 @@ class mt_stats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class mt_adaptive_info(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_blocks", "n_refined", "plain_history", "refine_history")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class mt_scene_desc(C.Structure):
@@ -269,6 +277,10 @@ class HipAbi:
         L.mt_shade_direct_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 6 + gl + [vp, ci, vp, vp]
         L.mt_update_lightbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp, ci, C.POINTER(mt_lightbuffer), vp]
         L.mt_update_lightbuffer_device.argtypes = L.mt_update_lightbuffer.argtypes
+        L.mt_refine_mask_device.argtypes = [vp] + [ci] * 7 + [vp] * 5
+        ps = C.POINTER(mt_sensor)
+        L.mt_render_chunk_adaptive.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
+        L.mt_render_chunk_adaptive_device.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
 
     def last_error(self) -> str:
         return self.lib.mt_last_error().decode(errors="replace")
@@ -438,6 +450,38 @@ class HipAbi:
                              ss, d_samples, d_tiles, stream=None):
         self.check(self.lib.mt_resolve_tiles_device(h, image_w, image_h, tile_w, tile_h, first_tile, tile_stride,
                                                     d_list, n_tiles, ss, d_samples, d_tiles, stream))
+
+    # ---- adaptive supersampling (include/mythtracer_hip.h, mt_render_chunk_adaptive ff.): sensor12 is the sensor of
+    # the output grid, sensor12_ss the sensor of the sample grid (None with ss = 1 only)
+    def render_chunk_adaptive(self, h, sensor12, sensor12_ss, image_w, image_h, ss, threshold, chunk=None, max_depth=5):
+        """mt_render_chunk_adaptive: dict rgb (the chunk), mask (bool [mask_h][mask_w], tiling.chunk_blocks), info
+        (mt_adaptive_info as a dict), stats."""
+        from .tiling import chunk_blocks
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        rgb = np.zeros((max(ch, 0), max(cw, 0), 3), dtype=np.uint8)
+        _, _, mw, mh = chunk_blocks((cx, cy, max(cw, 1), max(ch, 1)))
+        mask = np.zeros((mh, mw), dtype=np.uint8)
+        st, info = mt_stats(), mt_adaptive_info()
+        s = self.make_sensor(sensor12)
+        s_ss = C.byref(self.make_sensor(sensor12_ss)) if sensor12_ss is not None else None
+        self.check(self.lib.mt_render_chunk_adaptive(h, C.byref(s), s_ss, image_w, image_h, cx, cy, cw, ch, ss,
+                                                     threshold, max_depth, _ptr(rgb), _ptr(mask), C.byref(info),
+                                                     C.addressof(st)))
+        return dict(rgb=rgb, mask=mask.astype(bool), info=info.as_dict(), stats=st.as_dict())
+
+    def render_chunk_adaptive_device(self, h, sensor12, sensor12_ss, image_w, image_h, chunk, ss, threshold, max_depth,
+                                     d_rgb, d_mask=None, stream=None):
+        """mt_render_chunk_adaptive_device (synchronises `stream` once, see the header); returns the info dict."""
+        info = mt_adaptive_info()
+        s = self.make_sensor(sensor12)
+        s_ss = C.byref(self.make_sensor(sensor12_ss)) if sensor12_ss is not None else None
+        self.check(self.lib.mt_render_chunk_adaptive_device(h, C.byref(s), s_ss, image_w, image_h, *chunk, ss, threshold,
+                                                            max_depth, d_rgb, d_mask, C.byref(info), stream))
+        return info.as_dict()
+
+    def refine_mask_device(self, h, image_w, image_h, chunk, threshold, d_rgb, d_mask, d_list, d_count, stream=None):
+        self.check(self.lib.mt_refine_mask_device(h, image_w, image_h, *chunk, threshold, d_rgb, d_mask, d_list,
+                                                  d_count, stream))
 
     # ---- the primary-hit G-buffer (include/mythtracer_hip.h, mt_render_gbuffer)
     def render_gbuffer(self, h, sensor12, image_w, image_h, chunk=None, channels=None):
@@ -659,6 +703,8 @@ def host_lib():
     L.mth_set_max_level.restype = None
     L.mth_set_supersampling.argtypes = [vp, ci]
     L.mth_set_supersampling.restype = None
+    L.mth_set_adaptive_supersampling.argtypes = [vp, ci, ci]
+    L.mth_set_adaptive_supersampling.restype = None
     L.mth_finalize.argtypes = [vp]
     L.mth_finalize.restype = None
     L.mth_prepare.argtypes = [vp]
@@ -772,6 +818,11 @@ class MythTracer:
     def set_supersampling(self, s):
         """MythTracer::SetSupersampling: s x s samples per pixel in render / render_image (1 .. 4, default 1)."""
         self.L.mth_set_supersampling(self.h, int(s))
+
+    def set_adaptive_supersampling(self, s, threshold):
+        """MythTracer::SetAdaptiveSupersampling: s x s samples only in the 8 x 8 blocks whose neighbouring pixels differ
+        by more than `threshold`; s <= 1 switches it off.  Wins over set_supersampling."""
+        self.L.mth_set_adaptive_supersampling(self.h, int(s), int(threshold))
 
     def finalize(self):
         self.L.mth_finalize(self.h)

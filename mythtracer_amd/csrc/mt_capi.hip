@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -26,6 +27,7 @@
 // side so that no relocatable device code is needed.
 #include "mt_render.hip"
 #include "mt_resolve.h"
+#include "mt_adaptive.h"
 #include "mt_gbuffer.h"
 #include "mt_lightbuffer.h"
 
@@ -134,6 +136,39 @@ struct Tuning {
 // process-wide default of mt_scene_set_engine for scenes created from now on (mt_set_default_engine)
 std::atomic<int> g_default_engine{0};
 
+// The forecast state of a scene: what decide_launch, size_buffers and launch_render keep from one launch for the next
+// -- the measured block costs, the geometry, camera and engine they belong to, and the buffers of the work order made
+// from them.  A launch of another geometry starts it over, so two geometries that alternate each need their own: a
+// scene has two banks.  Bank 0 serves every call; bank 1, allocated on first use, only the refinement launch of an
+// adaptive chunk (mt_render_chunk_adaptive), which alternates with that chunk's plain launch.
+struct ForecastBank {
+  // cost feedback (schedule_kernel): valid for launches of the same geometry
+  Buf<unsigned int> d_item_cost;       // [n_items]
+  Buf<unsigned int> d_item_forecast;   // [n_items]
+  Buf<unsigned int> d_item_forms;      // [2 n_items] cost of a block as one unit / as four quarters (forecast_kernel)
+  Buf<unsigned char> d_item_form;      // [n_items] hybrid launches: how each block was rendered (hybrid_schedule_kernel)
+  Buf<unsigned int> d_item_unit;
+  Buf<unsigned short> d_item_cell;
+  Buf<unsigned int> d_order_item;      // [4 n_items]
+  Buf<signed char> d_order_sub;        // [4 n_items]
+  // tile-list launches (mt_render_tile_list_device): the launch's own copy of the list, and tile -> slot (last_P
+  // points at them)
+  Buf<int32_t> d_tile_list;
+  Buf<int32_t> d_tile_slot;
+  mt_sensor cost_sensor{};                // camera of the launch that measured the costs
+  unsigned long long cost_signature = 0;  // 0 = no history
+  int forecasts_in_a_row = 0;  // launches with this geometry and camera whose work order came from a forecast
+  int last_engine = 0;         // engine of the previous launch (cost histories are per engine)
+  bool last_history = false;   // LaunchPlan::history of the previous launch
+  RenderParams last_P{};       // geometry of the last launch (mt_scene_export_costs_device)
+  bool last_P_valid = false;
+  unsigned long long launches = 0;                 // launches of this bank so far
+  unsigned long long cost_map_for_launch = ~0ull;  // the scene's cost map describes the frame of launch number ... (`launches` then)
+  mt_sensor irr_sensor{};      // the sensor `irr_sensor_has` was found for (image irr_w x irr_h)
+  int irr_w = 0, irr_h = 0, irr_sensor_has = 0;
+  bool irr_sensor_valid = false;
+};
+
 }  // namespace
 
 struct mt_scene {
@@ -146,36 +181,34 @@ struct mt_scene {
   Buf<unsigned int> d_queues;  // kQueueWords: the per-XCD work orders' counters and bounds (RenderParams::queues)
   Buf<unsigned int> d_order_ctl;  // kOrdWords: the work-order kernels' sums, histograms, grids (zero at creation, never reset by the host)
   Buf<unsigned int> d_order_whist; // [kOrdGroupsMax][kOrdKeysMax]
-  Buf<unsigned int> d_item_unit;
   unsigned order_epoch = 0;             // work orders of this scene so far (order_forecast_kernel, order_count_kernel, order_scatter_kernel)
-  mt_sensor irr_sensor{};               // the sensor `irr_sensor_has` was found for (image irr_w x irr_h)
-  int irr_w = 0, irr_h = 0, irr_sensor_has = 0;
-  bool irr_sensor_valid = false;
   DevScene dev_uploaded;                // what d_dev holds
   bool dev_uploaded_valid = false;
-  Buf<unsigned short> d_item_cell;
   Buf<double> d_frames;            // throughput engine: recursion frames
   Buf<int32_t> d_hit_prim;         // launch 1 -> launch 2 hand-off (per pixel)
   Buf<double> d_hit_t;
   Buf<unsigned int> d_class_list;  // [3][n_items]
   Buf<char> d_pool;                // latency engine: ray pool scratch of every wave (mt_pool.h)
   int engine = 0;                  // 0 = automatic, 1 = throughput (state machine), 2 = latency (ray pool)
-  int last_engine = 0;             // engine of the previous launch (cost histories are per engine)
-  // cost feedback (schedule_kernel): valid for launches of the same geometry
-  Buf<unsigned int> d_item_cost;       // [n_items]
-  Buf<unsigned int> d_item_forecast;   // [n_items]
-  Buf<unsigned int> d_item_forms;      // [2 n_items] cost of a block as one unit / as four quarters (forecast_kernel)
-  Buf<unsigned char> d_item_form;      // [n_items] hybrid launches: how each block was rendered (hybrid_schedule_kernel)
-  mt_sensor cost_sensor{};               // camera of the launch that measured the costs
-  Buf<unsigned int> d_order_item;      // [4 n_items]
-  Buf<signed char> d_order_sub;        // [4 n_items]
-  unsigned long long cost_signature = 0;  // 0 = no history
+  ForecastBank bank0;                   // every call's forecast state ...
+  std::unique_ptr<ForecastBank> bank1;  // ... but the refinement launch's of an adaptive chunk (first use)
+  void forget_histories() {  // other settings, other order: start from a first frame
+    bank0.cost_signature = 0;
+    if (bank1) bank1->cost_signature = 0;
+  }
   bool use_history = true;
   Buf<uint8_t> d_rgb;
   Buf<uint8_t> d_samples;  // supersampled chunks: the sample frame on its way to resolve_kernel (mt_resolve.h)
   Buf<mt_debug_px> d_debug;
+  // adaptive chunks (mt_adaptive.h), allocated on first use: the chunk's block flags, the refined blocks' list, count
+  // and hash on the device and in pinned memory, the host call's mask, the events around the call's synchronisation
+  Buf<uint8_t> d_ad_flags;
+  Buf<int32_t> d_ad_list;
+  Buf<RefineCtl> d_ad_ctl;
+  Buf<RefineCtl, true> h_ad_ctl;
+  Buf<uint8_t> d_ad_mask;
+  hipEvent_t ev_ad[2] = {};
   std::vector<mt_light> lights_host;  // what d_lights holds
-  int forecasts_in_a_row = 0;  // launches with this geometry and camera whose work order came from a forecast
   int waves_per_block = 4;
   int deep = 0;                    // which DEEP instantiations of the kernels: 0, 1, 2 (mt_device.h, deep_layout)
   Buf<char> d_deep;                // their per-wave areas
@@ -194,11 +227,8 @@ struct mt_scene {
   Buf<DevScene> d_dev;                    // device copy of `dev` (DevScene::self)
   Tuning tune;
   // multi-GPU frames with a moving camera: every rank's costs of the previous frame (mt_scene_import_costs_device)
-  RenderParams last_P{};                  // geometry of the last launch (mt_scene_export_costs_device)
-  bool last_P_valid = false;
   Buf<unsigned int> d_cost_map;
   int cost_map_w = 0, cost_map_h = 0;
-  unsigned long long cost_map_for_launch = ~0ull;  // the map describes the frame of launch number ... (launches_timed then)
   int tree_depth_levels = 0, n_tris_total = 0, n_nodes_total = 0;  // for MT_TUNE_PACKED_STACK
   // -DMT_DEBUG_KNOBS builds only (read from the environment once, in mt_scene_create)
   std::string dbg_item_cycles, dbg_timeline;
@@ -218,9 +248,6 @@ struct mt_scene {
   static constexpr int kStagePieces = 16;
   hipEvent_t ev_stage[kStagePieces] = {};
   Buf<unsigned long long, true> h_counters;
-  // tile-list launches (mt_render_tile_list_device): the launch's own copy of the list, and tile -> slot
-  Buf<int32_t> d_tile_list;
-  Buf<int32_t> d_tile_slot;
   // mt_render_gbuffer (mt_gbuffer.h): stream index -> AddPrimitive index (mt_scene_desc::tri_id; kept OUTSIDE DevScene:
   // only gbuffer_kernel reads it; uploaded by the first call that wants the `prim` plane, like everything else here
   // allocated on first use: a scene that never makes a G-buffer has the allocations it had without the feature), the
@@ -423,7 +450,7 @@ struct LaunchPlan {
   int old_irr = 0, new_irr = 0;   // zero-component pixels in the frame that measured the costs / in this one
 };
 
-int decide_launch(mt_scene *s, const RenderParams &P, const mt_sensor *sensor, bool debug, const int32_t *d_list,
+int decide_launch(mt_scene *s, ForecastBank &B, const RenderParams &P, const mt_sensor *sensor, bool debug, const int32_t *d_list,
                   unsigned long long list_id, size_t waves, LaunchPlan &L) {
   const int image_w = P.image_w, image_h = P.image_h, max_depth = P.max_depth;
   // The block costs of the previous launch are a valid forecast when that
@@ -436,14 +463,14 @@ int decide_launch(mt_scene *s, const RenderParams &P, const mt_sensor *sensor, b
   L.sig = fnv1a({image_w, image_h, P.region_x, P.region_y, P.region_w, P.region_h, P.tile_w, P.tile_h, P.first_tile,
                  P.tile_stride, P.n_tiles, max_depth, s->dev.n_lights, d_list ? 1 : 0, d_list ? (long long)list_id : 0});
   // (a tile list promises to be the previous launch's list by its non-zero list_id only)
-  bool have_costs = s->use_history && s->cost_signature == L.sig && !(d_list != nullptr && list_id == 0);
+  bool have_costs = s->use_history && B.cost_signature == L.sig && !(d_list != nullptr && list_id == 0);
   // A list launch with ANOTHER list (the tiles were dealt out anew): the slots' cost words belong to other tiles, but the
   // frame-wide map imported since the previous launch has every block's cost by image position.
-  const bool map_ready = s->d_cost_map != nullptr && s->cost_map_for_launch == s->launches_timed &&
+  const bool map_ready = s->d_cost_map != nullptr && B.cost_map_for_launch == B.launches &&
                          s->cost_map_w >= (image_w + 7) / 8 && s->cost_map_h >= (image_h + 7) / 8;
-  L.from_map = s->use_history && d_list != nullptr && !have_costs && map_ready && s->last_P_valid &&
+  L.from_map = s->use_history && d_list != nullptr && !have_costs && map_ready && B.last_P_valid &&
                (P.tile_w & 7) == 0 && (P.tile_h & 7) == 0 && (P.region_x & 7) == 0 && (P.region_y & 7) == 0 &&
-               s->last_P.image_w == image_w && s->last_P.image_h == image_h && s->last_P.max_depth == max_depth;
+               B.last_P.image_w == image_w && B.last_P.image_h == image_h && B.last_P.max_depth == max_depth;
   if (L.from_map) have_costs = true;
   // ---- which engine?  Both compute every pixel with the same operations in the
   // same order (tests render through both).  The state machine (one lane per
@@ -510,59 +537,59 @@ int decide_launch(mt_scene *s, const RenderParams &P, const mt_sensor *sensor, b
   L.history = have_costs && (engine == 2 || !debug);  // (hybrid: both hold, see above)
   if (!L.history) return MT_OK;
   // (kept per sensor: a camera at rest is looked at once)
-  if (!s->irr_sensor_valid || memcmp(&s->irr_sensor, sensor, sizeof(mt_sensor)) != 0 || s->irr_w != image_w || s->irr_h != image_h) {
-    s->irr_sensor = *sensor; s->irr_w = image_w; s->irr_h = image_h;
-    s->irr_sensor_has = has_zero_component_pixel(*sensor, image_w, image_h);
-    s->irr_sensor_valid = true;
+  if (!B.irr_sensor_valid || memcmp(&B.irr_sensor, sensor, sizeof(mt_sensor)) != 0 || B.irr_w != image_w || B.irr_h != image_h) {
+    B.irr_sensor = *sensor; B.irr_w = image_w; B.irr_h = image_h;
+    B.irr_sensor_has = has_zero_component_pixel(*sensor, image_w, image_h);
+    B.irr_sensor_valid = true;
   }
-  L.new_irr = s->irr_sensor_has;
+  L.new_irr = B.irr_sensor_has;
   // Has the camera moved since the costs were measured?  Then forecast_kernel
   // re-projects them (radius 1 block; 2 when the origin moved too: parallax).
-  if (memcmp(&s->cost_sensor, sensor, sizeof(mt_sensor)) != 0) {
-    L.old_irr = has_zero_component_pixel(s->cost_sensor, image_w, image_h);
+  if (memcmp(&B.cost_sensor, sensor, sizeof(mt_sensor)) != 0) {
+    L.old_irr = has_zero_component_pixel(B.cost_sensor, image_w, image_h);
     L.reproject = 1;
-    L.radius = memcmp(s->cost_sensor.origin, sensor->origin, sizeof sensor->origin) != 0 ? 2 : 1;
+    L.radius = memcmp(B.cost_sensor.origin, sensor->origin, sizeof sensor->origin) != 0 ? 2 : 1;
     if (s->tune.v[MT_TUNE_FORECAST_RADIUS] >= 0.0) L.radius = (int)s->tune.v[MT_TUNE_FORECAST_RADIUS];
   }
-  if (!L.reproject && !L.from_map && s->forecasts_in_a_row > 0) {
+  if (!L.reproject && !L.from_map && B.forecasts_in_a_row > 0) {
     // swept (scripts/blend_sweep.py, state machine, 64 frames): 0 -> every other frame 6 % slower (mean 7.09 ms), 0.5 -> one
     // in three (7.03), 0.9 -> one in eight (7.01); a frozen forecast (1.0) repeats its frame time to 0.2 % (scripts/alternation.py)
     // (a running mean of the measurements first -- 1/2, 2/3, ... -- so that the first frames' costs, measured under a
     // guessed order, do not linger)
     const float cap = (float)s->tune.v[MT_TUNE_BLEND];
-    L.blend = std::min(cap, (float)s->forecasts_in_a_row / (float)(s->forecasts_in_a_row + 1));
+    L.blend = std::min(cap, (float)B.forecasts_in_a_row / (float)(B.forecasts_in_a_row + 1));
   }
   return MT_OK;
 }
 
 // The buffers a launch of plan L needs, and P's pointers to them
-int size_buffers(mt_scene *s, const LaunchPlan &L, const int32_t *d_list, size_t waves, RenderParams &P) {
+int size_buffers(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const int32_t *d_list, size_t waves, RenderParams &P) {
   const size_t n = P.n_items;
-  MT_TRY(s->d_item_cost.ensure(n * 4));
-  MT_TRY(s->d_item_forecast.ensure(n * 4));
-  MT_TRY(s->d_item_forms.ensure(n * 8));
-  MT_TRY(s->d_order_item.ensure(n * 64));
-  MT_TRY(s->d_order_sub.ensure(n * 16));
-  MT_TRY(s->d_item_form.ensure(n));
-  MT_TRY(s->d_item_unit.ensure(n * 4));
-  P.item_cost = s->d_item_cost;
-  P.item_forecast = s->d_item_forecast;
-  P.item_whole = s->d_item_forms;
-  P.item_qsum = s->d_item_forms + P.n_items;
+  MT_TRY(B.d_item_cost.ensure(n * 4));
+  MT_TRY(B.d_item_forecast.ensure(n * 4));
+  MT_TRY(B.d_item_forms.ensure(n * 8));
+  MT_TRY(B.d_order_item.ensure(n * 64));
+  MT_TRY(B.d_order_sub.ensure(n * 16));
+  MT_TRY(B.d_item_form.ensure(n));
+  MT_TRY(B.d_item_unit.ensure(n * 4));
+  P.item_cost = B.d_item_cost;
+  P.item_forecast = B.d_item_forecast;
+  P.item_whole = B.d_item_forms;
+  P.item_qsum = B.d_item_forms + P.n_items;
   if (s->tune.v[MT_TUNE_FORMS] == 0.0) P.item_whole = P.item_qsum = nullptr;
-  P.order_item = s->d_order_item;
-  P.order_sub = s->d_order_sub;
+  P.order_item = B.d_order_item;
+  P.order_sub = B.d_order_sub;
   P.n_work = s->d_work + 7;
   // the combined cost map of all ranks, if one was imported after the previous launch (else nullptr: own costs only)
-  P.cost_map = s->cost_map_for_launch == s->launches_timed ? s->d_cost_map.p : nullptr;
+  P.cost_map = B.cost_map_for_launch == B.launches ? s->d_cost_map.p : nullptr;
   P.cost_map_w = s->cost_map_w;
   P.cost_map_h = s->cost_map_h;
   if (L.from_map) P.item_whole = P.item_qsum = nullptr;  // (the two measured forms of a block are kept per slot)
   if (d_list != nullptr && P.n_tiles > 0) {
-    MT_TRY(s->d_tile_list.ensure((size_t)P.n_tiles * 4));
-    MT_TRY(s->d_tile_slot.ensure((size_t)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h) * 4));
-    P.tile_list = s->d_tile_list;
-    P.tile_slot = s->d_tile_slot;
+    MT_TRY(B.d_tile_list.ensure((size_t)P.n_tiles * 4));
+    MT_TRY(B.d_tile_slot.ensure((size_t)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h) * 4));
+    P.tile_list = B.d_tile_list;
+    P.tile_slot = B.d_tile_slot;
   }
   if (L.engine == 2 || L.engine == 3) {
     MT_TRY(s->d_pool.ensure(L.pool_stride * waves));
@@ -586,15 +613,15 @@ int size_buffers(mt_scene *s, const LaunchPlan &L, const int32_t *d_list, size_t
   if (n == 0) return MT_OK;  // (nothing is launched)
   P.order_ctl = s->d_order_ctl;
   P.order_whist = s->d_order_whist;
-  P.item_unit = s->d_item_unit;
+  P.item_unit = B.d_item_unit;
   // one work order per XCD: state-machine launches with a cost history only (the other engines keep the one order)
   // (measured and left out: first frames through the ray pool -- room 8.4 -> 8.9 ms, loft 19.7 -> 20.9: the probe's guess
   // balances the regions too roughly, and such a frame ends with its longest units either way --; the state machine's
   // part of hybrid launches, i.e. a rank's share of a frame -- mean of eight ranks' 4K shares 2.71 -> 2.77 ms)
   P.queues = (s->tune.v[MT_TUNE_XCD_QUEUES] != 0.0 && L.history && L.engine == 1) ? s->d_queues.p : nullptr;
   if (P.queues) {
-    MT_TRY(s->d_item_cell.ensure(n * 2));
-    P.item_cell = s->d_item_cell;
+    MT_TRY(B.d_item_cell.ensure(n * 2));
+    P.item_cell = B.d_item_cell;
   }
   // (the probe's grid follows the number of blocks: 16 of them per wave)
   const size_t block = (size_t)s->waves_per_block * 64;
@@ -611,9 +638,9 @@ void launch_order(const RenderParams &P, const ForecastArgs &fa, const OrderArgs
 }
 
 // The work order of a launch with a cost history, or of the ray pool's first frame (from probe_kernel's forecast)
-void launch_work_order(mt_scene *s, const LaunchPlan &L, const RenderParams &P, hipStream_t stream) {
+void launch_work_order(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const RenderParams &P, hipStream_t stream) {
   const double *tv = s->tune.v;
-  const int last = s->last_engine;  // (the engine that measured the costs)
+  const int last = B.last_engine;  // (the engine that measured the costs)
   const bool pool = L.engine == 2, hybrid = L.engine == 3;
   // blocks above this share of an even split are cut into quarters; a re-projected forecast (moving camera) is
   // cut more eagerly -- it is a neighbourhood maximum of stale costs (swept, scripts/quad_sweep.py: repeated frame
@@ -633,11 +660,11 @@ void launch_work_order(mt_scene *s, const LaunchPlan &L, const RenderParams &P, 
   // always have a history):
   //   pool  the cost words carry the ray pool's granularity
   //   w1    cost of a block's quarters over the block's whole cost, w2 the same for its cells
-  ForecastArgs fa{s->cost_sensor, L.reproject, L.radius,
+  ForecastArgs fa{B.cost_sensor, L.reproject, L.radius,
                   pool ? ((L.history && (last == 1 || last == 3)) ? 0 : 1) : (last == 2 ? 1 : 0),
                   pool ? ((L.history && last == 1) ? 1.7f : sp.piece_work[1]) : (last == 2 ? 1.1f : quad_work),
                   pool ? sp.piece_work[2] : 3.0f,
-                  16000u, L.blend, (L.history && last == 3) ? s->d_item_form.p : nullptr, (float)tv[MT_TUNE_HYBRID_WORK1],
+                  16000u, L.blend, (L.history && last == 3) ? B.d_item_form.p : nullptr, (float)tv[MT_TUNE_HYBRID_WORK1],
                   (float)tv[MT_TUNE_HYBRID_WORK2], (float)tv[MT_TUNE_FORECAST_STEP], (float)tv[MT_TUNE_SM_CELL_WORK],
                   L.old_irr, L.new_irr};
   OrderArgs oa{};
@@ -654,7 +681,7 @@ void launch_work_order(mt_scene *s, const LaunchPlan &L, const RenderParams &P, 
     oa.piece_time1 = (float)tv[MT_TUNE_POOL_PIECE_TIME1];
     oa.piece_time2 = (float)tv[MT_TUNE_POOL_PIECE_TIME2];
     oa.cell_factor = (float)tv[MT_TUNE_HYBRID_CELL_FACTOR];
-    oa.form_out = s->d_item_form;
+    oa.form_out = B.d_item_form;
     oa.starter_share = (float)tv[MT_TUNE_HYBRID_STARTER_SHARE];
     oa.max_starters = (unsigned)std::min(s->grid_blocks, (int)(0.25 * s->grid_blocks * s->waves_per_block));
     launch_order<1>(P, fa, oa, groups, stream);
@@ -676,12 +703,12 @@ void launch_work_order(mt_scene *s, const LaunchPlan &L, const RenderParams &P, 
 
 // Everything a launch puts on its stream.  Events: [0] -> [1] forecast / classification + work order; [1] -> [2] the
 // frame kernel.
-int launch_kernels(mt_scene *s, const LaunchPlan &L, const RenderParams &P, const int32_t *d_list, hipStream_t stream) {
+int launch_kernels(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const RenderParams &P, const int32_t *d_list, hipStream_t stream) {
   if (P.tile_list) {
     const int tiles_total = (int)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h);
-    HIP_TRY(hipMemcpyAsync(s->d_tile_list, d_list, (size_t)P.n_tiles * 4, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((tiles_total + 255) / 256), dim3(256), 0, stream, s->d_tile_list.p, P.n_tiles, s->d_tile_slot.p, tiles_total, 0);
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((P.n_tiles + 255) / 256), dim3(256), 0, stream, s->d_tile_list.p, P.n_tiles, s->d_tile_slot.p, tiles_total, 1);
+    HIP_TRY(hipMemcpyAsync(B.d_tile_list, d_list, (size_t)P.n_tiles * 4, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(tile_slot_kernel, dim3((tiles_total + 255) / 256), dim3(256), 0, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 0);
+    hipLaunchKernelGGL(tile_slot_kernel, dim3((P.n_tiles + 255) / 256), dim3(256), 0, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 1);
     HIP_TRY(hipGetLastError());
   }
   // (launches with a work order: order_forecast_kernel zeroes the counters on its way)
@@ -697,7 +724,7 @@ int launch_kernels(mt_scene *s, const LaunchPlan &L, const RenderParams &P, cons
   }
   HIP_TRY(hipEventRecord(ek[0], stream));
   // (the two measurements of a block belong to ONE camera, geometry and set of lights)
-  if (s->forecasts_in_a_row == 0) HIP_TRY(hipMemsetAsync(s->d_item_forms, 0, (size_t)P.n_items * 8, stream));
+  if (B.forecasts_in_a_row == 0) HIP_TRY(hipMemsetAsync(B.d_item_forms, 0, (size_t)P.n_items * 8, stream));
   const dim3 grid(s->grid_blocks), block(s->waves_per_block * 64);
   const LayoutKernels &k = kernels_of(s->deep);
   const int stats = s->stats_enabled ? 1 : 0;
@@ -705,7 +732,7 @@ int launch_kernels(mt_scene *s, const LaunchPlan &L, const RenderParams &P, cons
     hipLaunchKernelGGL(k.probe, dim3((4 * P.n_items + block.x - 1) / block.x), block, s->lds_bytes, stream, s->dev, P);
     HIP_TRY(hipGetLastError());
   }
-  if (L.engine == 2 || L.history) launch_work_order(s, L, P, stream);
+  if (L.engine == 2 || L.history) launch_work_order(s, B, L, P, stream);
   else hipLaunchKernelGGL(k.primary[stats], grid, block, s->lds_bytes, stream, s->dev, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ek[1], stream));
@@ -777,7 +804,9 @@ int debug_after_launch(mt_scene *s, const RenderParams &P, const unsigned long l
 int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int rx, int ry,
                   int rw, int rh, int tile_w, int tile_h, int first_tile, int tile_stride,
                   int n_tiles, int max_depth, uint8_t *d_rgb, mt_debug_px *d_debug,
-                  hipStream_t stream, const int32_t *d_list = nullptr, unsigned long long list_id = 0) {
+                  hipStream_t stream, const int32_t *d_list = nullptr, unsigned long long list_id = 0,
+                  ForecastBank *bank = nullptr) {
+  ForecastBank &B = bank ? *bank : s->bank0;
   if (max_depth < 0 || max_depth > MT_MAX_RECURSION) {
     return fail(MT_ERR_ARG, "max_depth %d outside [0, %d]", max_depth, MT_MAX_RECURSION);
   }
@@ -801,10 +830,10 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
   P.work_counter = s->d_work;
   const size_t waves = (size_t)s->grid_blocks * s->waves_per_block;
   LaunchPlan L;
-  MT_TRY(decide_launch(s, P, sensor, d_debug != nullptr, d_list, list_id, waves, L));
+  MT_TRY(decide_launch(s, B, P, sensor, d_debug != nullptr, d_list, list_id, waves, L));
   P.from_primary = L.history ? 0 : 1;
   P.from_map = L.from_map ? 1 : 0;
-  MT_TRY(size_buffers(s, L, d_list, waves, P));
+  MT_TRY(size_buffers(s, B, L, d_list, waves, P));
   if (P.n_items == 0) return MT_OK;
   Buf<unsigned long long> item_cycles;  // -DMT_DEBUG_KNOBS: MT_DEBUG_ITEM_CYCLES
   if (!s->dbg_item_cycles.empty()) {
@@ -812,16 +841,18 @@ int launch_render(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h
     HIP_TRY(hipMemset(item_cycles, 0, (size_t)P.n_items * 16 * 16 * 4));
     P.item_cycles = item_cycles;
   }
-  MT_TRY(launch_kernels(s, L, P, d_list, stream));
+  MT_TRY(launch_kernels(s, B, L, P, d_list, stream));
   // the scene's bookkeeping.  (A forecast made from the OTHER engine's costs -- the frame after a first frame -- does
   // not count: the next one starts the running mean with this engine's own measurement.)
-  s->forecasts_in_a_row = (L.history && !L.reproject && !L.from_map && s->last_engine == L.engine) ? s->forecasts_in_a_row + 1 : 0;
+  B.forecasts_in_a_row = (L.history && !L.reproject && !L.from_map && B.last_engine == L.engine) ? B.forecasts_in_a_row + 1 : 0;
   s->launches_timed++;
-  s->last_P = P;
-  s->last_P_valid = true;
-  s->cost_signature = (d_list != nullptr && list_id == 0) ? 0 : L.sig;  // the costs now in d_item_cost belong to this geometry and engine
-  s->last_engine = L.engine;
-  s->cost_sensor = *sensor;
+  B.launches++;
+  B.last_history = L.history;
+  B.last_P = P;
+  B.last_P_valid = true;
+  B.cost_signature = (d_list != nullptr && list_id == 0) ? 0 : L.sig;  // the costs now in d_item_cost belong to this geometry and engine
+  B.last_engine = L.engine;
+  B.cost_sensor = *sensor;
   return debug_after_launch(s, P, item_cycles, stream);
 }
 
@@ -1020,6 +1051,9 @@ void mt_scene_destroy(mt_scene *s) {
   if (s->multi_done) (void)hipEventDestroy(s->multi_done);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
+  for (hipEvent_t e : s->ev_ad) {
+    if (e) (void)hipEventDestroy(e);
+  }
   for (auto &tri : s->ev_k) {
     for (hipEvent_t e : tri) {
       if (e) (void)hipEventDestroy(e);
@@ -1495,7 +1529,8 @@ int mt_scene_set_lights(mt_scene *s, const mt_light *lights, int n) {
       (n && memcmp(s->lights_host.data(), lights, (size_t)n * sizeof(mt_light)) != 0)) {
     if (n) HIP_TRY(hipMemcpy(s->d_lights, lights, (size_t)n * sizeof(mt_light), hipMemcpyHostToDevice));
     s->lights_host.assign(lights, lights + n);
-    s->forecasts_in_a_row = 0;
+    s->bank0.forecasts_in_a_row = 0;
+    if (s->bank1) s->bank1->forecasts_in_a_row = 0;
   }
   s->dev.lights = s->d_lights;
   s->dev.n_lights = n;
@@ -1511,7 +1546,7 @@ int mt_scene_set_traversal_mode(mt_scene *s, int mode) {
 int mt_scene_set_scheduling(mt_scene *s, int use_cost_history) {
   if (!s || (use_cost_history != 0 && use_cost_history != 1)) return fail(MT_ERR_ARG, "bad scheduling argument");
   s->use_history = use_cost_history != 0;
-  s->cost_signature = 0;
+  s->forget_histories();
   return MT_OK;
 }
 
@@ -1524,7 +1559,7 @@ int mt_scene_set_stats(mt_scene *s, int enabled) {
 int mt_scene_set_engine(mt_scene *s, int engine) {
   if (!s || engine < 0 || engine > 3) return fail(MT_ERR_ARG, "engine must be 0 (automatic), 1, 2 or 3");
   s->engine = engine;
-  s->cost_signature = 0;
+  s->forget_histories();
   return MT_OK;
 }
 
@@ -1571,7 +1606,7 @@ int mt_scene_set_tuning(mt_scene *s, int knob, double value) {
     default: break;  // switches: any finite value (0 / non-zero)
   }
   s->tune.v[knob] = value;
-  s->cost_signature = 0;  // other constants, other order: start from a first frame
+  s->forget_histories();  // other constants, other order: start from a first frame
   if (knob == MT_TUNE_PACKED_STACK || knob == MT_TUNE_BLOCKS_PER_CU || knob == MT_TUNE_DEEP_LAYOUT) {
     if (knob == MT_TUNE_PACKED_STACK) s->dev.pack_shift = value != 0.0 ? pack_shift_for(s->dev.n_tris, s->dev.n_nodes) : 0;
     HIP_TRY(hipSetDevice(s->device));
@@ -1582,19 +1617,19 @@ int mt_scene_set_tuning(mt_scene *s, int knob, double value) {
 
 int mt_scene_export_costs_device(mt_scene *s, void *d_map, int map_w, int map_h, void *stream) {
   if (!s || !d_map || map_w <= 0 || map_h <= 0) return fail(MT_ERR_ARG, "bad cost map arguments");
-  if (!s->last_P_valid) return fail(MT_ERR_ARG, "no launch to export the costs of");
-  const RenderParams &P = s->last_P;
+  if (!s->bank0.last_P_valid) return fail(MT_ERR_ARG, "no launch to export the costs of");
+  const RenderParams &P = s->bank0.last_P;
   if (map_w < (P.image_w + 7) / 8 || map_h < (P.image_h + 7) / 8 || (P.tile_w & 7) || (P.tile_h & 7) || (P.region_x & 7) || (P.region_y & 7)) {
     return fail(MT_ERR_ARG, "cost map smaller than the image's 8x8 blocks, or tiles not on the 8-pixel grid");
   }
   HIP_TRY(hipSetDevice(s->device));
   if (P.n_items == 0) return MT_OK;
   const double *tv = s->tune.v;
-  const bool hy = s->last_engine == 3;
-  hipLaunchKernelGGL(export_costs_kernel, dim3((P.n_items + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, s->last_engine,
+  const bool hy = s->bank0.last_engine == 3;
+  hipLaunchKernelGGL(export_costs_kernel, dim3((P.n_items + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, s->bank0.last_engine,
                      (float)(hy ? tv[MT_TUNE_HYBRID_WORK1] : tv[MT_TUNE_POOL_PIECE_WORK1]),
                      (float)(hy ? tv[MT_TUNE_HYBRID_WORK2] : tv[MT_TUNE_POOL_PIECE_WORK2]), (float)tv[MT_TUNE_SM_CELL_WORK],
-                     (const unsigned char *)s->d_item_form, (unsigned *)d_map, map_w, map_h);
+                     (const unsigned char *)s->bank0.d_item_form, (unsigned *)d_map, map_w, map_h);
   HIP_TRY(hipGetLastError());
   return MT_OK;
 }
@@ -1607,7 +1642,7 @@ int mt_scene_import_costs_device(mt_scene *s, const void *d_map, int map_w, int 
   HIP_TRY(hipMemcpyAsync(s->d_cost_map, d_map, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   s->cost_map_w = map_w;
   s->cost_map_h = map_h;
-  s->cost_map_for_launch = s->launches_timed;  // valid for the NEXT launch only
+  s->bank0.cost_map_for_launch = s->bank0.launches;  // valid for the NEXT launch only
   return MT_OK;
 }
 
@@ -1881,6 +1916,188 @@ int mt_resolve_tiles_device(mt_scene *s, int image_w, int image_h, int tile_w, i
   return launch_resolve(ss, image_w, image_h, tile_w, tile_h, d_list ? 0 : first_tile, d_list ? 1 : tile_stride,
                         (const int32_t *)d_list, n_tiles, (const uint8_t *)d_samples, (uint8_t *)d_tiles,
                         (hipStream_t)stream);
+}
+
+// ---- adaptive supersampling (mt_adaptive.h): the plain launch, the blocks whose pixels differ, a tile-list launch of
+// those blocks' samples on the scene's second forecast bank, the resolve over the plain frame ----
+namespace {
+
+// the blocks of a chunk (include/mythtracer_hip.h) and the kernels' arguments for them
+RefineArgs refine_args(int image_w, int chunk_x, int chunk_y, int chunk_w, int chunk_h, int threshold) {
+  RefineArgs A{};
+  A.chunk_x = chunk_x; A.chunk_y = chunk_y; A.chunk_w = chunk_w; A.chunk_h = chunk_h;
+  A.tiles_x = (image_w + 7) / 8;
+  A.mask_x0 = chunk_x / 8;
+  A.mask_y0 = chunk_y / 8;
+  A.mask_w = (chunk_x + chunk_w - 1) / 8 - A.mask_x0 + 1;
+  A.mask_h = (chunk_y + chunk_h - 1) / 8 - A.mask_y0 + 1;
+  A.threshold = threshold;
+  return A;
+}
+
+int check_threshold(int threshold) {
+  if (threshold < 0 || threshold > 255) return fail(MT_ERR_ARG, "threshold %d outside [0, 255]", threshold);
+  return MT_OK;
+}
+
+int check_image_size(int image_w, int image_h) {
+  if (image_w <= 0 || image_h <= 0 || image_w > 100000 || image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d out of range", image_w, image_h);
+  }
+  return MT_OK;
+}
+
+// refine_mask_kernel + refine_compact_kernel: flags in s->d_ad_flags (and d_mask), the list in d_list, count and hash
+// in s->d_ad_ctl (the count in d_count too)
+int launch_refine_mask(mt_scene *s, RefineArgs A, const uint8_t *d_rgb, uint8_t *d_mask, int32_t *d_list,
+                       uint32_t *d_count, hipStream_t stream) {
+  const size_t n_blocks = (size_t)A.mask_w * (size_t)A.mask_h;
+  MT_TRY(s->d_ad_flags.ensure(n_blocks));
+  MT_TRY(s->d_ad_ctl.ensure(sizeof(RefineCtl)));
+  A.rgb = d_rgb;
+  A.flags = s->d_ad_flags;
+  A.mask_out = d_mask;
+  const unsigned grid = (unsigned)std::min<size_t>((n_blocks + 3) / 4, 8192);
+  hipLaunchKernelGGL(refine_mask_kernel, dim3(grid), dim3(256), 0, stream, A);
+  hipLaunchKernelGGL(refine_compact_kernel, dim3(1), dim3(kRefineCompactThreads), 0, stream, A, d_list, d_count, s->d_ad_ctl.p);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+int launch_refine_resolve(int ss, const RefineArgs &M, int image_w, int image_h, const int32_t *d_list, int n_slots,
+                          const uint8_t *d_samples, uint8_t *d_rgb, hipStream_t stream) {
+  RefineResolveArgs A{};
+  A.image_w = image_w; A.image_h = image_h;
+  A.chunk_x = M.chunk_x; A.chunk_y = M.chunk_y; A.chunk_w = M.chunk_w; A.chunk_h = M.chunk_h;
+  A.tiles_x = M.tiles_x;
+  A.n_slots = n_slots;
+  A.list = d_list;
+  A.samples = d_samples;
+  A.rgb = d_rgb;
+  const dim3 grid((unsigned)std::min((n_slots + 3) / 4, 8192)), block(256);
+  switch (ss) {
+    case 2: hipLaunchKernelGGL(refine_resolve_kernel<2>, grid, block, 0, stream, A); break;
+    case 3: hipLaunchKernelGGL(refine_resolve_kernel<3>, grid, block, 0, stream, A); break;
+    case 4: hipLaunchKernelGGL(refine_resolve_kernel<4>, grid, block, 0, stream, A); break;
+    default: return fail(MT_ERR_ARG, "ss %d has no resolve kernel", ss);
+  }
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+// The checks of the adaptive calls, before any device call: ss and the sample grid, threshold, the output pointer,
+// image and chunk, the scene, the sensors.
+int check_adaptive_args(const mt_scene *s, const mt_sensor *sensor, const mt_sensor *sensor_ss, int image_w, int image_h,
+                        int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int threshold, const void *rgb,
+                        const char *rgb_name) {
+  MT_TRY(check_ss(ss, image_w, image_h));
+  MT_TRY(check_threshold(threshold));
+  if (!rgb) return fail(MT_ERR_ARG, "%s is NULL", rgb_name);
+  MT_TRY(check_image_size(image_w, image_h));
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (!sensor) return fail(MT_ERR_ARG, "sensor is NULL");
+  if (ss > 1 && !sensor_ss) return fail(MT_ERR_ARG, "sensor_ss is NULL (the sensor of the sample grid, needed with ss > 1)");
+  return MT_OK;
+}
+
+// The composed call on checked arguments.  *synced: events ev_ad[0] .. ev_ad[1] enclose the stream's idle time.
+int render_adaptive(mt_scene *s, const mt_sensor *sensor, const mt_sensor *sensor_ss, int image_w, int image_h,
+                    int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int threshold, int max_depth,
+                    uint8_t *d_rgb, uint8_t *d_mask, mt_adaptive_info *info, hipStream_t stream, bool *synced) {
+  *synced = false;
+  const RefineArgs M = refine_args(image_w, chunk_x, chunk_y, chunk_w, chunk_h, threshold);
+  const size_t n_blocks = (size_t)M.mask_w * (size_t)M.mask_h;
+  mt_adaptive_info I{(int32_t)n_blocks, 0, 0, 0};
+  MT_TRY(launch_render(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, chunk_w, chunk_h, 0, 1, 1,
+                       max_depth, d_rgb, nullptr, stream));
+  I.plain_history = s->bank0.last_history ? 1 : 0;
+  if (ss == 1) {  // the plain call
+    if (d_mask) HIP_TRY(hipMemsetAsync(d_mask, 0, n_blocks, stream));
+    if (info) *info = I;
+    return MT_OK;
+  }
+  MT_TRY(s->d_ad_list.ensure(n_blocks * sizeof(int32_t)));
+  MT_TRY(s->h_ad_ctl.ensure(sizeof(RefineCtl)));
+  for (hipEvent_t &e : s->ev_ad) {
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  }
+  MT_TRY(launch_refine_mask(s, M, d_rgb, d_mask, s->d_ad_list, nullptr, stream));
+  // how many blocks, and which list: the one synchronisation of the call (a launch sizes its buffers on the host)
+  HIP_TRY(hipMemcpyAsync(s->h_ad_ctl, s->d_ad_ctl, sizeof(RefineCtl), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipEventRecord(s->ev_ad[0], stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipEventRecord(s->ev_ad[1], stream));
+  *synced = true;
+  const RefineCtl ctl = *s->h_ad_ctl.p;
+  if ((size_t)ctl.count > n_blocks) return fail(MT_ERR_INTERNAL, "%u refined blocks of %zu: kernel logic error", ctl.count, n_blocks);
+  I.n_refined = (int32_t)ctl.count;
+  if (ctl.count > 0) {
+    MT_TRY(ensure_samples(s, (size_t)ctl.count * 64 * 3 * ss * ss));
+    if (!s->bank1) s->bank1.reset(new ForecastBank());
+    MT_TRY(launch_render(s, sensor_ss, ss * image_w, ss * image_h, 0, 0, ss * image_w, ss * image_h, 8 * ss, 8 * ss, 0, 1,
+                         (int)ctl.count, max_depth, s->d_samples, nullptr, stream, s->d_ad_list,
+                         (unsigned long long)ctl.hash | 1ull, s->bank1.get()));
+    I.refine_history = s->bank1->last_history ? 1 : 0;
+    MT_TRY(launch_refine_resolve(ss, M, image_w, image_h, s->d_ad_list, (int)ctl.count, s->d_samples, d_rgb, stream));
+  }
+  if (info) *info = I;
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_refine_mask_device(mt_scene *s, int image_w, int image_h, int chunk_x, int chunk_y, int chunk_w, int chunk_h,
+                          int threshold, const void *d_rgb, void *d_mask, void *d_list, void *d_count, void *stream) {
+  MT_TRY(check_threshold(threshold));
+  if (!d_rgb || !d_list || !d_count) return fail(MT_ERR_ARG, "d_rgb, d_list or d_count is NULL");
+  MT_TRY(check_image_size(image_w, image_h));
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_refine_mask(s, refine_args(image_w, chunk_x, chunk_y, chunk_w, chunk_h, threshold), (const uint8_t *)d_rgb,
+                            (uint8_t *)d_mask, (int32_t *)d_list, (uint32_t *)d_count, (hipStream_t)stream);
+}
+
+int mt_render_chunk_adaptive_device(mt_scene *s, const mt_sensor *sensor, const mt_sensor *sensor_ss, int image_w,
+                                    int image_h, int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int threshold,
+                                    int max_depth, void *d_rgb, void *d_mask, mt_adaptive_info *info, void *stream) {
+  MT_TRY(check_adaptive_args(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
+                             d_rgb, "d_rgb"));
+  HIP_TRY(hipSetDevice(s->device));
+  bool synced = false;
+  return render_adaptive(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
+                         max_depth, (uint8_t *)d_rgb, (uint8_t *)d_mask, info, (hipStream_t)stream, &synced);
+}
+
+int mt_render_chunk_adaptive(mt_scene *s, const mt_sensor *sensor, const mt_sensor *sensor_ss, int image_w, int image_h,
+                             int chunk_x, int chunk_y, int chunk_w, int chunk_h, int ss, int threshold, int max_depth,
+                             uint8_t *out_rgb, uint8_t *out_mask, mt_adaptive_info *info, mt_stats *stats) {
+  MT_TRY(check_adaptive_args(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
+                             out_rgb, "out_rgb"));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * chunk_h;
+  const RefineArgs M = refine_args(image_w, chunk_x, chunk_y, chunk_w, chunk_h, threshold);
+  const size_t n_blocks = (size_t)M.mask_w * (size_t)M.mask_h;
+  hipStream_t stream = nullptr;
+  MT_TRY(begin_host_chunk(s, npx, false, stream));
+  if (out_mask) MT_TRY(s->d_ad_mask.ensure(n_blocks));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  bool synced = false;
+  const int rc = render_adaptive(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
+                                 max_depth, s->d_rgb, out_mask ? s->d_ad_mask.p : nullptr, info, stream, &synced);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, s->d_ad_mask, n_blocks, hipMemcpyDeviceToHost, stream));
+  MT_TRY(finish_host_chunk(s, npx, out_rgb, nullptr, stats, w0, stream));
+  if (stats && synced) {  // (the stream idled between these two while the host read the count)
+    float idle = 0;
+    HIP_TRY(hipEventElapsedTime(&idle, s->ev_ad[0], s->ev_ad[1]));
+    stats->kernel_ms = std::max(0.0, stats->kernel_ms - (double)idle);
+  }
+  return MT_OK;
 }
 
 // ---- the primary-hit G-buffer (mt_gbuffer.h): one kernel next to the frame kernels.  Nothing here reads or writes

@@ -113,6 +113,15 @@ class MythTracer {
   // debug record belongs to a ray, not to a mean) and, for the W x H overload, s > 1 with more than one device
   // (SetDevices): a supersampled frame is rendered on one device, never silently so when several were asked for.
   void SetSupersampling(int s) { supersampling_ = s; }
+  // Adaptive supersampling (mt_render_chunk_adaptive): one ray per pixel, then s x s samples in the 8 x 8 blocks of
+  // the image where neighbouring pixels differ by more than `threshold` (0 .. 255) in a channel.  s <= 1 switches it
+  // off.  Independent of SetSupersampling; with both set, adaptive wins.  Refused like SetSupersampling's frames:
+  // with output_debug, and by the W x H overload after SetDevices with several devices.  A chunk's result depends on
+  // the chunk's borders (pairs of pixels across them are not looked at).
+  void SetAdaptiveSupersampling(int s, int threshold) {
+    adaptive_ss_ = s > 1 ? s : 1;
+    adaptive_threshold_ = threshold;
+  }
   // The primary-hit G-buffer of a W x H frame, or of chunk->chunk_* (its camera and image size; output_bitmap and
   // output_debug are not touched).  No reference counterpart: the reference returns a colour and PerPixelDebugInfo.
   // One kernel launch next to the frame's (mt_render_gbuffer); the frames' cost history is left alone.
@@ -164,6 +173,7 @@ class MythTracer {
   void DropDeviceScenes();
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
+  int adaptive_ss_ = 1, adaptive_threshold_ = 16;
   bool CheckSupersampling(int image_width, int image_height, bool on_all_devices);
   bool quiet_ = false;
   bool collect_stats_ = true;

@@ -124,6 +124,9 @@ void mth_set_lights(void* p, const double* l, int n) {
 
 void mth_set_max_level(void* p, int level) { static_cast<Handle*>(p)->mt.SetMaxRecursionLevel(level); }
 void mth_set_supersampling(void* p, int s) { static_cast<Handle*>(p)->mt.SetSupersampling(s); }
+void mth_set_adaptive_supersampling(void* p, int s, int threshold) {
+  static_cast<Handle*>(p)->mt.SetAdaptiveSupersampling(s, threshold);
+}
 
 // host-only: builds the octree (no GPU needed)
 void mth_finalize(void* p) { static_cast<Handle*>(p)->mt.GetScene()->tree.Finalize(); }

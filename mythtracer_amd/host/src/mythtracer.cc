@@ -207,11 +207,16 @@ bool MythTracer::Prepare() {
 
 // The supersampling factor is checked before anything touches a device: a caller without one sees this message too.
 bool MythTracer::CheckSupersampling(int image_width, int image_height, bool on_all_devices) {
-  const int s = supersampling_;
+  // (SetAdaptiveSupersampling wins over SetSupersampling)
+  const bool adaptive = adaptive_ss_ > 1;
+  const int s = adaptive ? adaptive_ss_ : supersampling_;
+  const std::string what = adaptive ? "adaptive supersampling" : "supersampling";
   if (s < 1 || s > 4) {
-    error_ = "supersampling factor " + std::to_string(s) + " outside 1 .. 4";
+    error_ = what + " factor " + std::to_string(s) + " outside 1 .. 4";
+  } else if (adaptive && (adaptive_threshold_ < 0 || adaptive_threshold_ > 255)) {
+    error_ = "adaptive supersampling threshold " + std::to_string(adaptive_threshold_) + " outside 0 .. 255";
   } else if (s > 1 && on_all_devices && devices_.size() > 1) {
-    error_ = "supersampling is not supported with several devices (SetDevices)";
+    error_ = what + " is not supported with several devices (SetDevices)";
   } else if (s > 1 && (image_width <= 0 || image_height <= 0 || image_width > 100000 / s || image_height > 100000 / s)) {
     error_ = "image size " + std::to_string(image_width) + "x" + std::to_string(image_height) + " out of range for supersampling factor " + std::to_string(s);
   } else {
@@ -281,9 +286,11 @@ bool MythTracer::RayTrace(int image_width, int image_height, Camera* camera,
 
 bool MythTracer::RayTrace(WorkChunk* chunk) {
   if (!CheckSupersampling(chunk->image_width, chunk->image_height, false)) return false;
-  const int ss = supersampling_;
+  const bool adaptive = adaptive_ss_ > 1;
+  const int ss = adaptive ? adaptive_ss_ : supersampling_;
   if (ss > 1 && !chunk->output_debug.empty()) {
-    error_ = "WorkChunk::output_debug is not available with supersampling";
+    error_ = adaptive ? "WorkChunk::output_debug is not available with adaptive supersampling"
+                      : "WorkChunk::output_debug is not available with supersampling";
     fprintf(stderr, "error: %s\n", error_.c_str());
     return false;
   }
@@ -306,6 +313,13 @@ bool MythTracer::RayTrace(WorkChunk* chunk) {
   memcpy(ms.start_point, sensor.StartPoint().v, 24);
   memcpy(ms.delta_scanline, sensor.DeltaScanline().v, 24);
   memcpy(ms.delta_pixel, sensor.DeltaPixel().v, 24);
+  mt_sensor ms1 = ms;  // adaptive: the sensor of the output grid for the plain pass, `ms` for the refined blocks
+  if (adaptive) {
+    const Camera::Sensor plain = chunk->camera.GetSensor(chunk->image_width, chunk->image_height);
+    memcpy(ms1.start_point, plain.StartPoint().v, 24);
+    memcpy(ms1.delta_scanline, plain.DeltaScanline().v, 24);
+    memcpy(ms1.delta_pixel, plain.DeltaPixel().v, 24);
+  }
 
   const size_t npx = (size_t)chunk->chunk_width * (size_t)chunk->chunk_height;
   if (chunk->output_bitmap.size() < npx * 3) {
@@ -325,7 +339,12 @@ bool MythTracer::RayTrace(WorkChunk* chunk) {
   mt_stats st;
   memset(&st, 0, sizeof st);
   (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
-  const int rc = ss > 1 ? mt_render_chunk_ss(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,
+  const int rc = adaptive ? mt_render_chunk_adaptive(dev_, &ms1, &ms, chunk->image_width, chunk->image_height,
+                                                     chunk->chunk_x, chunk->chunk_y, chunk->chunk_width,
+                                                     chunk->chunk_height, ss, adaptive_threshold_, max_level_,
+                                                     chunk->output_bitmap.data(), nullptr, nullptr,
+                                                     collect_stats_ ? &st : nullptr)
+           : ss > 1 ? mt_render_chunk_ss(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,
                                              chunk->chunk_y, chunk->chunk_width, chunk->chunk_height, ss, max_level_,
                                              chunk->output_bitmap.data(), collect_stats_ ? &st : nullptr)
                         : mt_render_chunk(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x,

@@ -116,3 +116,54 @@ def resolve_ss(samples: np.ndarray, s: int) -> np.ndarray:
     n = s * s
     total = a.reshape(sh // s, s, sw // s, s, c).astype(np.uint32).sum(axis=(1, 3))
     return ((total + n // 2) // n).astype(np.uint8)
+
+
+# ---- adaptive supersampling (include/mythtracer_hip.h, mt_render_chunk_adaptive ff.; csrc/mt_adaptive.h)
+def chunk_blocks(chunk):
+    """The blocks of a chunk -- those of the IMAGE's 8 x 8 grid that hold a chunk pixel: (mask_x0, mask_y0, mask_w,
+    mask_h)."""
+    cx, cy, cw, ch = chunk
+    x0, y0 = cx // 8, cy // 8
+    return x0, y0, (cx + cw - 1) // 8 - x0 + 1, (cy + ch - 1) // 8 - y0 + 1
+
+
+def refine_mask(plain_rgb: np.ndarray, image_w: int, image_h: int, chunk=None, threshold: int = 16):
+    """Which blocks of a chunk does an adaptive frame supersample?  plain_rgb = the chunk's plain frame, uint8
+    [chunk_h][chunk_w][3].  Two horizontal or vertical neighbours inside the chunk are contrasty when they differ by
+    more than `threshold` in a channel; a block is refined iff a pixel of a contrasty pair lies in it.  Returns (mask
+    bool [mask_h][mask_w], the refined blocks' tile numbers by * ceil(image_w / 8) + bx, int32 ascending)."""
+    cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+    f = np.asarray(plain_rgb)
+    if f.dtype != np.uint8 or f.shape != (ch, cw, 3):
+        raise ValueError("plain_rgb must be the chunk's uint8 [%d][%d][3] bitmap" % (ch, cw))
+    if not 0 <= int(threshold) <= 255:
+        raise ValueError("threshold %r outside 0 .. 255" % (threshold,))
+    f = f.astype(np.int16)
+    hot = np.zeros((ch, cw), dtype=bool)  # pixels of contrasty pairs
+    h = np.abs(f[:, 1:] - f[:, :-1]).max(axis=2) > int(threshold)
+    hot[:, 1:] |= h
+    hot[:, :-1] |= h
+    v = np.abs(f[1:] - f[:-1]).max(axis=2) > int(threshold)
+    hot[1:] |= v
+    hot[:-1] |= v
+    x0, y0, mw, mh = chunk_blocks((cx, cy, cw, ch))
+    mask = np.zeros((mh, mw), dtype=bool)
+    ys, xs = np.nonzero(hot)
+    mask[(ys + cy) // 8 - y0, (xs + cx) // 8 - x0] = True
+    my, mx = np.nonzero(mask)
+    tiles = ((my + y0) * ((image_w + 7) // 8) + mx + x0).astype(np.int32)
+    return mask, tiles
+
+
+def compose_adaptive(plain_rgb: np.ndarray, ss_rgb: np.ndarray, mask: np.ndarray, chunk) -> np.ndarray:
+    """The adaptive frame of a chunk: the supersampled frame's bytes where the pixel's block is refined, the plain
+    frame's elsewhere.  mask as refine_mask returns it for `chunk`."""
+    cx, cy, cw, ch = chunk
+    x0, y0, mw, mh = chunk_blocks(chunk)
+    m = np.asarray(mask, dtype=bool)
+    if m.shape != (mh, mw):
+        raise ValueError("mask must be [%d][%d] for this chunk" % (mh, mw))
+    by = (np.arange(ch) + cy) // 8 - y0
+    bx = (np.arange(cw) + cx) // 8 - x0
+    px = m[by[:, None], bx[None, :]]
+    return np.where(px[:, :, None], np.asarray(ss_rgb), np.asarray(plain_rgb)).astype(np.uint8)
