@@ -464,6 +464,101 @@ int mt_update_lightbuffer_device(mt_scene *scene, int chunk_w, int chunk_h,
                                  const mt_gbuffer *d_gb, const int32_t *light_idx, int n_idx,
                                  const mt_lightbuffer *d_lb, void *stream);
 
+/* The ray-tree buffer of a chunk: the whole call tree of TraceRayWorker (mythtracer.cc:13-228) for every pixel, traced
+ * once and kept in HBM, and the relight pass over it -- the FULL-DEPTH frame under edited light colours without tracing
+ * a ray.  Nothing in the shape of the recursion depends on a light's colour: whether a call spawns a reflected child
+ * (:181-184) or a refracted one (:192) depends on level, the material's reflectance and transparency,
+ * current_reflection_coef and in_object; the rays, their hits and every shadow loop depend on geometry, materials and
+ * the lights' POSITIONS.  (No reference counterpart.)
+ *
+ * Layers, for a given max_depth (which stands where the reference has MAX_RECURSION_LEVEL):
+ *   layer 0      one ray per pixel of the chunk: Sensor::GetRay, level 0, in_object = false, coef = 1.0
+ *   layer k + 1  the child rays of layer k's rays: the reflected ray of :68-74 (origin = point + direction * 0.0001, the
+ *                direction NOT normalised) where :181-184 holds, the refracted ray of :208-218 where :192 holds; ordered
+ *                by parent index, a parent's reflected ray before its refracted one; in_object and coef as the recursive
+ *                call receives them (:186-187, :222-223)
+ * A miss and a hit on a triangle without a material have no children.  Layers end before the first empty one: there are
+ * at most max_depth + 1, and a layer's rays are the calls of TraceRayWorker at that level.
+ * Order of layer 0: the 8x8-pixel blocks of the CHUNK (block (0, 0) at the chunk's corner) in row-major order; within a
+ * block its pixels in row-major order; a block cut by the chunk's right or bottom edge holds only its pixels, so the list
+ * has chunk_w * chunk_h entries and no holes.  Chunk pixel (x, y), with bw = min(8, chunk_w - 8 (x / 8)) and
+ * bh = min(8, chunk_h - 8 (y / 8)), has index  8 (y / 8) chunk_w + 8 (x / 8) bh + (y % 8) bw + x % 8.  A fixed function
+ * of (chunk_w, chunk_h); mythtracer_amd/tiling.py restates it (raytree_layer0_order).
+ *
+ * Per ray of a layer of n rays (mt_raytree_layer: the planes mt_raytree_read_layer copies out, each pointer nullable):
+ *   ray        [n][6] doubles: origin and direction exactly as handed to OctTree::IntersectRay
+ *   in_object  [n] bytes 0 / 1;   coef  [n] doubles
+ *   point, normal, albedo  [n][3] doubles, material [n] int32: mt_render_gbuffer's planes for that ray, with its bits
+ *              (normal unflipped; a miss: NaN / -1; no material: albedo NaN, material -1)
+ *   power      [n_lights][n][3] doubles, in_shadow [n_lights][n] bytes: mt_render_lightbuffer's meaning and its
+ *              NaN / 255 rule for rays that never enter the light loop
+ *   child_refl, child_refr  [n] int32: index into layer k + 1, -1 = none
+ *   pixel      [n] int32, LAYER 0 ONLY (MT_ERR_ARG for another layer): the ray's chunk-local row-major pixel index
+ *
+ * mt_raytree_create traces the tree under the scene's CURRENT lights (mt_scene_set_lights; zero lights is valid: the
+ * light planes are empty) and returns it, or NULL with mt_last_error set.  The tree is opaque and lives on the scene's
+ * GPU.  The call is synchronous and makes one host round trip per layer: a layer's child count sizes the next one.
+ * stats (nullable): the sums over all layers -- rays_primary, rays_secondary, rays_shadow and shaded_hits equal what
+ * mt_render_chunk reports for the same frame --, kernel_ms = device time from the first to the last kernel (the round
+ * trips between the layers included), total_ms = wall time.  A layer of 2^31 rays or more is MT_ERR_UNSUPPORTED; an
+ * allocation that does not fit is MT_ERR_NOMEM (never a shallower tree); a tripped loop bound is MT_ERR_INTERNAL.
+ * mt_raytree_destroy (NULL is fine) must be called BEFORE the scene's mt_scene_destroy; trees of one scene may be
+ * destroyed in any order.  mt_raytree_info fills an mt_raytree_desc: layers, lights, chunk, depth, rays per layer, bytes.
+ *
+ * mt_raytree_shade shades the layers bottom-up, one thread per ray and one launch per layer.  Per ray: colour = the
+ * direct term of :38-177 from the stored planes, the stored ray direction and the CALLER's lights -- mt_shade_direct's
+ * arithmetic, grey for material == -1 and black for a miss included --; where child_refl >= 0
+ * colour += colour[child_refl] * reflectance (:185-188); where child_refr >= 0
+ * colour += colour[child_refr] * transmission_filter * transparency, associated as :220-224 writes it; layer 0 ends in
+ * V3DtoRGB (:235-241), written to the pixel's place of the chunk-local row-major bitmap.  Material constants come from
+ * the scene.  `lights` is a HOST array in both forms; the scene's own lights are neither read nor changed.  They may
+ * differ from the lights the tree was made with in ambient, diffuse and specular ONLY; of that, the count is checked
+ * (MT_ERR_ARG), the positions cannot be.
+ * CONTRACT: for lights whose count and positions are those the tree was made with, the bitmap is byte-identical to
+ * mt_render_chunk(..., max_depth, ...) after mt_scene_set_lights(lights, n_lights), for the same scene, sensor and chunk.
+ *   mt_raytree_shade: out_rgb = chunk_w * chunk_h * 3 host bytes; stats (nullable): kernel_ms = the layers' launches
+ *     by HIP events, total_ms = wall time of the call; the work counters are zero (no ray is traced).
+ *   mt_raytree_shade_device: d_rgb on the scene's GPU; asynchronous on `stream`.  Up to 8 lights travel with the
+ *     launches; a longer array is copied by the stream into a buffer the scene owns and must stay unchanged until the
+ *     stream has reached the call.
+ * The per-ray colours are scratch of the TREE: one shade may be in flight per tree.  All calls share the scene's work
+ * counter, statistics and light buffer with their siblings: one call in flight per scene.  Like the G-buffer and
+ * light-buffer calls they leave everything a frame launch decides by -- cost history, engine choice, forecasts,
+ * mt_scene_kernel_times -- alone.
+ *
+ * Argument checks come before any device call, in this order.  mt_raytree_create: image size and chunk
+ * (mt_render_chunk's limits and messages), scene, sensor, max_depth in 0 .. MT_MAX_RECURSION.  mt_raytree_info: tree,
+ * out.  mt_raytree_read_layer: tree, layer in 0 .. n_layers - 1, out, `pixel` for a layer other than 0.
+ * mt_raytree_shade[_device]: the bitmap, tree, then the lights (n_lights < 0 or a NULL array of n_lights > 0; n_lights
+ * unequal to the tree's). */
+typedef struct mt_raytree mt_raytree;
+typedef struct mt_raytree_desc {
+  int32_t n_layers, n_lights;
+  int32_t image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h;
+  int32_t max_depth, reserved;
+  int64_t n_rays[MT_MAX_RECURSION + 1];   /* per layer; 0 from n_layers on */
+  double trace_ms[MT_MAX_RECURSION + 1];  /* per layer: its tracing kernel at creation, by HIP events */
+  uint64_t bytes;                          /* HBM held by the tree */
+} mt_raytree_desc;
+typedef struct mt_raytree_layer {
+  double *ray;
+  uint8_t *in_object;
+  double *coef;
+  double *point, *normal, *albedo;
+  int32_t *material;
+  double *power;
+  uint8_t *in_shadow;
+  int32_t *child_refl, *child_refr;
+  int32_t *pixel;
+} mt_raytree_layer;
+mt_raytree *mt_raytree_create(mt_scene *scene, const mt_sensor *sensor, int image_w, int image_h,
+                              int chunk_x, int chunk_y, int chunk_w, int chunk_h, int max_depth, mt_stats *stats);
+void mt_raytree_destroy(mt_raytree *tree);
+int mt_raytree_info(const mt_raytree *tree, mt_raytree_desc *out);
+int mt_raytree_read_layer(mt_raytree *tree, int layer, const mt_raytree_layer *out);
+int mt_raytree_shade(mt_raytree *tree, const mt_light *lights, int n_lights, uint8_t *out_rgb, mt_stats *stats);
+int mt_raytree_shade_device(mt_raytree *tree, const mt_light *lights, int n_lights, void *d_rgb, void *stream);
+
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into
  * WorkChunks, every worker renders chunks with the full-image sensor from its

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -30,7 +31,10 @@ HIP_SYMBOLS = [
     "mt_render_lightbuffer", "mt_render_lightbuffer_device", "mt_shade_direct", "mt_shade_direct_device",
     "mt_update_lightbuffer", "mt_update_lightbuffer_device",
     "mt_refine_mask_device", "mt_render_chunk_adaptive", "mt_render_chunk_adaptive_device",
+    "mt_raytree_create", "mt_raytree_destroy", "mt_raytree_info", "mt_raytree_read_layer",
+    "mt_raytree_shade", "mt_raytree_shade_device",
 ]
+MT_MAX_RECURSION = 16
 
 # mt_scene_set_tuning knobs, in the order of the enum in include/mythtracer_hip.h
 TUNE = {name: i for i, name in enumerate([
@@ -212,6 +216,31 @@ def _update_planes(gbuffer, lightbuffer):
 DEBUG_PX_DTYPE = np.dtype([("line_no", "<i4"), ("reserved", "<i4"), ("point", "<f8", 3)])
 
 
+class mt_raytree_desc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_layers", "n_lights", "image_w", "image_h", "chunk_x", "chunk_y", "chunk_w",
+                                         "chunk_h", "max_depth", "reserved")] + [
+        ("n_rays", C.c_int64 * (MT_MAX_RECURSION + 1)), ("trace_ms", C.c_double * (MT_MAX_RECURSION + 1)),
+        ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        n = int(self.n_layers)
+        return dict(n_layers=n, n_lights=int(self.n_lights), image=(int(self.image_w), int(self.image_h)),
+                    chunk=(int(self.chunk_x), int(self.chunk_y), int(self.chunk_w), int(self.chunk_h)),
+                    max_depth=int(self.max_depth), n_rays=[int(v) for v in self.n_rays[:n]],
+                    trace_ms=[float(v) for v in self.trace_ms[:n]], bytes=int(self.bytes))
+
+
+# the planes of mt_raytree_layer in declaration order: name -> (dtype, values per ray, per light?)
+RAYTREE_PLANES = {"ray": (np.float64, 6, False), "in_object": (np.uint8, 1, False), "coef": (np.float64, 1, False),
+                  "point": (np.float64, 3, False), "normal": (np.float64, 3, False), "albedo": (np.float64, 3, False),
+                  "material": (np.int32, 1, False), "power": (np.float64, 3, True), "in_shadow": (np.uint8, 1, True),
+                  "child_refl": (np.int32, 1, False), "child_refr": (np.int32, 1, False), "pixel": (np.int32, 1, False)}
+
+
+class mt_raytree_layer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RAYTREE_PLANES]
+
+
 def _load(path):
     if not os.path.exists(path):
         raise NativeLibraryMissing(
@@ -278,6 +307,14 @@ class HipAbi:
         L.mt_update_lightbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp, ci, C.POINTER(mt_lightbuffer), vp]
         L.mt_update_lightbuffer_device.argtypes = L.mt_update_lightbuffer.argtypes
         L.mt_refine_mask_device.argtypes = [vp] + [ci] * 7 + [vp] * 5
+        L.mt_raytree_create.restype = vp
+        L.mt_raytree_create.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp]
+        L.mt_raytree_destroy.argtypes = [vp]
+        L.mt_raytree_destroy.restype = None
+        L.mt_raytree_info.argtypes = [vp, C.POINTER(mt_raytree_desc)]
+        L.mt_raytree_read_layer.argtypes = [vp, ci, C.POINTER(mt_raytree_layer)]
+        L.mt_raytree_shade.argtypes = [vp, vp, ci, vp, vp]
+        L.mt_raytree_shade_device.argtypes = [vp, vp, ci, vp, vp]
         ps = C.POINTER(mt_sensor)
         L.mt_render_chunk_adaptive.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
         L.mt_render_chunk_adaptive_device.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
@@ -601,6 +638,60 @@ class HipAbi:
         self.check(self.lib.mt_update_lightbuffer_device(h, chunk_w, chunk_h, C.byref(g), _ptr(idx), len(idx),
                                                          C.byref(lb), stream))
 
+    # ---- the ray-tree buffer (include/mythtracer_hip.h, mt_raytree_create)
+    def raytree_create(self, h, sensor12, image_w, image_h, chunk=None, max_depth=5):
+        """mt_raytree_create under the scene's current lights: (tree handle, stats dict).  raytree_destroy it before
+        the scene."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        st = mt_stats()
+        s = self.make_sensor(sensor12) if sensor12 is not None else None
+        t = self.lib.mt_raytree_create(h, C.byref(s) if s is not None else None, image_w, image_h, cx, cy, cw, ch,
+                                       max_depth, C.addressof(st))
+        if not t:
+            raise RuntimeError("mythtracer_hip error: mt_raytree_create: %s" % self.last_error())
+        return t, st.as_dict()
+
+    def raytree_destroy(self, tree):
+        self.lib.mt_raytree_destroy(tree)
+
+    def raytree_info(self, tree) -> dict:
+        d = mt_raytree_desc()
+        self.check(self.lib.mt_raytree_info(tree, C.byref(d)))
+        return d.as_dict()
+
+    def raytree_read_layer(self, tree, layer, planes=None) -> dict:
+        """mt_raytree_read_layer: dict plane name -> numpy array of the layer's n rays ((n,), (n, 3), (n, 6); power
+        (n_lights, n, 3), in_shadow (n_lights, n)) for the planes named (None = all; `pixel` for layer 0 only)."""
+        info = self.raytree_info(tree)
+        if not 0 <= layer < info["n_layers"]:
+            raise ValueError("layer %d outside the tree's %d layers" % (layer, info["n_layers"]))
+        names = [n for n in RAYTREE_PLANES if n != "pixel" or layer == 0] if planes is None else list(planes)
+        n, n_l = info["n_rays"][layer], info["n_lights"]
+        out = {}
+        for name in names:
+            if name not in RAYTREE_PLANES:
+                raise ValueError("unknown ray-tree plane %r (planes: %s)" % (name, ", ".join(RAYTREE_PLANES)))
+            dt, k, per_light = RAYTREE_PLANES[name]
+            out[name] = np.zeros(((n_l,) if per_light else ()) + (n,) + ((k,) if k > 1 else ()), dtype=dt)
+        ls = mt_raytree_layer(**{name: (a.ctypes.data if a.size else None) for name, a in out.items()})
+        self.check(self.lib.mt_raytree_read_layer(tree, layer, C.byref(ls)))
+        return out
+
+    def raytree_shade(self, tree, lights) -> dict:
+        """mt_raytree_shade under `lights` (n x 12; count and positions as when the tree was made): dict(rgb, stats)."""
+        info = self.raytree_info(tree)
+        l = _f64(lights).reshape(-1, 12)
+        _, _, cw, ch = info["chunk"]
+        rgb = np.zeros((ch, cw, 3), dtype=np.uint8)
+        st = mt_stats()
+        self.check(self.lib.mt_raytree_shade(tree, _ptr(l), l.shape[0], _ptr(rgb), C.addressof(st)))
+        return dict(rgb=rgb, stats=st.as_dict())
+
+    def raytree_shade_device(self, tree, lights, d_rgb, stream=None):
+        """mt_raytree_shade_device: `lights` a host array (n x 12), d_rgb a device pointer; asynchronous on `stream`."""
+        l = _f64(lights).reshape(-1, 12)
+        self.check(self.lib.mt_raytree_shade_device(tree, _ptr(l), l.shape[0], d_rgb, stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -733,6 +824,13 @@ def host_lib():
     L.mth_shade_direct.argtypes = [vp, vp] + [ci] * 6 + [vp, ci, vp, vp, vp]
     L.mth_update_lightbuffer.argtypes = [vp, ci, ci, vp, vp, ci, C.c_uint, vp, ci, vp, vp]
     L.mth_num_lights.argtypes = [vp]
+    L.mth_raytree_build.restype = vp
+    L.mth_raytree_build.argtypes = [vp, vp] + [ci] * 6 + [vp, vp]
+    L.mth_raytree_free.argtypes = [vp]
+    L.mth_raytree_free.restype = None
+    L.mth_raytree_handle.argtypes = [vp]
+    L.mth_raytree_handle.restype = vp
+    L.mth_raytree_shade.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mth_chunk_serialize_input.argtypes = [vp, vp]
@@ -759,6 +857,55 @@ def sensor_ray(cam7, w, h, x, y):
     return d
 
 
+class RayTree:
+    """raytracer::RayTree as MythTracer.raytree returns it: `.info`, `.layer(k)`, `.shade(lights=None)`, `.close()`.
+    Close it before its MythTracer."""
+
+    def __init__(self, mt, handle, counters, kernel_ms, total_ms):
+        self.mt, self.h = mt, handle
+        self.counters, self.kernel_ms, self.total_ms = counters, kernel_ms, total_ms
+
+    def _tree(self):
+        if not self.h:
+            raise RuntimeError("the RayTree is closed")
+        return self.mt.L.mth_raytree_handle(self.h)
+
+    @property
+    def info(self) -> dict:
+        return hip_abi().raytree_info(self._tree())
+
+    def layer(self, k, planes=None) -> dict:
+        return hip_abi().raytree_read_layer(self._tree(), k, planes)
+
+    def shade(self, lights=None) -> dict:
+        """MythTracer::ShadeRayTree.  `lights` (n x 12) replaces the facade's lights first, as set_lights does; None
+        keeps them.  Returns dict(rgb, kernel_ms, total_ms)."""
+        self._tree()
+        if lights is not None:
+            self.mt.set_lights(lights)
+        _, _, cw, ch = self.info["chunk"]
+        rgb = np.zeros((ch, cw, 3), dtype=np.uint8)
+        ms = np.zeros(2)
+        if not self.mt.L.mth_raytree_shade(self.mt.h, self.h, _ptr(rgb), rgb.size, _ptr(ms)):
+            raise RuntimeError("ShadeRayTree failed: " + self.mt.last_error())
+        return dict(rgb=rgb, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.mt.L.mth_raytree_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self.mt, "h", None):  # (after its MythTracer the tree is gone already)
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class MythTracer:
     """raytracer::MythTracer (host facade) through the ctypes shim."""
 
@@ -770,6 +917,11 @@ class MythTracer:
 
     def close(self):
         if getattr(self, "h", None):
+            for ref in getattr(self, "_trees", []):  # a RayTree goes before the scene it lives on
+                t = ref()
+                if t is not None:
+                    t.close()
+            self._trees = []
             self.L.mth_free(self.h)
             self.h = None
 
@@ -1004,6 +1156,23 @@ class MythTracer:
         out = dict(lb)
         out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
         return out
+
+    def raytree(self, cam, image_w, image_h, chunk=None, max_depth=None) -> RayTree:
+        """MythTracer::BuildRayTree under the lights of set_lights: the whole call tree of the chunk's pixels, kept on
+        the GPU.  max_depth (None = the facade's level) goes through set_max_level first.  The object's .counters are
+        those of render() for the same frame."""
+        cx, cy, cw, ch = chunk if chunk else (0, 0, image_w, image_h)
+        if max_depth is not None:
+            self.set_max_level(int(max_depth))
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        cam = _f64(cam)
+        t = self.L.mth_raytree_build(self.h, _ptr(cam), image_w, image_h, cx, cy, cw, ch, _ptr(st), _ptr(ms))
+        if not t:
+            raise RuntimeError("BuildRayTree failed: " + self.last_error())
+        tree = RayTree(self, t, dict(zip(STAT_NAMES, (int(x) for x in st))), float(ms[0]), float(ms[1]))
+        self._trees = [r for r in getattr(self, "_trees", []) if r() is not None] + [weakref.ref(tree)]
+        return tree
 
     def render_image(self, cam, image_w, image_h):
         """MythTracer::RayTrace(int, int, Camera*, vector<uint8_t>*)."""

@@ -30,6 +30,7 @@
 #include "mt_adaptive.h"
 #include "mt_gbuffer.h"
 #include "mt_lightbuffer.h"
+#include "mt_raytree.h"
 
 using namespace mt;
 
@@ -330,6 +331,7 @@ struct LayoutKernels {
   void (*gbuffer[2])(DevScene, GBufferArgs);
   void (*lightbuffer[2])(DevScene, LightBufferArgs);
   void (*lightbuffer_update[2])(DevScene, LightUpdateArgs);
+  void (*raytree_trace[2])(DevScene, RayTreeTraceArgs);
 };
 template <int D>
 LayoutKernels layout_kernels() {
@@ -337,7 +339,8 @@ LayoutKernels layout_kernels() {
           {pool_kernel<false, D>, pool_kernel<true, D>}, {hybrid_kernel<false, D>, hybrid_kernel<true, D>},
           probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>},
           {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>},
-          {lightbuffer_update_kernel<false, D>, lightbuffer_update_kernel<true, D>}};
+          {lightbuffer_update_kernel<false, D>, lightbuffer_update_kernel<true, D>},
+          {raytree_trace_kernel<false, D>, raytree_trace_kernel<true, D>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -2601,6 +2604,307 @@ int mt_update_lightbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffe
   HIP_TRY(hipEventRecord(s->ev1, stream));
   MT_TRY(planes_to_host(s, copies, stream));
   if (stats) MT_TRY(fill_call_stats(s, stats, w0));
+  return MT_OK;
+}
+
+// ---- the ray-tree buffer (mt_raytree.h).  Like the G-buffer and light-buffer calls, nothing here reads or writes what
+// decide_launch looks at. ----
+struct mt_raytree {
+  mt_scene *scene = nullptr;
+  mt_raytree_desc info{};
+  mt_sensor sensor{};
+  void *alloc[MT_MAX_RECURSION + 1] = {};  // one allocation per layer
+  RayTreeLayer layer[MT_MAX_RECURSION + 1] = {};
+  unsigned long long *d_count = nullptr;   // the compaction's answer
+  uint8_t *d_rgb = nullptr;                // the host shade's bitmap (first use)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_layer[MT_MAX_RECURSION + 1][2] = {};
+};
+
+namespace {
+
+// hipMalloc for a tree: what does not fit is MT_ERR_NOMEM
+int raytree_malloc(void **p, size_t bytes, const char *what) {
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+  if (e == hipSuccess) return MT_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s", bytes, what);
+  return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
+}
+
+// One allocation holds a layer's planes, each at a multiple of 256 bytes.
+int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
+  const size_t n_l = (size_t)t->info.n_lights;
+  struct Part { void **at; size_t bytes; };
+  RayTreeLayer &L = t->layer[k];
+  const Part parts[] = {
+      {(void **)&L.ray, n * 48}, {(void **)&L.coef, n * 8}, {(void **)&L.point, n * 24}, {(void **)&L.normal, n * 24},
+      {(void **)&L.albedo, n * 24}, {(void **)&L.power, n_l * n * 24}, {(void **)&L.color, n * 24},
+      {(void **)&L.material, n * 4}, {(void **)&L.child_refl, n * 4}, {(void **)&L.child_refr, n * 4},
+      {(void **)&L.pixel, k == 0 ? n * 4 : 0}, {(void **)&L.in_object, n}, {(void **)&L.in_shadow, n_l * n},
+      {(void **)&L.spawn, n}};
+  size_t total = 0;
+  for (const Part &p : parts) total += (p.bytes + 255) & ~(size_t)255;
+  char what[64];
+  snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
+  MT_TRY(raytree_malloc(&t->alloc[k], total, what));
+  size_t at = 0;
+  for (const Part &p : parts) {
+    *p.at = (char *)t->alloc[k] + at;
+    at += (p.bytes + 255) & ~(size_t)255;
+  }
+  if (k != 0) L.pixel = nullptr;
+  t->info.bytes += total;
+  t->info.n_rays[k] = (int64_t)n;
+  t->info.n_layers = k + 1;
+  return MT_OK;
+}
+
+int check_raytree_create_args(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x,
+                              int chunk_y, int chunk_w, int chunk_h, int max_depth) {
+  if (image_w <= 0 || image_h <= 0 || image_w > 100000 || image_h > 100000) {
+    return fail(MT_ERR_ARG, "image size %dx%d out of range", image_w, image_h);
+  }
+  MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  if (max_depth < 0 || max_depth > MT_MAX_RECURSION) {
+    return fail(MT_ERR_ARG, "max_depth %d outside [0, %d]", max_depth, MT_MAX_RECURSION);
+  }
+  return MT_OK;
+}
+
+int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_lights, const void *rgb) {
+  if (!rgb) return fail(MT_ERR_ARG, "the output bitmap is NULL");
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (n_lights < 0 || (n_lights > 0 && !lights)) return fail(MT_ERR_ARG, "bad lights argument");
+  if (n_lights != t->info.n_lights) {
+    return fail(MT_ERR_ARG, "%d lights for a ray tree made with %d", n_lights, t->info.n_lights);
+  }
+  return MT_OK;
+}
+
+// the counters so far, checked: no further layer after a tripped bound
+int raytree_read_counters(mt_scene *s, hipStream_t stream) {
+  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return check_status(s->h_counters);
+}
+
+// Layer after layer: trace, compact, (host: size the next layer), spawn.
+int raytree_build(mt_raytree *t, mt_stats *stats) {
+  mt_scene *s = t->scene;
+  const auto w0 = std::chrono::steady_clock::now();
+  hipStream_t stream = nullptr;
+  const mt_raytree_desc &I = t->info;
+  const size_t npx = (size_t)I.chunk_w * (size_t)I.chunk_h;
+  if (npx >= 0x80000000ull) return fail(MT_ERR_UNSUPPORTED, "layer 0 of the ray tree would have %zu rays (2^31 or more)", npx);
+  HIP_TRY(hipEventCreate(&t->ev0));
+  HIP_TRY(hipEventCreate(&t->ev1));
+  MT_TRY(raytree_malloc((void **)&t->d_count, sizeof(unsigned long long), "the ray tree's child count"));
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  MT_TRY(raytree_alloc_layer(t, 0, npx));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(t->ev0, stream));
+  {
+    RayTreePrimaryArgs A{};
+    A.sensor = t->sensor;
+    A.chunk_x = I.chunk_x; A.chunk_y = I.chunk_y; A.chunk_w = I.chunk_w; A.chunk_h = I.chunk_h;
+    A.L = t->layer[0];
+    hipLaunchKernelGGL(raytree_primary_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, A);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int k = 0;; k++) {
+    const size_t n = (size_t)I.n_rays[k];
+    RayTreeTraceArgs A{};
+    A.L = t->layer[k];
+    A.n_rays = (uint32_t)n;
+    A.n_items = (uint32_t)((n + 63) / 64);
+    A.secondary = k > 0 ? 1 : 0;
+    A.may_spawn = k < I.max_depth ? 1 : 0;
+    unsigned grid = 0;
+    MT_TRY(prepare_persistent_launch(s, A.n_items, &grid, stream));
+    A.counters = s->d_counters;
+    A.work_counter = s->d_gb_work;
+    HIP_TRY(hipEventCreate(&t->ev_layer[k][0]));
+    HIP_TRY(hipEventCreate(&t->ev_layer[k][1]));
+    HIP_TRY(hipEventRecord(t->ev_layer[k][0], stream));
+    hipLaunchKernelGGL(kernels_of(s->deep).raytree_trace[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
+                       s->lds_bytes, stream, s->dev, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t->ev_layer[k][1], stream));
+    if (k == I.max_depth) {  // no ray of the deepest layer has a child
+      HIP_TRY(hipMemsetAsync(t->layer[k].child_refl, 0xff, n * 4, stream));
+      HIP_TRY(hipMemsetAsync(t->layer[k].child_refr, 0xff, n * 4, stream));
+      break;
+    }
+    hipLaunchKernelGGL(raytree_compact_kernel, dim3(1), dim3(kRayTreeCompactThreads), 0, stream, t->layer[k], (uint32_t)n,
+                       t->d_count);
+    HIP_TRY(hipGetLastError());
+    unsigned long long children = 0;
+    HIP_TRY(hipMemcpyAsync(&children, t->d_count, sizeof children, hipMemcpyDeviceToHost, stream));
+    MT_TRY(raytree_read_counters(s, stream));  // (synchronises: `children` has arrived)
+    if (children == 0) break;
+    if (children >= 0x80000000ull) {
+      return fail(MT_ERR_UNSUPPORTED, "layer %d of the ray tree would have %llu rays (2^31 or more)", k + 1, children);
+    }
+    MT_TRY(raytree_alloc_layer(t, k + 1, (size_t)children));
+    RayTreeSpawnArgs SA{};
+    SA.parent = t->layer[k];
+    SA.child = t->layer[k + 1];
+    SA.n_parent = (uint32_t)n;
+    SA.mtls = s->dev.mtls;
+    hipLaunchKernelGGL(raytree_spawn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, SA);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(t->ev1, stream));
+  MT_TRY(raytree_read_counters(s, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  for (int k = 0; k < I.n_layers; k++) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev_layer[k][0], t->ev_layer[k][1]));
+    t->info.trace_ms[k] = ms;
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    fill_stats(s->h_counters, stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
+  return MT_OK;
+}
+
+// raytree_shade_kernel over the layers, deepest first; d_rgb = device pointer
+int launch_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *d_rgb, hipStream_t stream) {
+  mt_scene *s = t->scene;
+  RayTreeShadeArgs A{};
+  A.n_lights = n_lights;
+  A.mtls = s->dev.mtls;
+  const bool in_args = n_lights <= kShadeArgLights;
+  if (in_args) {
+    for (int i = 0; i < n_lights; i++) A.lights[i] = lights[i];
+  } else {
+    MT_TRY(s->d_shade_lights.ensure((size_t)n_lights * sizeof(mt_light)));
+    HIP_TRY(hipMemcpyAsync(s->d_shade_lights, lights, (size_t)n_lights * sizeof(mt_light), hipMemcpyHostToDevice, stream));
+    A.d_lights = s->d_shade_lights;
+  }
+  for (int k = t->info.n_layers - 1; k >= 0; k--) {
+    const size_t n = (size_t)t->info.n_rays[k];
+    A.L = t->layer[k];
+    A.child_color = k + 1 < t->info.n_layers ? t->layer[k + 1].color : nullptr;
+    A.n_rays = (uint32_t)n;
+    A.out_rgb = k == 0 ? d_rgb : nullptr;
+    hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, stream, A);
+    HIP_TRY(hipGetLastError());
+  }
+  return MT_OK;
+}
+
+}  // namespace
+
+void mt_raytree_destroy(mt_raytree *t) {
+  if (!t) return;
+  (void)hipSetDevice(t->scene->device);
+  (void)hipDeviceSynchronize();
+  for (void *p : t->alloc) {
+    if (p) (void)hipFree(p);
+  }
+  if (t->d_count) (void)hipFree(t->d_count);
+  if (t->d_rgb) (void)hipFree(t->d_rgb);
+  if (t->ev0) (void)hipEventDestroy(t->ev0);
+  if (t->ev1) (void)hipEventDestroy(t->ev1);
+  for (auto &e : t->ev_layer) {
+    if (e[0]) (void)hipEventDestroy(e[0]);
+    if (e[1]) (void)hipEventDestroy(e[1]);
+  }
+  delete t;
+}
+
+mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
+                              int chunk_w, int chunk_h, int max_depth, mt_stats *stats) {
+  if (check_raytree_create_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, max_depth) != MT_OK) {
+    return nullptr;
+  }
+  if (hipSetDevice(s->device) != hipSuccess) {
+    (void)fail(MT_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+    return nullptr;
+  }
+  mt_raytree *t = new mt_raytree();
+  t->scene = s;
+  t->sensor = *sensor;
+  t->info.n_lights = s->dev.n_lights;
+  t->info.image_w = image_w; t->info.image_h = image_h;
+  t->info.chunk_x = chunk_x; t->info.chunk_y = chunk_y; t->info.chunk_w = chunk_w; t->info.chunk_h = chunk_h;
+  t->info.max_depth = max_depth;
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = raytree_build(t, stats);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) {
+    const std::string why = g_err;  // (the text survives the clean-up)
+    mt_raytree_destroy(t);
+    (void)fail(rc, "%s", why.c_str());
+    return nullptr;
+  }
+  return t;
+}
+
+int mt_raytree_info(const mt_raytree *t, mt_raytree_desc *out) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (!out) return fail(MT_ERR_ARG, "the mt_raytree_desc is NULL");
+  *out = t->info;
+  return MT_OK;
+}
+
+int mt_raytree_read_layer(mt_raytree *t, int layer, const mt_raytree_layer *out) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (layer < 0 || layer >= t->info.n_layers) {
+    return fail(MT_ERR_ARG, "layer %d outside the ray tree's %d layers", layer, t->info.n_layers);
+  }
+  if (!out) return fail(MT_ERR_ARG, "the mt_raytree_layer is NULL");
+  if (out->pixel != nullptr && layer != 0) return fail(MT_ERR_ARG, "only layer 0 has a pixel plane");
+  HIP_TRY(hipSetDevice(t->scene->device));
+  const RayTreeLayer &L = t->layer[layer];
+  const size_t n = (size_t)t->info.n_rays[layer], n_l = (size_t)t->info.n_lights;
+  const PlaneCopy copies[] = {
+      {out->ray, L.ray, n * 48}, {out->in_object, L.in_object, n}, {out->coef, L.coef, n * 8},
+      {out->point, L.point, n * 24}, {out->normal, L.normal, n * 24}, {out->albedo, L.albedo, n * 24},
+      {out->material, L.material, n * 4}, {out->power, L.power, n_l * n * 24}, {out->in_shadow, L.in_shadow, n_l * n},
+      {out->child_refl, L.child_refl, n * 4}, {out->child_refr, L.child_refr, n * 4}, {out->pixel, L.pixel, n * 4}};
+  for (const PlaneCopy &c : copies) {
+    if (c.host != nullptr && c.bytes > 0) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
+  }
+  return MT_OK;
+}
+
+int mt_raytree_shade_device(mt_raytree *t, const mt_light *lights, int n_lights, void *d_rgb, void *stream) {
+  MT_TRY(check_raytree_shade_args(t, lights, n_lights, d_rgb));
+  HIP_TRY(hipSetDevice(t->scene->device));
+  return launch_raytree_shade(t, lights, n_lights, (uint8_t *)d_rgb, (hipStream_t)stream);
+}
+
+int mt_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *out_rgb, mt_stats *stats) {
+  MT_TRY(check_raytree_shade_args(t, lights, n_lights, out_rgb));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(t->scene->device));
+  const size_t npx = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
+  hipStream_t stream = nullptr;
+  if (!t->d_rgb) MT_TRY(raytree_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
+  HIP_TRY(hipEventRecord(t->ev0, stream));
+  MT_TRY(launch_raytree_shade(t, lights, n_lights, t->d_rgb, stream));
+  HIP_TRY(hipEventRecord(t->ev1, stream));
+  HIP_TRY(hipMemcpyAsync(out_rgb, t->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
   return MT_OK;
 }
 

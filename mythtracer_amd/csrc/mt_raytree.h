@@ -1,0 +1,381 @@
+// mt_raytree.h — the ray-tree buffer: the whole call tree of TraceRayWorker (mythtracer.cc:13-228) for every pixel of a
+// chunk, traced once and stored layer by layer, so that the full-depth frame under edited light COLOURS is arithmetic
+// over the stored tree (include/mythtracer_hip.h, mt_raytree_create ff.).  Nothing in the shape of the recursion depends
+// on a light's colour: :181-184 and :192 read level, the material's reflectance and transparency, the reflection
+// coefficient and in_object; the rays, their hits and the shadow loops read geometry, materials and light POSITIONS.
+//
+// Layer 0 holds one ray per chunk pixel (Sensor::GetRay), layer k + 1 the child rays of layer k in parent order, a
+// parent's reflected ray before its refracted one.  Per ray: origin and direction as handed to IntersectRay, in_object,
+// coef, the G-buffer planes point / normal (unflipped) / albedo / material, per light power and in_shadow
+// (mt_lightbuffer.h's meaning, planes [n_lights][n_rays]), the two child indices into the next layer (-1 = none), and
+// in layer 0 the chunk-local pixel index.
+//
+//   raytree_primary_kernel  layer 0's ray list from the sensor, in raytree_layer0_index's order (8x8 blocks of the
+//                           chunk, row-major; a block clipped by the chunk's edge holds only its pixels, row-major:
+//                           the list has no holes).  mythtracer_amd/tiling.py restates it (raytree_layer0_order).
+//   raytree_trace_kernel    lightbuffer_kernel's execution model over a ray LIST: a work item is 64 consecutive rays.
+//                           Each lane loads its ray, traces it, writes the planes (write_gbuffer_planes), runs the
+//                           lights' shadow loops -- lightbuffer_kernel's loop body restated, that kernel is as it was --
+//                           and leaves the two child conditions in a byte per ray.
+//   raytree_compact_kernel  one workgroup, refine_compact_kernel's scan: the child conditions become indices into the
+//                           next layer, in order; the count goes to the host, which sizes the next layer by it.
+//   raytree_spawn_kernel    one thread per parent: the child rays of :68-74 and :208-218 with the in_object and coef the
+//                           recursive call receives (:186-187, :222-223), in the frame kernels' arithmetic.
+//   raytree_shade_kernel    one thread per ray, one launch per layer, bottom-up: the direct term as shade_direct_kernel
+//                           states it (from the stored direction instead of the sensor), + colour[child_refl] *
+//                           reflectance (:185-188), + colour[child_refr] * transmission_filter * transparency
+//                           (:220-224); layer 0 ends in V3DtoRGB at the ray's pixel.
+// fp64 in the reference's order of operations (-ffp-contract=off), so a shaded tree is mt_render_chunk's frame byte for
+// byte.
+#pragma once
+#include "mt_lightbuffer.h"
+
+namespace mt {
+
+// One layer's planes on the device (n rays).  `color` and `spawn` are the tree's own scratch.
+struct RayTreeLayer {
+  double *ray;         // [n][6] origin, direction
+  double *coef;        // [n]
+  double *point, *normal, *albedo;  // [n][3]
+  double *power;       // [n_lights][n][3]
+  double *color;       // [n][3] the shade's per-ray colour
+  int32_t *material;   // [n]
+  int32_t *child_refl, *child_refr;  // [n]
+  int32_t *pixel;      // [n], layer 0 only
+  uint8_t *in_object;  // [n]
+  uint8_t *in_shadow;  // [n_lights][n]
+  uint8_t *spawn;      // [n] bit 0: a reflected child, bit 1: a refracted child
+};
+
+// index of chunk pixel (x, y) in layer 0's list
+__host__ __device__ inline size_t raytree_layer0_index(int x, int y, int chunk_w, int chunk_h) {
+  const int bx = x >> 3, by = y >> 3;
+  const int bh = chunk_h - by * 8 < 8 ? chunk_h - by * 8 : 8;
+  const int bw = chunk_w - bx * 8 < 8 ? chunk_w - bx * 8 : 8;
+  return (size_t)by * 8 * (size_t)chunk_w + (size_t)bx * 8 * (size_t)bh + (size_t)((y & 7) * bw + (x & 7));
+}
+
+struct RayTreePrimaryArgs {
+  mt_sensor sensor;
+  int32_t chunk_x, chunk_y, chunk_w, chunk_h;
+  RayTreeLayer L;
+};
+
+__global__ __launch_bounds__(256) void raytree_primary_kernel(RayTreePrimaryArgs A) {
+  const size_t npx = (size_t)A.chunk_w * (size_t)A.chunk_h;
+  const size_t px = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (px >= npx) return;
+  const int lx = (int)(px % (size_t)A.chunk_w), ly = (int)(px / (size_t)A.chunk_w);
+  const size_t i = raytree_layer0_index(lx, ly, A.chunk_w, A.chunk_h);
+  // Sensor::GetRay, camera.cc:65-69
+  const V3 d = v3_load(A.sensor.start_point) + (v3_load(A.sensor.delta_scanline) * (double)(A.chunk_y + ly)) +
+               (v3_load(A.sensor.delta_pixel) * (double)(A.chunk_x + lx));
+  const V3 rd = normalized(d);
+  double *r = A.L.ray + i * 6;
+  r[0] = A.sensor.origin[0]; r[1] = A.sensor.origin[1]; r[2] = A.sensor.origin[2];
+  r[3] = rd.x; r[4] = rd.y; r[5] = rd.z;
+  A.L.coef[i] = 1.0;
+  A.L.in_object[i] = 0;
+  A.L.pixel[i] = (int32_t)px;
+}
+
+struct RayTreeTraceArgs {
+  RayTreeLayer L;
+  uint32_t n_rays;
+  uint32_t n_items;              // ceil(n_rays / 64)
+  int32_t secondary;             // layer >= 1: the rays count as secondary
+  int32_t may_spawn;             // layer < max_depth
+  unsigned long long *counters;  // ST_COUNT
+  unsigned int *work_counter;    // zero at launch
+};
+
+template <bool STATS, int DEEP>
+__global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void raytree_trace_kernel(DevScene S, RayTreeTraceArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave_in_block = threadIdx.x >> 6;
+  WaveStack stk;
+  stk.bind(smem, wave_in_block, S.tree_depth, S.pack_shift, DEEP != 0);
+  const MT_CONST mt_material *mtls = as_const(S.mtls);
+  const MT_CONST mt_light *lights = as_const(S.lights);
+  LaneStats st;
+  st.clear();
+  GBufferPlanes planes{};
+  planes.point = A.L.point; planes.normal = A.L.normal; planes.albedo = A.L.albedo; planes.material = A.L.material;
+  const size_t n = (size_t)A.n_rays;
+  // every iteration of a shadow loop crosses another surface
+  const int iteration_bound = S.n_tris + 2;
+  bool failed = false;
+  while (!failed) {
+    const unsigned item = fetch_work(A.work_counter, lane);
+    if (item >= A.n_items) break;
+    const size_t i = (size_t)item * 64 + (size_t)lane;
+    const bool want = i < n;
+    V3 org = v3(0, 0, 0), rd = v3(0, 0, 1);
+    if (want) {
+      org = v3_load(A.L.ray + i * 6);
+      rd = v3_load(A.L.ray + i * 6 + 3);
+      if (STATS) st.v[ST_BYTES_VECTOR] += 48u;
+    }
+    const TraceOut to = trace_wave<STATS, DEEP>(S.self, stk.base, lane, want, org.x, org.y, org.z, rd.x, rd.y, rd.z);
+    add_trace_stats<STATS>(st, to);
+    if (to.status != DEV_OK) {
+      if (lane == 0) atomicMax(A.counters + ST_STATUS, (unsigned long long)to.status);
+      break;
+    }
+    V3 Pt = v3(0, 0, 0);
+    bool lit = false;  // does the reference enter the light loop for this ray?
+    if (want) {
+      const PrimaryHit h = write_gbuffer_planes<STATS>(S, planes, i, org, rd, to, st, true);
+      if (STATS && A.secondary) {  // (write_gbuffer_planes counted a primary ray)
+        st.v[ST_RAYS_PRIMARY]--;
+        st.v[ST_RAYS_SECONDARY]++;
+      }
+      lit = to.prim >= 0 && h.mtl >= 0;
+      if (lit) Pt = h.point;
+      // the child conditions, :181-184 and :192 (level < max_depth is the layer's: wave-uniform)
+      unsigned spawn = 0;
+      if (lit && A.may_spawn) {
+        const MT_CONST mt_material *m = mtls + h.mtl;
+        const bool in_object = A.L.in_object[i] != 0;
+        if (m->reflectance > 0.0 && A.L.coef[i] > 0.01 && !in_object) spawn |= 1u;
+        if (m->transparency > 0.0) spawn |= 2u;
+      }
+      A.L.spawn[i] = (uint8_t)spawn;
+    }
+    for (int li = 0; li < S.n_lights && !failed; li++) {
+      const MT_CONST mt_light *lt = lights + li;
+      const V3 lpos = v3(lt->position[0], lt->position[1], lt->position[2]);
+      // from here to the stores: lightbuffer_kernel's light loop body, the same operations in the same order
+      V3 start = Pt, lp = v3(1.0, 1.0, 1.0);  // :90, :94
+      bool in_shadow = false, traversing = false, running = lit;
+      V3 ro = Pt, ld = v3(0, 0, 1);
+      if (lit) {
+        ld = normalized(lpos - Pt);  // light_direction, :79-80
+        ro = Pt + (ld * 0.00001);    // :95-99
+      }
+      int iterations = 0;
+      while (__ballot(running) != 0ull) {
+        const TraceOut so = trace_wave<STATS, DEEP>(S.self, stk.base, lane, running, ro.x, ro.y, ro.z, ld.x, ld.y, ld.z);
+        add_trace_stats<STATS>(st, so);
+        if (so.status != DEV_OK || ++iterations > iteration_bound) {
+          if (lane == 0) {
+            atomicMax(A.counters + ST_STATUS, (unsigned long long)(so.status != DEV_OK ? so.status : DEV_ERR_PIXEL_BOUND));
+          }
+          failed = true;
+          break;
+        }
+        if (running) {  // one iteration of the shadow loop, mythtracer.cc:94-156 (as mt_render.hip states it)
+          if (STATS) {
+            st.v[ST_RAYS_SHADOW]++;
+            st.v[ST_BYTES_VECTOR] += 96u + 4u + 32u;  // light, occluder's material index and transparency
+          }
+          const int prim = so.prim;
+          const double t = so.t;
+          if (prim < 0) {
+            running = false;  // :109-112
+          } else {
+            const double light_distance = distance(start, lpos);  // :101-102
+            if (t > light_distance) {
+              running = false;  // :115-118
+            } else {
+              // :121 dereferences shadow_primitive->mtl unconditionally; defined as opaque (mt_render.hip)
+              const int sm = S.tri_mtl[prim];
+              const double s_tr = sm >= 0 ? mtls[sm].transparency : 0.0;
+              if (s_tr == 0.0) {
+                lp = v3(0, 0, 0);
+                in_shadow = true;
+                running = false;
+              } else {
+                if (!traversing) {  // :129-132
+                  const MT_CONST mt_material *smm = mtls + sm;
+                  const V3 tf = v3(smm->transmission_filter[0], smm->transmission_filter[1],
+                                   smm->transmission_filter[2]);
+                  lp = lp * (tf * s_tr);
+                }
+                traversing = !traversing;
+                const V3 sp = ro + ld * t;
+                start = sp + (ld * 0.0000001);  // :137
+                if (sqr_distance(Pt, start) > sqr_distance(Pt, lpos)) {
+                  running = false;  // :141-145
+                } else if (lp.x <= 0.001 && lp.y <= 0.001 && lp.z <= 0.001) {
+                  lp = v3(0, 0, 0);  // :149-155
+                  in_shadow = true;
+                  running = false;
+                } else {
+                  ro = start + (ld * 0.00001);  // next iteration, :95-99
+                }
+              }
+            }
+          }
+        }
+      }
+      if (want && !failed) {
+        const size_t at = (size_t)li * n + i;
+        const double nan = __builtin_nan("");
+        store3(A.L.power, at, lit ? lp : v3(nan, nan, nan));
+        A.L.in_shadow[at] = lit ? (in_shadow ? 1 : 0) : 255;
+        if (STATS) st.v[ST_BYTES_VECTOR] += 24u + 1u;
+      }
+    }
+    flush_item_stats<STATS>(st, A.counters, lane);
+  }
+}
+
+constexpr int kRayTreeCompactThreads = 1024;
+
+// One workgroup of kRayTreeCompactThreads: thread t owns the rays [t per, (t + 1) per); an exclusive scan of the threads'
+// child counts gives each its place in the next layer (refine_compact_kernel's scan: the same layer gives the same
+// order).  Writes both child indices of every ray and the next layer's ray count -- 64 bits: it is the host that
+// refuses 2^31 or more.
+__global__ void __launch_bounds__(kRayTreeCompactThreads) raytree_compact_kernel(RayTreeLayer L, uint32_t n,
+                                                                                 unsigned long long *count_out) {
+  __shared__ unsigned long long s_count[kRayTreeCompactThreads];
+  const unsigned t = threadIdx.x;
+  const unsigned per = (n + kRayTreeCompactThreads - 1) / kRayTreeCompactThreads;
+  const unsigned i0 = min(t * per, n), i1 = min(i0 + per, n);
+  unsigned long long mine = 0;
+  for (unsigned i = i0; i < i1; i++) {
+    const unsigned f = L.spawn[i];
+    mine += (f & 1u) + (f >> 1);
+  }
+  s_count[t] = mine;
+  __syncthreads();
+  // inclusive scan (Hillis-Steele) over the threads' counts
+  for (unsigned d = 1; d < kRayTreeCompactThreads; d <<= 1) {
+    const unsigned long long add = t >= d ? s_count[t - d] : 0ull;
+    __syncthreads();
+    s_count[t] += add;
+    __syncthreads();
+  }
+  const unsigned long long total = s_count[kRayTreeCompactThreads - 1];
+  if (t == 0) *count_out = total;
+  if (total >= 0x80000000ull) return;  // no index of such a layer fits: the host fails the call
+  int32_t j = (int32_t)(s_count[t] - mine);
+  for (unsigned i = i0; i < i1; i++) {
+    const unsigned f = L.spawn[i];
+    L.child_refl[i] = (f & 1u) ? j++ : -1;
+    L.child_refr[i] = (f & 2u) ? j++ : -1;
+  }
+}
+
+struct RayTreeSpawnArgs {
+  RayTreeLayer parent, child;
+  uint32_t n_parent;
+  const mt_material *mtls;
+};
+
+__global__ __launch_bounds__(256) void raytree_spawn_kernel(RayTreeSpawnArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_parent) return;
+  const int cr = A.parent.child_refl[i], ct = A.parent.child_refr[i];
+  if (cr < 0 && ct < 0) return;
+  const V3 dir = v3_load(A.parent.ray + i * 6 + 3);
+  const V3 Pt = v3_load(A.parent.point + i * 3);
+  const double coef = A.parent.coef[i];
+  const bool in_object = A.parent.in_object[i] != 0;
+  if (cr >= 0) {
+    V3 Nn = v3_load(A.parent.normal + i * 3);  // as GetNormal returned it, :38
+    if (dot(Nn, -dir) < 0.0) Nn = -Nn;         // :42-45
+    const V3 Rd = dir - Nn * (2 * dot(dir, Nn));  // :68-69
+    const V3 ro = Pt + (Rd * 0.0001);             // :70-74
+    double *r = A.child.ray + (size_t)cr * 6;
+    r[0] = ro.x; r[1] = ro.y; r[2] = ro.z; r[3] = Rd.x; r[4] = Rd.y; r[5] = Rd.z;
+    A.child.coef[cr] = coef * A.mtls[A.parent.material[i]].reflectance;  // :187
+    A.child.in_object[cr] = in_object ? 1 : 0;
+  }
+  if (ct >= 0) {
+    const V3 rdir = normalized(dir);  // :208-212 (direction unchanged, re-normalised)
+    const V3 ro = Pt + rdir * 0.00001;
+    double *r = A.child.ray + (size_t)ct * 6;
+    r[0] = ro.x; r[1] = ro.y; r[2] = ro.z; r[3] = rdir.x; r[4] = rdir.y; r[5] = rdir.z;
+    A.child.coef[ct] = coef;                    // :223
+    A.child.in_object[ct] = in_object ? 0 : 1;  // :222
+  }
+}
+
+struct RayTreeShadeArgs {
+  RayTreeLayer L;
+  const double *child_color;  // the next layer's colours; nullptr: this is the deepest layer
+  uint32_t n_rays;
+  int32_t n_lights;
+  const mt_material *mtls;
+  const mt_light *d_lights;   // ARG_LIGHTS = false
+  uint8_t *out_rgb;           // layer 0: chunk-local row-major RGB8; else nullptr
+  mt_light lights[kShadeArgLights];  // ARG_LIGHTS = true
+};
+
+template <bool ARG_LIGHTS>
+__global__ __launch_bounds__(256) void raytree_shade_kernel(RayTreeShadeArgs A) {
+  const size_t n = (size_t)A.n_rays;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  V3 color = v3(0, 0, 0);
+  const V3 Pt = v3_load(A.L.point + i * 3);
+  if (Pt.x == Pt.x) {  // (a miss: background, mythtracer.cc:23-31)
+    const V3 dir = v3_load(A.L.ray + i * 6 + 3);
+    V3 Nn = v3_load(A.L.normal + i * 3);  // as GetNormal returned it, :38
+    const V3 towards_camera = -dir;
+    double normal_ray_dot = dot(Nn, towards_camera);
+    if (normal_ray_dot < 0.0) {  // :42-45
+      Nn = -Nn;
+      normal_ray_dot = dot(Nn, towards_camera);
+    }
+    const int mtl = A.L.material[i];
+    if (mtl < 0) {  // :49-52
+      normal_ray_dot = (normal_ray_dot + 1.0) * 0.5;
+      color = v3(normal_ray_dot, normal_ray_dot, normal_ray_dot);
+    } else {
+      const mt_material *m = A.mtls + mtl;
+      const V3 surf = v3_load(A.L.albedo + i * 3);            // :58-64
+      const V3 Rd = dir - Nn * (2 * dot(dir, Nn));            // :68-69
+      const double refl_dot = dot(Rd, towards_camera);        // :170
+      const V3 kd = v3(m->diffuse[0], m->diffuse[1], m->diffuse[2]);
+      for (int li = 0; li < A.n_lights; li++) {
+        const mt_light *lt = ARG_LIGHTS ? A.lights + li : A.d_lights + li;
+        const V3 lpos = v3(lt->position[0], lt->position[1], lt->position[2]);
+        const V3 amb = v3(lt->ambient[0], lt->ambient[1], lt->ambient[2]);
+        const V3 ld = normalized(lpos - Pt);                  // :79-80
+        color = color + amb * surf;                           // :83-84
+        const size_t at = (size_t)li * n + i;
+        V3 lp = v3_load(A.L.power + at * 3);
+        lp.x = std_max(lp.x, amb.x);                          // :159-161
+        lp.y = std_max(lp.y, amb.y);
+        lp.z = std_max(lp.z, amb.z);
+        const V3 ldiff = v3(lt->diffuse[0], lt->diffuse[1], lt->diffuse[2]);
+        color = color + kd * surf * dot(ld, Nn) * ldiff * lp;  // :163-167
+        if (A.L.in_shadow[at] == 0 && refl_dot > 0) {         // :169-177
+          const V3 ks = v3(m->specular[0], m->specular[1], m->specular[2]);
+          const V3 ls = v3(lt->specular[0], lt->specular[1], lt->specular[2]);
+          color = color + ks * surf * ::pow(refl_dot, m->specular_exp) * ls;
+        }
+      }
+      const int cr = A.L.child_refl[i], ct = A.L.child_refr[i];
+      if (cr >= 0) color = color + v3_load(A.child_color + (size_t)cr * 3) * m->reflectance;  // :185-188
+      if (ct >= 0) {                                                                          // :220-224
+        const V3 tf = v3(m->transmission_filter[0], m->transmission_filter[1], m->transmission_filter[2]);
+        color = color + v3_load(A.child_color + (size_t)ct * 3) * tf * m->transparency;
+      }
+    }
+  }
+  if (A.out_rgb != nullptr) {
+    uint8_t *o = A.out_rgb + (size_t)A.L.pixel[i] * 3;
+    o[0] = channel_to_u8(color.x);  // V3DtoRGB, :235-241
+    o[1] = channel_to_u8(color.y);
+    o[2] = channel_to_u8(color.z);
+  } else {
+    store3(A.L.color, i, color);
+  }
+}
+
+#define MT_INSTANTIATE_RT(DEEP_)                                                          \
+  template __global__ void raytree_trace_kernel<true, DEEP_>(DevScene, RayTreeTraceArgs);  \
+  template __global__ void raytree_trace_kernel<false, DEEP_>(DevScene, RayTreeTraceArgs);
+MT_INSTANTIATE_RT(0)
+MT_INSTANTIATE_RT(1)
+MT_INSTANTIATE_RT(2)
+#undef MT_INSTANTIATE_RT
+template __global__ void raytree_shade_kernel<true>(RayTreeShadeArgs);
+template __global__ void raytree_shade_kernel<false>(RayTreeShadeArgs);
+
+}  // namespace mt

@@ -13,6 +13,7 @@
 
 struct mt_scene;
 struct mt_stats;
+struct mt_raytree;
 
 namespace raytracer {
 using math3d::V3D;
@@ -83,6 +84,40 @@ struct LightBuffer {
   std::vector<uint8_t> in_shadow;
 };
 
+// The ray-tree buffer of a frame or chunk (extension; mt_raytree_create in mythtracer_hip.h): the whole call tree of
+// TraceRayWorker for every pixel, traced once by BuildRayTree and kept on the GPU, from which ShadeRayTree makes the
+// full-depth frame under edited light colours without tracing a ray.  Move-only; destroys its mt_raytree.  It belongs
+// to the MythTracer that built it and must be destroyed (or Reset) before that MythTracer, and before anything that
+// uploads the scene again (LoadObj, SetDevices).
+class RayTree {
+ public:
+  RayTree() = default;
+  ~RayTree() { Reset(); }
+  RayTree(const RayTree&) = delete;
+  RayTree& operator=(const RayTree&) = delete;
+  RayTree(RayTree&& o) noexcept : tree_(o.tree_) { o.tree_ = nullptr; }
+  RayTree& operator=(RayTree&& o) noexcept {
+    if (this != &o) {
+      Reset();
+      tree_ = o.tree_;
+      o.tree_ = nullptr;
+    }
+    return *this;
+  }
+  void Reset();
+  bool Empty() const { return tree_ == nullptr; }
+  mt_raytree* Get() const { return tree_; }
+  // layers, rays of layer k (0 beyond the last layer), lights, bytes of HBM held; zeros for an empty handle
+  int Layers() const;
+  long long Rays(int layer) const;
+  int Lights() const;
+  unsigned long long Bytes() const;
+
+ private:
+  friend class MythTracer;
+  mt_raytree* tree_ = nullptr;
+};
+
 class MythTracer {
  public:
   MythTracer();
@@ -149,6 +184,18 @@ class MythTracer {
   // updated.  The result is what a new RayTraceLightBuffer gives if only the listed lights moved since the planes were
   // made.  Refused with several devices, like its siblings; LastStats() describes the call.
   bool UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer);
+  // The ray tree of a W x H frame, or of chunk->chunk_* (its camera and image size), to the recursion level of
+  // SetMaxRecursionLevel under GetScene()->lights (mt_raytree_create); what `tree` held before is destroyed.
+  // SetSupersampling does not apply.  Refused with a message after SetDevices with several devices, like
+  // RayTraceGBuffer.  LastStats() describes the call: its ray counts are those of RayTrace for the same frame.
+  bool BuildRayTree(int image_width, int image_height, Camera* camera, RayTree* tree);
+  bool BuildRayTree(WorkChunk* chunk, RayTree* tree);
+  // The frame RayTrace would give -- at the level the tree was built with -- under the CURRENT GetScene()->lights,
+  // from the stored tree without tracing a ray (mt_raytree_shade): for lights whose ambient, diffuse or specular were
+  // edited since BuildRayTree.  Their count must be the tree's (checked) and so must their positions (not checked).
+  // The chunk form writes chunk->output_bitmap; the chunk must have the tree's size.
+  bool ShadeRayTree(const RayTree& tree, std::vector<uint8_t>* output_bitmap);
+  bool ShadeRayTree(const RayTree& tree, WorkChunk* chunk);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

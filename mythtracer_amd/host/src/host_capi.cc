@@ -400,6 +400,57 @@ int mth_shade_direct(void* p, const double* cam7, int iw, int ih, int cx, int cy
   return 1;
 }
 
+// MythTracer::BuildRayTree(WorkChunk*, RayTree*) at the facade's recursion level and lights: a new RayTree on the heap
+// (mth_raytree_free), NULL on failure.
+void* mth_raytree_build(void* p, const double* cam7, int iw, int ih, int cx, int cy, int cw, int ch, uint64_t* stats8,
+                        double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  WorkChunk chunk{iw, ih, cx, cy, cw, ch, MakeCamera(cam7), {}, {}};
+  raytracer::RayTree* t = new raytracer::RayTree();
+  if (!h->mt.BuildRayTree(&chunk, t)) {
+    delete t;
+    return nullptr;
+  }
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return t;
+}
+
+void mth_raytree_free(void* t) { delete static_cast<raytracer::RayTree*>(t); }
+
+// the mt_raytree behind a RayTree (for mt_raytree_info / mt_raytree_read_layer)
+void* mth_raytree_handle(void* t) { return t ? static_cast<raytracer::RayTree*>(t)->Get() : nullptr; }
+
+// MythTracer::ShadeRayTree(tree, &bitmap) under the facade's current lights; rgb holds rgb_bytes bytes.
+int mth_raytree_shade(void* p, void* t, uint8_t* rgb, size_t rgb_bytes, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  if (t == nullptr) {
+    h->shim_error = "the RayTree is NULL";
+    return 0;
+  }
+  std::vector<uint8_t> bitmap;
+  if (!h->mt.ShadeRayTree(*static_cast<raytracer::RayTree*>(t), &bitmap)) return 0;
+  if (bitmap.size() != rgb_bytes) {
+    h->shim_error = "the bitmap was sized for " + std::to_string(rgb_bytes) + " bytes, the tree's chunk has " +
+                    std::to_string(bitmap.size());
+    return 0;
+  }
+  memcpy(rgb, bitmap.data(), bitmap.size());
+  if (ms2) {
+    ms2[0] = h->mt.LastStats().kernel_ms;
+    ms2[1] = h->mt.LastStats().total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::UpdateLightBuffer(GBuffer, lights, LightBuffer*) under the facade's lights.  gb_planes[2] = point
 // (doubles), material (int32) of the cw x ch chunk; lb_channels = LightBuffer::k* bits, lb_planes[2] = power, in_shadow
 // for n_lights lights (each NULL or sized for them), updated in place: the planes of the listed lights only.

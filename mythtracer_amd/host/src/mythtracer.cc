@@ -595,6 +595,109 @@ bool MythTracer::ShadeDirect(WorkChunk* chunk, const GBuffer& gbuffer, const Lig
   return true;
 }
 
+void RayTree::Reset() {
+  if (tree_) mt_raytree_destroy(tree_);
+  tree_ = nullptr;
+}
+
+namespace {
+mt_raytree_desc DescOf(const mt_raytree* t) {
+  mt_raytree_desc d;
+  memset(&d, 0, sizeof d);
+  if (t) (void)mt_raytree_info(t, &d);
+  return d;
+}
+}  // namespace
+
+int RayTree::Layers() const { return DescOf(tree_).n_layers; }
+long long RayTree::Rays(int layer) const {
+  return layer >= 0 && layer <= MT_MAX_RECURSION ? (long long)DescOf(tree_).n_rays[layer] : 0;
+}
+int RayTree::Lights() const { return DescOf(tree_).n_lights; }
+unsigned long long RayTree::Bytes() const { return DescOf(tree_).bytes; }
+
+bool MythTracer::BuildRayTree(int image_width, int image_height, Camera* camera, RayTree* tree) {
+  WorkChunk chunk{image_width, image_height, 0, 0, image_width, image_height, *camera, {}, {}};
+  return BuildRayTree(&chunk, tree);
+}
+
+bool MythTracer::BuildRayTree(WorkChunk* chunk, RayTree* tree) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device, as in RayTraceGBuffer)
+  if (tree == nullptr) return refuse("RayTree is NULL");
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (chunk->chunk_width <= 0 || chunk->chunk_height <= 0) return refuse("empty chunk");
+  if (max_level_ < 0 || max_level_ > MT_MAX_RECURSION) {
+    return refuse("recursion level " + std::to_string(max_level_) + " outside 0 .. " + std::to_string(MT_MAX_RECURSION));
+  }
+  tree->Reset();
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("ray tree failed: ") + mt_last_error());
+  }
+  const mt_sensor ms = SensorOf(*chunk);
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  tree->tree_ = mt_raytree_create(dev_, &ms, chunk->image_width, chunk->image_height, chunk->chunk_x, chunk->chunk_y,
+                                  chunk->chunk_width, chunk->chunk_height, max_level_, &st);
+  if (tree->tree_ == nullptr) return refuse(std::string("ray tree failed: ") + mt_last_error());
+  stats_ = RenderStats{};
+  stats_.rays_primary = st.rays_primary;
+  stats_.rays_secondary = st.rays_secondary;
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.shaded_hits = st.shaded_hits;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
+bool MythTracer::ShadeRayTree(const RayTree& tree, std::vector<uint8_t>* output_bitmap) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (output_bitmap == nullptr) return refuse("the output bitmap is NULL");
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (tree.Empty()) return refuse("the RayTree is empty: BuildRayTree first");
+  const mt_raytree_desc d = DescOf(tree.Get());
+  if ((size_t)d.n_lights != scene.lights.size()) {
+    return refuse("the RayTree was made with another number of lights: a new BuildRayTree is needed");
+  }
+  output_bitmap->resize((size_t)d.chunk_w * (size_t)d.chunk_h * 3);
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  if (mt_raytree_shade(tree.Get(), reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size(),
+                       output_bitmap->data(), &st) != MT_OK) {
+    return refuse(std::string("ray-tree shade failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
+bool MythTracer::ShadeRayTree(const RayTree& tree, WorkChunk* chunk) {
+  if (!tree.Empty()) {
+    const mt_raytree_desc d = DescOf(tree.Get());
+    if (d.chunk_w != chunk->chunk_width || d.chunk_h != chunk->chunk_height) {
+      error_ = "the RayTree must describe the chunk";
+      fprintf(stderr, "error: %s\n", error_.c_str());
+      return false;
+    }
+  }
+  return ShadeRayTree(tree, &chunk->output_bitmap);
+}
+
 bool MythTracer::UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer) {
   auto refuse = [&](const std::string& why) {
     error_ = why;

@@ -167,3 +167,20 @@ def compose_adaptive(plain_rgb: np.ndarray, ss_rgb: np.ndarray, mask: np.ndarray
     bx = (np.arange(cw) + cx) // 8 - x0
     px = m[by[:, None], bx[None, :]]
     return np.where(px[:, :, None], np.asarray(ss_rgb), np.asarray(plain_rgb)).astype(np.uint8)
+
+
+# ---- the ray-tree buffer (include/mythtracer_hip.h, mt_raytree_create ff.; csrc/mt_raytree.h)
+def raytree_layer0_order(chunk_w: int, chunk_h: int) -> np.ndarray:
+    """The order of a ray tree's layer 0 (numpy restatement of raytree_layer0_index, csrc/mt_raytree.h): entry i = the
+    chunk-local row-major pixel index of ray i.  The 8 x 8 blocks of the CHUNK in row-major order, within a block its
+    pixels in row-major order; a block cut by the chunk's right or bottom edge holds only its pixels, so the list has
+    chunk_w * chunk_h entries.  A fixed function of (chunk_w, chunk_h)."""
+    if chunk_w <= 0 or chunk_h <= 0:
+        raise ValueError("chunk %dx%d is empty" % (chunk_w, chunk_h))
+    out = []
+    for by in range(0, chunk_h, 8):
+        ys = np.arange(by, min(by + 8, chunk_h))
+        for bx in range(0, chunk_w, 8):
+            xs = np.arange(bx, min(bx + 8, chunk_w))
+            out.append((ys[:, None] * chunk_w + xs[None, :]).reshape(-1))
+    return np.concatenate(out).astype(np.int32)
