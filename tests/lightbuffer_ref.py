@@ -147,17 +147,21 @@ def ref_lightbuffer(orc, gb, lights):
     return out
 
 
-def shade(orc, gb, lb, lights):
+def shade(orc, gb, lb, lights, materials=None, hit=None, info=None):
     """mythtracer.cc:38-177 and V3DtoRGB per pixel from the planes: the frame of the direct term, (ch, cw, 3) uint8.
     gb: oracle_gbuffer's dict (rays, point, normal -- unflipped --, albedo, material in the oracle's numbering, prim);
-    lb: power and in_shadow.  pow is math.pow: glibc's, what the oracle and the reference call."""
-    ch, cw = gb["prim"].shape
+    lb: power and in_shadow.  pow is math.pow: glibc's, what the oracle and the reference call.
+    For planes no scene made (tests/synthetic_inputs.py): `materials` = a table (n_materials, 16) of material values in
+    place of the oracle scene's (orc may be None), its numbering the material plane's -- an index outside the table is
+    "no material", as shade_direct_kernel defines it --, and `hit` (ch, cw) bool in place of prim >= 0.  info: a dict
+    that receives "specular" (ch, cw) bool, the pixels that take the specular branch (:169-177) for some light."""
+    ch, cw = gb["material"].shape
     n = ch * cw
     L = np.asarray(lights, dtype=np.float64).reshape(-1, 12)
     assert lb["power"].shape == (len(L), ch, cw, 3) and lb["in_shadow"].shape == (len(L), ch, cw)
-    mats = orc.materials()
+    table = np.array([m[1] for m in orc.materials()] if materials is None else materials, dtype=np.float64).reshape(-1, 16)
     direction = gb["rays"][..., 3:].reshape(n, 3)
-    hit = gb["prim"].reshape(n) >= 0
+    hit = (gb["prim"] >= 0 if hit is None else np.asarray(hit, dtype=bool)).reshape(n)
     material = gb["material"].reshape(n)
     color = np.zeros((n, 3))                                    # :23-31 for the misses
     h = np.nonzero(hit)[0]
@@ -168,7 +172,7 @@ def shade(orc, gb, lb, lights):
     flip = nrd < 0.0                                            # :42-45
     normal[flip] = -normal[flip]
     nrd[flip] = _dot(normal[flip], towards_camera[flip])
-    bare = material[h] < 0                                      # :49-52
+    bare = (material[h] < 0) | (material[h] >= len(table))      # :49-52
     g = (nrd[bare] + 1.0) * 0.5
     color[h[bare]] = np.stack([g, g, g], axis=1)
     s = ~bare
@@ -176,11 +180,12 @@ def shade(orc, gb, lb, lights):
     d, normal, towards_camera = d[s], normal[s], towards_camera[s]
     Pt = gb["point"].reshape(n, 3)[hs]
     surf = gb["albedo"].reshape(n, 3)[hs]
-    values = np.array([mats[m][1] for m in material[hs]]).reshape(len(hs), 16)
+    values = table[material[hs]].reshape(len(hs), 16)
     kd, ks, ns = values[:, 3:6], values[:, 6:9], values[:, 9]
     reflected = d - normal * (2 * _dot(d, normal))[:, None]     # :68-69 (ray.direction.Dot(normal))
     refl_dot = _dot(reflected, towards_camera)                  # :170
     c = np.zeros((len(hs), 3))
+    specular = np.zeros(n, dtype=bool)
     for li, light in enumerate(L):
         lpos, amb, ldiff, lspec = light[0:3], light[3:6], light[6:9], light[9:12]
         ld = _norm(lpos[None, :] - Pt)                          # :79-80
@@ -190,9 +195,12 @@ def shade(orc, gb, lb, lights):
         c = c + kd * surf * _dot(ld, normal)[:, None] * ldiff[None, :] * lp  # :163-167 (light_direction.Dot(normal))
         spec = (lb["in_shadow"][li].reshape(n)[hs] == 0) & (refl_dot > 0)      # :169-177
         k = np.nonzero(spec)[0]
+        specular[hs[k]] = True
         p = np.array([math.pow(a, b) for a, b in zip(refl_dot[k], ns[k])]).reshape(len(k))
         c[k] = c[k] + ks[k] * surf[k] * p[:, None] * lspec[None, :]
     color[hs] = c
+    if info is not None:
+        info["specular"] = specular.reshape(ch, cw)
     rgb = np.zeros((n, 3), dtype=np.uint8)
     for i in range(n):
         rgb[i] = orclib.v3d_to_rgb(color[i])

@@ -168,9 +168,10 @@ def truncated(tree, max_depth):
     return finish(dict(layers=layers, max_depth=max_depth, n_lights=tree["n_lights"]))
 
 
-def direct_term(orc, lay, lights):
+def direct_term(orc, lay, lights, info=None):
     """mythtracer.cc:38-177 per ray of a layer from its planes and the stored direction: lightbuffer_ref.shade before
-    V3DtoRGB -- black for a miss, the grey of :49-52 without a material -- as (n, 3) float64."""
+    V3DtoRGB -- black for a miss, the grey of :49-52 without a material -- as (n, 3) float64.  info: a dict that
+    receives "specular" (n,) bool, the rays that take the specular branch (:169-177) for some light."""
     n = len(lay["ray"])
     L = np.asarray(lights, dtype=np.float64).reshape(-1, 12)
     assert lay["power"].shape == (len(L), n, 3), (lay["power"].shape, len(L), n)
@@ -193,6 +194,7 @@ def direct_term(orc, lay, lights):
     reflected = d - normal * (2 * lr._dot(d, normal))[:, None]  # :68-69
     refl_dot = lr._dot(reflected, towards_camera)               # :170
     c = np.zeros((len(hs), 3))
+    specular = np.zeros(n, dtype=bool)
     for li, light in enumerate(L):
         lpos, amb, ldiff, lspec = light[0:3], light[3:6], light[6:9], light[9:12]
         ld = lr._norm(lpos[None, :] - Pt)                       # :79-80
@@ -202,27 +204,38 @@ def direct_term(orc, lay, lights):
         c = c + kd * surf * lr._dot(ld, normal)[:, None] * ldiff[None, :] * lp  # :163-167
         spec = (lay["in_shadow"][li][hs] == 0) & (refl_dot > 0)                # :169-177
         k = np.nonzero(spec)[0]
+        specular[hs[k]] = True
         p = np.array([math.pow(a, b) for a, b in zip(refl_dot[k], ns[k])]).reshape(len(k))
         c[k] = c[k] + ks[k] * surf[k] * p[:, None] * lspec[None, :]
     color[hs] = c
+    if info is not None:
+        info["specular"] = specular
     return color
 
 
 def v3d_to_rgb(color):
-    """MythTracer::V3DtoRGB (mythtracer.cc:235-241) over (n, 3): > 1 -> 255, < 0 -> 0, else the truncated v * 255."""
-    assert not np.isnan(color).any()
-    inside = np.clip(color, 0.0, 1.0)
+    """MythTracer::V3DtoRGB (mythtracer.cc:235-241) over (n, 3): > 1 -> 255, < 0 -> 0, else the truncated v * 255; a
+    NaN -- light colours no scene file holds -- gives 0, as orclib.v3d_to_rgb and channel_to_u8 define it."""
+    inside = np.clip(np.where(np.isnan(color), 0.0, color), 0.0, 1.0)
     return np.where(color > 1.0, 255, np.where(color < 0.0, 0, (inside * 255).astype(np.uint8))).astype(np.uint8)
 
 
-def shade(orc, tree, lights, cw, ch):
+def shade(orc, tree, lights, cw, ch, info=None):
     """The frame of a tree under `lights` (count and positions the tree's): layers bottom-up, per ray the direct term,
     + colour[child_refl] * reflectance (:185-188), + colour[child_refr] * transmission_filter * transparency as
-    :220-224 associates it; layer 0 through V3DtoRGB to the ray's pixel.  (ch, cw, 3) uint8."""
+    :220-224 associates it; layer 0 through V3DtoRGB to the ray's pixel.  (ch, cw, 3) uint8.  info: a dict that
+    receives "specular" (ch, cw) bool, the pixels with a ray in their tree that takes the specular branch."""
     mats = orc.materials()
-    below = None
+    below = spec_below = None
     for lay in reversed(tree["layers"]):
-        color = direct_term(orc, lay, lights)
+        term = {}
+        color = direct_term(orc, lay, lights, term)
+        spec = term["specular"]
+        for name in ("child_refl", "child_refr"):
+            k = np.nonzero(lay[name] >= 0)[0]
+            if len(k):
+                spec[k] |= spec_below[lay[name][k]]
+        spec_below = spec
         values = np.array([mats[m][1] if m >= 0 else np.zeros(16) for m in lay["material"]]).reshape(len(color), 16)
         k = np.nonzero(lay["child_refl"] >= 0)[0]
         if len(k):
@@ -233,4 +246,8 @@ def shade(orc, tree, lights, cw, ch):
         below = color
     rgb = np.zeros((cw * ch, 3), dtype=np.uint8)
     rgb[tree["layers"][0]["pixel"]] = v3d_to_rgb(below)
+    if info is not None:
+        px = np.zeros(cw * ch, dtype=bool)
+        px[tree["layers"][0]["pixel"]] = spec_below
+        info["specular"] = px.reshape(ch, cw)
     return rgb.reshape(ch, cw, 3)
