@@ -559,6 +559,39 @@ int mt_raytree_read_layer(mt_raytree *tree, int layer, const mt_raytree_layer *o
 int mt_raytree_shade(mt_raytree *tree, const mt_light *lights, int n_lights, uint8_t *out_rgb, mt_stats *stats);
 int mt_raytree_shade_device(mt_raytree *tree, const mt_light *lights, int n_lights, void *d_rgb, void *stream);
 
+/* A moved light: the planes of the listed lights again in EVERY layer of a ray tree, from the tree's own stored hits.
+ * The shape of the tree does not depend on the lights -- rays, hits, G-buffer planes and child indices of all layers
+ * stay as they are --, so a light that moved since the tree was made costs its shadow loops and nothing else: no
+ * sensor is used, no primary or secondary ray is traced.  (No reference counterpart; mt_update_lightbuffer's
+ * counterpart at depth.)
+ * For every listed light l, every layer k and every ray i of that layer with point[i][0] not NaN and
+ * 0 <= material[i] < the scene's material count, the shadow loop of mythtracer.cc:90-156 runs from the stored point
+ * under the scene's CURRENT light l (mt_scene_set_lights), exactly as mt_raytree_create runs it (the same operations
+ * in the same order), and power / in_shadow are stored at [l][i] of that layer.  Every other ray of the layer gets NaN
+ * and 255 there.  Planes of unlisted lights are not written, not one byte, and nothing else in the tree is: not rays,
+ * G-buffer planes, child indices or `pixel`.
+ * CONTRACT: a tree made under lights A, after mt_scene_set_lights(B) -- same count, positions different at the listed
+ * indices only -- and an update at those indices, is bit-identical in every plane of every layer to mt_raytree_create
+ * under B for the same scene, sensor, chunk and max_depth (power with NaN = NaN, bytes and indices exactly); so
+ * mt_raytree_shade(tree, B) is mt_render_chunk(..., max_depth, ...) under B byte for byte.
+ * `light_idx` is a HOST array in both forms; each index at most once, in any order.
+ *   mt_raytree_update_lights: synchronous.  stats (nullable): rays_primary = rays_secondary = shaded_hits = 0,
+ *     rays_shadow = the loop iterations of the listed lights over all layers, the traversal's counters, kernel_ms =
+ *     the kernel by HIP events, total_ms = wall time of the call; with stats set the counters are switched on for the
+ *     call.  A tripped loop bound is MT_ERR_INTERNAL.
+ *   mt_raytree_update_lights_device: fully asynchronous on `stream` -- no synchronisation, no read-back; counters as
+ *     for mt_render_chunk_device.  Up to 8 indices travel with the launch; a longer list is copied by the stream into a
+ *     buffer the scene owns and must stay unchanged until the stream has reached the call.
+ * One kernel next to the frame kernels, ONE launch for all layers and all listed lights (mt::raytree_update_kernel; a
+ * work item is 64 consecutive rays of one layer x one listed light); more than 0xfffffff0 items are MT_ERR_ARG.  One
+ * call in flight per scene and per tree, as for the siblings (they share the work counter and the statistics); cost
+ * history, engine choice, forecasts and mt_scene_kernel_times are left alone.
+ * Argument checks come before any device call, in this order: the tree (NULL), the list (n_idx <= 0 or NULL), the
+ * scene's current light count unequal to the tree's, an index outside 0 .. n_lights - 1, an index listed twice.  All
+ * are MT_ERR_ARG; a tree of zero lights refuses every list. */
+int mt_raytree_update_lights(mt_raytree *tree, const int32_t *light_idx, int n_idx, mt_stats *stats);
+int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, int n_idx, void *stream);
+
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into
  * WorkChunks, every worker renders chunks with the full-image sensor from its

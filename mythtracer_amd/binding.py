@@ -33,6 +33,7 @@ HIP_SYMBOLS = [
     "mt_refine_mask_device", "mt_render_chunk_adaptive", "mt_render_chunk_adaptive_device",
     "mt_raytree_create", "mt_raytree_destroy", "mt_raytree_info", "mt_raytree_read_layer",
     "mt_raytree_shade", "mt_raytree_shade_device",
+    "mt_raytree_update_lights", "mt_raytree_update_lights_device",
 ]
 MT_MAX_RECURSION = 16
 
@@ -315,6 +316,8 @@ class HipAbi:
         L.mt_raytree_read_layer.argtypes = [vp, ci, C.POINTER(mt_raytree_layer)]
         L.mt_raytree_shade.argtypes = [vp, vp, ci, vp, vp]
         L.mt_raytree_shade_device.argtypes = [vp, vp, ci, vp, vp]
+        L.mt_raytree_update_lights.argtypes = [vp, vp, ci, vp]
+        L.mt_raytree_update_lights_device.argtypes = [vp, vp, ci, vp]
         ps = C.POINTER(mt_sensor)
         L.mt_render_chunk_adaptive.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
         L.mt_render_chunk_adaptive_device.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
@@ -692,6 +695,19 @@ class HipAbi:
         l = _f64(lights).reshape(-1, 12)
         self.check(self.lib.mt_raytree_shade_device(tree, _ptr(l), l.shape[0], d_rgb, stream))
 
+    def raytree_update_lights(self, tree, light_indices) -> dict:
+        """mt_raytree_update_lights after set_lights(the moved lights): the planes of the lights in `light_indices`
+        in every layer of `tree` traced again from the stored hits.  Returns the stats dict."""
+        idx = _i32(light_indices).reshape(-1)
+        st = mt_stats()
+        self.check(self.lib.mt_raytree_update_lights(tree, _ptr(idx), len(idx), C.addressof(st)))
+        return st.as_dict()
+
+    def raytree_update_lights_device(self, tree, light_indices, stream=None):
+        """mt_raytree_update_lights_device: `light_indices` a host list; asynchronous on `stream`."""
+        idx = _i32(light_indices).reshape(-1)
+        self.check(self.lib.mt_raytree_update_lights_device(tree, _ptr(idx), len(idx), stream))
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -831,6 +847,7 @@ def host_lib():
     L.mth_raytree_handle.argtypes = [vp]
     L.mth_raytree_handle.restype = vp
     L.mth_raytree_shade.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.mth_raytree_update.argtypes = [vp, vp, vp, ci, vp, vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mth_chunk_serialize_input.argtypes = [vp, vp]
@@ -858,8 +875,8 @@ def sensor_ray(cam7, w, h, x, y):
 
 
 class RayTree:
-    """raytracer::RayTree as MythTracer.raytree returns it: `.info`, `.layer(k)`, `.shade(lights=None)`, `.close()`.
-    Close it before its MythTracer."""
+    """raytracer::RayTree as MythTracer.raytree returns it: `.info`, `.layer(k)`, `.shade(lights=None)`,
+    `.update(light_indices, lights=None)`, `.close()`.  Close it before its MythTracer."""
 
     def __init__(self, mt, handle, counters, kernel_ms, total_ms):
         self.mt, self.h = mt, handle
@@ -889,6 +906,20 @@ class RayTree:
         if not self.mt.L.mth_raytree_shade(self.mt.h, self.h, _ptr(rgb), rgb.size, _ptr(ms)):
             raise RuntimeError("ShadeRayTree failed: " + self.mt.last_error())
         return dict(rgb=rgb, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def update(self, light_indices, lights=None) -> dict:
+        """MythTracer::UpdateRayTree: the planes of the lights in `light_indices`, in every layer, traced again under
+        the facade's lights (the moved ones among them).  `lights` (n x 12) replaces the facade's lights first, as in
+        shade; None keeps them.  Returns dict(counters, kernel_ms, total_ms)."""
+        self._tree()
+        if lights is not None:
+            self.mt.set_lights(lights)
+        idx = _i32(light_indices).reshape(-1)
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        if not self.mt.L.mth_raytree_update(self.mt.h, self.h, _ptr(idx), len(idx), _ptr(st), _ptr(ms)):
+            raise RuntimeError("UpdateRayTree failed: " + self.mt.last_error())
+        return dict(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
 
     def close(self):
         if getattr(self, "h", None):

@@ -332,6 +332,7 @@ struct LayoutKernels {
   void (*lightbuffer[2])(DevScene, LightBufferArgs);
   void (*lightbuffer_update[2])(DevScene, LightUpdateArgs);
   void (*raytree_trace[2])(DevScene, RayTreeTraceArgs);
+  void (*raytree_update[2])(DevScene, RayTreeUpdateArgs);
 };
 template <int D>
 LayoutKernels layout_kernels() {
@@ -340,7 +341,8 @@ LayoutKernels layout_kernels() {
           probe_kernel<D>, intersect_kernel<D>, {gbuffer_kernel<false, D>, gbuffer_kernel<true, D>},
           {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>},
           {lightbuffer_update_kernel<false, D>, lightbuffer_update_kernel<true, D>},
-          {raytree_trace_kernel<false, D>, raytree_trace_kernel<true, D>}};
+          {raytree_trace_kernel<false, D>, raytree_trace_kernel<true, D>},
+          {raytree_update_kernel<false, D>, raytree_update_kernel<true, D>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -2684,6 +2686,64 @@ int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_
   return MT_OK;
 }
 
+// mt_raytree_update_lights[_device]: checked before any device call, in the order of the header.
+int check_raytree_update_args(const mt_raytree *t, const int32_t *light_idx, int n_idx) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (n_idx <= 0 || !light_idx) return fail(MT_ERR_ARG, "bad light index list");
+  const int n_lights = t->info.n_lights;
+  if (t->scene->dev.n_lights != n_lights) {
+    return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", t->scene->dev.n_lights, n_lights);
+  }
+  for (int i = 0; i < n_idx; i++) {
+    if (light_idx[i] < 0 || light_idx[i] >= n_lights) {
+      return fail(MT_ERR_ARG, "light index %d outside the ray tree's %d lights", light_idx[i], n_lights);
+    }
+  }
+  // (no index is listed twice: at most n_lights entries are compared)
+  std::vector<bool> seen((size_t)n_lights, false);
+  for (int i = 0; i < n_idx; i++) {
+    if (seen[(size_t)light_idx[i]]) return fail(MT_ERR_ARG, "light index %d is listed twice", light_idx[i]);
+    seen[(size_t)light_idx[i]] = true;
+  }
+  return MT_OK;
+}
+
+// raytree_update_kernel over all layers x the listed lights, one launch; light_idx = host array
+int launch_raytree_update(mt_raytree *t, const int32_t *light_idx, int n_idx, hipStream_t stream) {
+  mt_scene *s = t->scene;
+  RayTreeUpdateArgs A{};
+  unsigned long long per_light = 0;
+  for (int k = 0; k < t->info.n_layers; k++) {
+    const RayTreeLayer &L = t->layer[k];
+    RayTreeUpdateLayer &U = A.layer[k];
+    U.point = L.point; U.material = L.material; U.power = L.power; U.in_shadow = L.in_shadow;
+    U.n_rays = (uint32_t)t->info.n_rays[k];
+    U.first_item = (uint32_t)per_light;  // (a layer has fewer than 2^31 rays: 17 layers stay below 2^32 items)
+    per_light += ((unsigned long long)t->info.n_rays[k] + 63) / 64;
+  }
+  const unsigned long long items = per_light * (unsigned long long)n_idx;
+  if (items > 0xfffffff0ull) return fail(MT_ERR_ARG, "too many work items (%llu)", items);
+  A.n_layers = t->info.n_layers;
+  A.n_materials = s->n_materials;
+  A.items_per_light = (unsigned)per_light;
+  A.n_items = (unsigned)items;
+  if (n_idx <= kUpdateArgLights) {
+    for (int i = 0; i < n_idx; i++) A.idx[i] = light_idx[i];
+  } else {
+    MT_TRY(s->d_update_idx.ensure((size_t)n_idx * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(s->d_update_idx, light_idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    A.d_idx = s->d_update_idx;
+  }
+  unsigned grid = 0;
+  MT_TRY(prepare_persistent_launch(s, items, &grid, stream));
+  A.counters = s->d_counters;
+  A.work_counter = s->d_gb_work;
+  hipLaunchKernelGGL(kernels_of(s->deep).raytree_update[s->stats_enabled ? 1 : 0], dim3(grid),
+                     dim3(s->waves_per_block * 64), s->lds_bytes, stream, s->dev, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
 // the counters so far, checked: no further layer after a tripped bound
 int raytree_read_counters(mt_scene *s, hipStream_t stream) {
   HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -2900,6 +2960,43 @@ int mt_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_
   HIP_TRY(hipStreamSynchronize(stream));
   if (stats) {
     memset(stats, 0, sizeof *stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
+  return MT_OK;
+}
+
+int mt_raytree_update_lights_device(mt_raytree *t, const int32_t *light_idx, int n_idx, void *stream) {
+  MT_TRY(check_raytree_update_args(t, light_idx, n_idx));
+  HIP_TRY(hipSetDevice(t->scene->device));
+  return launch_raytree_update(t, light_idx, n_idx, (hipStream_t)stream);
+}
+
+// The host form: the tree's planes are where they are; only the counters come back.
+int mt_raytree_update_lights(mt_raytree *t, const int32_t *light_idx, int n_idx, mt_stats *stats) {
+  MT_TRY(check_raytree_update_args(t, light_idx, n_idx));
+  const auto w0 = std::chrono::steady_clock::now();
+  mt_scene *s = t->scene;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t stream = nullptr;
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(t->ev0, stream));
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = launch_raytree_update(t, light_idx, n_idx, stream);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipEventRecord(t->ev1, stream));
+  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  MT_TRY(check_status(s->h_counters));
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    fill_stats(s->h_counters, stats);
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
     stats->kernel_ms = ms;

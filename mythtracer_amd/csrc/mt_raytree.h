@@ -25,6 +25,8 @@
 //                           states it (from the stored direction instead of the sensor), + colour[child_refl] *
 //                           reflectance (:185-188), + colour[child_refr] * transmission_filter * transparency
 //                           (:220-224); layer 0 ends in V3DtoRGB at the ray's pixel.
+//   raytree_update_kernel   a moved light: the listed lights' planes of ALL layers again from the stored point and
+//                           material planes, one launch (a work item is 64 rays of one layer x one listed light).
 // fp64 in the reference's order of operations (-ffp-contract=off), so a shaded tree is mt_render_chunk's frame byte for
 // byte.
 #pragma once
@@ -367,6 +369,158 @@ __global__ __launch_bounds__(256) void raytree_shade_kernel(RayTreeShadeArgs A) 
     store3(A.L.color, i, color);
   }
 }
+
+// raytree_update_kernel: the planes of the LISTED lights again in EVERY layer, from the stored hits -- a layer's `point`
+// and `material` planes hold, bit for bit, the two things a shadow loop takes from the ray's trace, and no ray, hit or
+// child index of the tree depends on a light.  No sensor, no primary or secondary trace_wave; the planes of the other
+// lights and everything else in the tree are not touched.  The listed lights' loops of all layers are independent, so
+// they all go out in ONE launch: a work item is 64 consecutive rays of one layer x one listed light, so that the few
+// items of the deep layers share the chip with layer 0's.  Within a light, place j belongs to layer l when it lies
+// between l's first_item and the next layer's; the items are handed out light-major and within a light from the LAST
+// place down (j = items_per_light - 1 - item % items_per_light): the deepest layers, whose waves mix rays of many
+// blocks and whose loops are the long ones, start first and layer 0's many coherent items fill in behind them
+// (measured against layer 0 first; the order changes no bit of the result).  A wave finds its layer
+// from the wave-uniform j.  A ray's loop runs when point[0] is not NaN and 0 <= material < n_materials; every other
+// ray of the layer gets NaN / 255.  raytree_trace_kernel's light loop body restated, that kernel is as it was.
+struct RayTreeUpdateLayer {
+  const double *point;      // [n][3]
+  const int32_t *material;  // [n]
+  double *power;            // [n_lights][n][3], plane l written for listed l only
+  uint8_t *in_shadow;       // [n_lights][n]
+  uint32_t n_rays;
+  uint32_t first_item;      // of this layer within one light's items
+};
+
+struct RayTreeUpdateArgs {
+  RayTreeUpdateLayer layer[MT_MAX_RECURSION + 1];
+  int32_t n_layers;
+  int32_t n_materials;
+  uint32_t items_per_light;          // sum over the layers of ceil(n_rays / 64)
+  uint32_t n_items;                  // items_per_light x listed lights
+  const int32_t *d_idx;              // the list when it has more than kUpdateArgLights entries, else nullptr
+  int32_t idx[kUpdateArgLights];
+  unsigned long long *counters;      // ST_COUNT
+  unsigned int *work_counter;        // zero at launch
+};
+
+template <bool STATS, int DEEP>
+__global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void raytree_update_kernel(DevScene S, RayTreeUpdateArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave_in_block = threadIdx.x >> 6;
+  WaveStack stk;
+  stk.bind(smem, wave_in_block, S.tree_depth, S.pack_shift, DEEP != 0);
+  const MT_CONST mt_material *mtls = as_const(S.mtls);
+  const MT_CONST mt_light *lights = as_const(S.lights);
+  LaneStats st;
+  st.clear();
+  // every iteration of a shadow loop crosses another surface
+  const int iteration_bound = S.n_tris + 2;
+  bool failed = false;
+  while (!failed) {
+    const unsigned item = fetch_work(A.work_counter, lane);
+    if (item >= A.n_items) break;
+    const unsigned k = item / A.items_per_light, j = A.items_per_light - 1u - item % A.items_per_light;  // (wave-uniform)
+    const int li = A.d_idx != nullptr ? A.d_idx[k] : A.idx[k];
+    int layer = 0;
+    while (layer + 1 < A.n_layers && j >= A.layer[layer + 1].first_item) layer++;
+    const RayTreeUpdateLayer L = A.layer[layer];
+    const size_t n = (size_t)L.n_rays;
+    const size_t i = (size_t)(j - L.first_item) * 64 + (size_t)lane;
+    const bool want = i < n;
+    V3 Pt = v3(0, 0, 0);
+    bool lit = false;
+    if (want) {
+      const V3 p = v3_load(L.point + i * 3);
+      const int mtl = L.material[i];
+      lit = p.x == p.x && mtl >= 0 && mtl < A.n_materials;
+      if (lit) Pt = p;
+      if (STATS) st.v[ST_BYTES_VECTOR] += 24u + 4u;
+    }
+    const MT_CONST mt_light *lt = lights + li;
+    const V3 lpos = v3(lt->position[0], lt->position[1], lt->position[2]);
+    // from here to the stores: raytree_trace_kernel's light loop body, the same operations in the same order
+    V3 start = Pt, lp = v3(1.0, 1.0, 1.0);  // :90, :94
+    bool in_shadow = false, traversing = false, running = lit;
+    V3 ro = Pt, ld = v3(0, 0, 1);
+    if (lit) {
+      ld = normalized(lpos - Pt);  // light_direction, :79-80
+      ro = Pt + (ld * 0.00001);    // :95-99
+    }
+    int iterations = 0;
+    while (__ballot(running) != 0ull) {
+      const TraceOut so = trace_wave<STATS, DEEP>(S.self, stk.base, lane, running, ro.x, ro.y, ro.z, ld.x, ld.y, ld.z);
+      add_trace_stats<STATS>(st, so);
+      if (so.status != DEV_OK || ++iterations > iteration_bound) {
+        if (lane == 0) {
+          atomicMax(A.counters + ST_STATUS, (unsigned long long)(so.status != DEV_OK ? so.status : DEV_ERR_PIXEL_BOUND));
+        }
+        failed = true;
+        break;
+      }
+      if (running) {  // one iteration of the shadow loop, mythtracer.cc:94-156 (as mt_render.hip states it)
+        if (STATS) {
+          st.v[ST_RAYS_SHADOW]++;
+          st.v[ST_BYTES_VECTOR] += 96u + 4u + 32u;  // light, occluder's material index and transparency
+        }
+        const int prim = so.prim;
+        const double t = so.t;
+        if (prim < 0) {
+          running = false;  // :109-112
+        } else {
+          const double light_distance = distance(start, lpos);  // :101-102
+          if (t > light_distance) {
+            running = false;  // :115-118
+          } else {
+            // :121 dereferences shadow_primitive->mtl unconditionally; defined as opaque (mt_render.hip)
+            const int sm = S.tri_mtl[prim];
+            const double s_tr = sm >= 0 ? mtls[sm].transparency : 0.0;
+            if (s_tr == 0.0) {
+              lp = v3(0, 0, 0);
+              in_shadow = true;
+              running = false;
+            } else {
+              if (!traversing) {  // :129-132
+                const MT_CONST mt_material *smm = mtls + sm;
+                const V3 tf = v3(smm->transmission_filter[0], smm->transmission_filter[1],
+                                 smm->transmission_filter[2]);
+                lp = lp * (tf * s_tr);
+              }
+              traversing = !traversing;
+              const V3 sp = ro + ld * t;
+              start = sp + (ld * 0.0000001);  // :137
+              if (sqr_distance(Pt, start) > sqr_distance(Pt, lpos)) {
+                running = false;  // :141-145
+              } else if (lp.x <= 0.001 && lp.y <= 0.001 && lp.z <= 0.001) {
+                lp = v3(0, 0, 0);  // :149-155
+                in_shadow = true;
+                running = false;
+              } else {
+                ro = start + (ld * 0.00001);  // next iteration, :95-99
+              }
+            }
+          }
+        }
+      }
+    }
+    if (want && !failed) {
+      const size_t at = (size_t)li * n + i;
+      const double nan = __builtin_nan("");
+      store3(L.power, at, lit ? lp : v3(nan, nan, nan));
+      L.in_shadow[at] = lit ? (in_shadow ? 1 : 0) : 255;
+      if (STATS) st.v[ST_BYTES_VECTOR] += 24u + 1u;
+    }
+    flush_item_stats<STATS>(st, A.counters, lane);
+  }
+}
+
+#define MT_INSTANTIATE_RT_UPDATE(DEEP_)                                                      \
+  template __global__ void raytree_update_kernel<true, DEEP_>(DevScene, RayTreeUpdateArgs);  \
+  template __global__ void raytree_update_kernel<false, DEEP_>(DevScene, RayTreeUpdateArgs);
+MT_INSTANTIATE_RT_UPDATE(0)
+MT_INSTANTIATE_RT_UPDATE(1)
+MT_INSTANTIATE_RT_UPDATE(2)
+#undef MT_INSTANTIATE_RT_UPDATE
 
 #define MT_INSTANTIATE_RT(DEEP_)                                                          \
   template __global__ void raytree_trace_kernel<true, DEEP_>(DevScene, RayTreeTraceArgs);  \

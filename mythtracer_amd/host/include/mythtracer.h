@@ -196,6 +196,15 @@ class MythTracer {
   // The chunk form writes chunk->output_bitmap; the chunk must have the tree's size.
   bool ShadeRayTree(const RayTree& tree, std::vector<uint8_t>* output_bitmap);
   bool ShadeRayTree(const RayTree& tree, WorkChunk* chunk);
+  // After lights have MOVED: the planes of the lights listed in `lights` (indices into GetScene()->lights, each at most
+  // once) in every layer of `tree` traced again under GetScene()->lights from the tree's own stored hits, without a
+  // primary or secondary ray (mt_raytree_update_lights); nothing else in the tree is touched.  The tree is then what a new
+  // BuildRayTree gives if only the listed lights moved since it was built, and ShadeRayTree gives RayTrace's frame.
+  // The facade itself refuses, with a message and before any device call: several devices (SetDevices), an empty
+  // list, a NULL or empty RayTree, and another number of lights than the tree's.  An index out of range or listed twice
+  // is refused by mt_raytree_update_lights, after the facade has uploaded GetScene()->lights; the tree is untouched in
+  // every case.  LastStats() describes the call.
+  bool UpdateRayTree(const std::vector<int>& lights, RayTree* tree);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

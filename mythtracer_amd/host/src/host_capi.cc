@@ -451,6 +451,25 @@ int mth_raytree_shade(void* p, void* t, uint8_t* rgb, size_t rgb_bytes, double* 
   return 1;
 }
 
+// MythTracer::UpdateRayTree(lights, tree) under the facade's lights; `t` as mth_raytree_build returned it (NULL is
+// refused by the facade, after the checks that need no tree).
+int mth_raytree_update(void* p, void* t, const int* light_idx, int n_idx, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  const std::vector<int> lights(light_idx, light_idx + (light_idx && n_idx > 0 ? n_idx : 0));
+  if (!h->mt.UpdateRayTree(lights, static_cast<raytracer::RayTree*>(t))) return 0;
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::UpdateLightBuffer(GBuffer, lights, LightBuffer*) under the facade's lights.  gb_planes[2] = point
 // (doubles), material (int32) of the cw x ch chunk; lb_channels = LightBuffer::k* bits, lb_planes[2] = power, in_shadow
 // for n_lights lights (each NULL or sized for them), updated in place: the planes of the listed lights only.

@@ -698,6 +698,43 @@ bool MythTracer::ShadeRayTree(const RayTree& tree, WorkChunk* chunk) {
   return ShadeRayTree(tree, &chunk->output_bitmap);
 }
 
+bool MythTracer::UpdateRayTree(const std::vector<int>& lights, RayTree* tree) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (the facade's own refusals, before anything touches a device; the indices are checked by the C ABI, below)
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (lights.empty()) return refuse("no light is listed");
+  if (tree == nullptr) return refuse("RayTree is NULL");
+  if (tree->Empty()) return refuse("the RayTree is empty: BuildRayTree first");
+  const size_t n_l = scene.lights.size();
+  if ((size_t)DescOf(tree->Get()).n_lights != n_l) {
+    return refuse("the RayTree was made with another number of lights: a new BuildRayTree is needed");
+  }
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)n_l) != MT_OK) {
+    return refuse(std::string("ray-tree update failed: ") + mt_last_error());
+  }
+  const std::vector<int32_t> idx(lights.begin(), lights.end());
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_raytree_update_lights(tree->Get(), idx.data(), (int)idx.size(), &st) != MT_OK) {
+    return refuse(std::string("ray-tree update failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
 bool MythTracer::UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer) {
   auto refuse = [&](const std::string& why) {
     error_ = why;
