@@ -1438,7 +1438,9 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
       if (a > bmax[i % 3]) bmax[i % 3] = a;
     }
     if ((rc = upload(s, boxes32.data(), boxes32.size(), &s->dev.tri_aabb32)) != MT_OK) return rc;
-    for (int k = 0; k < 3; k++) s->dev.bmax[k] = bmax[k];
+    // Never below 2^-7: make_filter32's check M = (bmax + |o|) |1/d| <= 2^120 then bounds |1/d| by 2^127 as well, the
+    // range in which its fp32 copy is finite (mt_trace.h, Filter32's preconditions).
+    for (int k = 0; k < 3; k++) s->dev.bmax[k] = std::max(bmax[k], 0x1p-7);
   }
   if ((rc = upload(s, d->tri_vertex, nt * 9, &s->dev.tri_vertex)) != MT_OK) return rc;
   if ((rc = upload(s, d->tri_normal, nt * 9, &s->dev.tri_normal)) != MT_OK) return rc;

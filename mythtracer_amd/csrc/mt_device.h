@@ -118,7 +118,7 @@ struct DevScene {
   // reads: per quad of list positions kSlQuadFloats floats = per axis [lo x 4][hi x 4][lo x 4]; a list starts at quad
   // HsRec::sl_begin and is padded to whole quads with inverted boxes.
   const float *sl_box32;
-  double bmax[3];            // max |coordinate| of any triangle box, per axis
+  double bmax[3];            // max |coordinate| of any triangle box, per axis (an upper bound: at least 2^-7)
   const double *tri_vertex;  // 9 per triangle
   const double *tri_normal;  // 9 per triangle
   const double *tri_uvw;     // 9 per triangle

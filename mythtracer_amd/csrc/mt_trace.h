@@ -490,7 +490,14 @@ __device__ __forceinline__ void scan_node_prims(const DevScene &S, const RayRegs
 // lower bounds of the near values, upper bounds of the far values.  Hence
 //   max3(lower near) > min3(upper far)  or  min3(upper far) < 0   =>  exact test fails.
 // Preconditions (else the filter is off for the wave): M <= 2^120 on every
-// axis (no fp32 overflow) and the NaN-free mode.  2^-100 covers fp32 underflow.
+// axis (no fp32 overflow), 2^-126 <= |i| <= 2^127 on every axis and the
+// NaN-free mode.  The bounds on |i| make I a normal fp32 number, whose error IS
+// relative: beyond 2^128 I is infinite and the fma returns +-inf by the sign of
+// X whatever C holds, below 2^-126 it is denormal or zero.  M alone lets both
+// through when bmax + |o| is small or large enough.  The upper bound costs
+// nothing here: the host never hands over a bmax below 2^-7 (scene_create_impl;
+// a larger bmax only widens E), so M <= 2^120 implies it.  The lower bound is
+// one comparison per ray.  2^-100 covers fp32 underflow.
 struct Filter32 {
   float ix, iy, iz;
   float cnx, cny, cnz;
@@ -574,6 +581,8 @@ __device__ __forceinline__ bool make_filter32(const DevScene &S, const RayRegs &
     Cn[k] = f32_not_above(-oi - E);
     Cf[k] = f32_not_below(-oi + E);
   }
+  // |i| >= 2^-126 on every axis (|i| <= 2^127 follows from M <= 2^120 and bmax >= 2^-7)
+  ok = ok && __builtin_fmin(__builtin_fmin(__builtin_fabs(iv[0]), __builtin_fabs(iv[1])), __builtin_fabs(iv[2])) >= 0x1p-126;
   f.ix = I[0]; f.iy = I[1]; f.iz = I[2];
   f.cnx = Cn[0]; f.cny = Cn[1]; f.cnz = Cn[2];
   f.cfx = Cf[0]; f.cfy = Cf[1]; f.cfz = Cf[2];
