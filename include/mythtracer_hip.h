@@ -535,7 +535,7 @@ typedef struct mt_raytree mt_raytree;
 typedef struct mt_raytree_desc {
   int32_t n_layers, n_lights;
   int32_t image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h;
-  int32_t max_depth, reserved;
+  int32_t max_depth, from_rays;           /* 0: made from a sensor (mt_raytree_create), 1: from a ray list */
   int64_t n_rays[MT_MAX_RECURSION + 1];   /* per layer; 0 from n_layers on */
   double trace_ms[MT_MAX_RECURSION + 1];  /* per layer: its tracing kernel at creation, by HIP events */
   uint64_t bytes;                          /* HBM held by the tree */
@@ -591,6 +591,66 @@ int mt_raytree_shade_device(mt_raytree *tree, const mt_light *lights, int n_ligh
  * are MT_ERR_ARG; a tree of zero lights refuses every list. */
 int mt_raytree_update_lights(mt_raytree *tree, const int32_t *light_idx, int n_idx, mt_stats *stats);
 int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, int n_idx, void *stream);
+
+/* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
+ * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour
+ * of.  Everything after layer 0 of a ray tree already runs over a ray list and never looks at a sensor or an image, so
+ * a tree whose layer 0 comes from the caller is traced by the same kernels, launch for launch, and carries the relight
+ * family with it.
+ *
+ * Layer 0 of a ray-list tree: the list counts as a list_w x list_h chunk at (0, 0) of an image of that size.  Caller's
+ * ray p (row-major: x = p % list_w, y = p / list_w) goes to the place the order of layer 0 above gives chunk pixel
+ * (x, y), with in_object[p] and coef[p] (0 and 1.0 where the arrays are NULL), and pixel = p.  A list_w x 1 list keeps
+ * the caller's order: the place of p is p.  An image-shaped ray set therefore gets an 8x8 block per wave, like a
+ * sensor tree; a bare list gets waves of 64 consecutive rays of the caller's.  The directions need NOT be normalised
+ * (a reflected child ray is not either); exact zeros in one or two components are valid.
+ * From there the tree is an ordinary mt_raytree: the same planes and layer rules; mt_raytree_info, _read_layer,
+ * _shade[_device], _update_lights[_device] and _destroy work unchanged; mt_raytree_shade's bitmap is [n][3] bytes in the
+ * caller's order.  mt_raytree_desc reports image_w = chunk_w = list_w, image_h = chunk_h = list_h,
+ * chunk_x = chunk_y = 0 and from_rays = 1.
+ * CONTRACT: the sensor's rays of a chunk, handed in as a chunk_w x chunk_h list, give mt_raytree_create's tree in every
+ * plane of every layer; layer k of a tree, handed in as an n x 1 list with its in_object and coef and
+ * max_depth - k, gives that tree's layers k onwards.
+ *   mt_raytree_create_rays: the arrays of `rays` are HOST memory.  Synchronous.  stats (nullable): rays_primary = n,
+ *     everything else as mt_raytree_create fills it (the copy of the list and its import are inside kernel_ms).
+ *   mt_raytree_create_rays_device: the arrays of `d_rays` are on the scene's GPU (the struct itself is host memory).
+ *     They are read on the scene's DEFAULT stream: the caller must have finished producing them (synchronise the
+ *     producing stream first).  Synchronous, like the host form.
+ * A ray is REFUSED when one of its six numbers is not finite, its direction is (0, 0, 0), its in_object byte is above
+ * 1, or its coef is not finite: the walk has never been handed such a ray and is not by these calls.  The host form
+ * scans the list on the host before any device call.  The device form cannot: the import kernel
+ * (mt::raytree_rays_kernel) counts the refused rays and keeps the lowest index, and the host reads both BEFORE the
+ * first tracing launch.  In both forms any refused ray is MT_ERR_ARG with the count and the first index in the
+ * message; no tree is returned, no tracing kernel has run and no work counter has moved.
+ * Argument checks come before any device call, in this order: `rays` or rays->ray NULL; list_w < 1, list_h < 1
+ * (MT_ERR_ARG), list_w * list_h of 2^31 or more (MT_ERR_ARG, the layer limit's message; there is no limit of 100000
+ * per side); the scene; max_depth in 0 .. MT_MAX_RECURSION; host form only: the content of the list.
+ *
+ * mt_raytree_shade_colors[_device]: mt_raytree_shade[_device] with layer 0's colours written as they are, before
+ * V3DtoRGB clamps and quantises them: [n][3] doubles at the rays' `pixel` places -- chunk-local row-major for a sensor
+ * tree, the caller's order for a ray-list tree (mt::raytree_color_kernel: out[pixel[i]] = colour[i]).  For a caller
+ * who filters, tone-maps or composites.  Both kinds of tree; lights, stats, asynchrony and the one-shade-in-flight rule
+ * as for mt_raytree_shade[_device]; the checks in its order (the output, tree, lights).
+ * CONTRACT: V3DtoRGB of the colours equals mt_raytree_shade's bytes, byte for byte, for the same tree and lights.
+ *
+ * mt_trace_rays: mt_raytree_create_rays, the shade under the scene's CURRENT lights (mt_scene_set_lights), destroy.
+ * out_color ([n][3] doubles) and out_rgb ([n][3] bytes) in the caller's order; either may be NULL, both NULL is
+ * MT_ERR_ARG and checked first, then mt_raytree_create_rays's checks.  Synchronous.  stats (nullable): the create's
+ * counters, kernel_ms = the create's plus the shade's, total_ms = wall time of the call. */
+typedef struct mt_ray_list {
+  const double *ray;        /* [n][6] origin, direction as handed to OctTree::IntersectRay;
+                               the direction need NOT be normalised (child rays are not either) */
+  const uint8_t *in_object; /* [n] 0 / 1, nullable = all 0 */
+  const double *coef;       /* [n] current_reflection_coef, nullable = all 1.0 */
+  int32_t list_w, list_h;   /* n = list_w * list_h, caller's order row-major;
+                               a plain list is n x 1 */
+} mt_ray_list;
+mt_raytree *mt_raytree_create_rays(mt_scene *scene, const mt_ray_list *rays, int max_depth, mt_stats *stats);
+mt_raytree *mt_raytree_create_rays_device(mt_scene *scene, const mt_ray_list *d_rays, int max_depth, mt_stats *stats);
+int mt_raytree_shade_colors(mt_raytree *tree, const mt_light *lights, int n_lights, double *out_color, mt_stats *stats);
+int mt_raytree_shade_colors_device(mt_raytree *tree, const mt_light *lights, int n_lights, void *d_color, void *stream);
+int mt_trace_rays(mt_scene *scene, const mt_ray_list *rays, int max_depth, double *out_color, uint8_t *out_rgb,
+                  mt_stats *stats);
 
 /* One frame on SEVERAL GPUs of this process -- the master/worker farm of the
  * reference (main_net_master.cc:195-236: GenerateWork cuts the frame into

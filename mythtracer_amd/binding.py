@@ -34,6 +34,8 @@ HIP_SYMBOLS = [
     "mt_raytree_create", "mt_raytree_destroy", "mt_raytree_info", "mt_raytree_read_layer",
     "mt_raytree_shade", "mt_raytree_shade_device",
     "mt_raytree_update_lights", "mt_raytree_update_lights_device",
+    "mt_raytree_create_rays", "mt_raytree_create_rays_device", "mt_raytree_shade_colors",
+    "mt_raytree_shade_colors_device", "mt_trace_rays",
 ]
 MT_MAX_RECURSION = 16
 
@@ -219,7 +221,7 @@ DEBUG_PX_DTYPE = np.dtype([("line_no", "<i4"), ("reserved", "<i4"), ("point", "<
 
 class mt_raytree_desc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_layers", "n_lights", "image_w", "image_h", "chunk_x", "chunk_y", "chunk_w",
-                                         "chunk_h", "max_depth", "reserved")] + [
+                                         "chunk_h", "max_depth", "from_rays")] + [
         ("n_rays", C.c_int64 * (MT_MAX_RECURSION + 1)), ("trace_ms", C.c_double * (MT_MAX_RECURSION + 1)),
         ("bytes", C.c_uint64)]
 
@@ -227,8 +229,13 @@ class mt_raytree_desc(C.Structure):
         n = int(self.n_layers)
         return dict(n_layers=n, n_lights=int(self.n_lights), image=(int(self.image_w), int(self.image_h)),
                     chunk=(int(self.chunk_x), int(self.chunk_y), int(self.chunk_w), int(self.chunk_h)),
-                    max_depth=int(self.max_depth), n_rays=[int(v) for v in self.n_rays[:n]],
+                    max_depth=int(self.max_depth), from_rays=int(self.from_rays), n_rays=[int(v) for v in self.n_rays[:n]],
                     trace_ms=[float(v) for v in self.trace_ms[:n]], bytes=int(self.bytes))
+
+
+class mt_ray_list(C.Structure):
+    _fields_ = [("ray", C.c_void_p), ("in_object", C.c_void_p), ("coef", C.c_void_p), ("list_w", C.c_int32),
+                ("list_h", C.c_int32)]
 
 
 # the planes of mt_raytree_layer in declaration order: name -> (dtype, values per ray, per light?)
@@ -318,6 +325,13 @@ class HipAbi:
         L.mt_raytree_shade_device.argtypes = [vp, vp, ci, vp, vp]
         L.mt_raytree_update_lights.argtypes = [vp, vp, ci, vp]
         L.mt_raytree_update_lights_device.argtypes = [vp, vp, ci, vp]
+        L.mt_raytree_create_rays.restype = vp
+        L.mt_raytree_create_rays.argtypes = [vp, vp, ci, vp]
+        L.mt_raytree_create_rays_device.restype = vp
+        L.mt_raytree_create_rays_device.argtypes = [vp, vp, ci, vp]
+        L.mt_raytree_shade_colors.argtypes = [vp, vp, ci, vp, vp]
+        L.mt_raytree_shade_colors_device.argtypes = [vp, vp, ci, vp, vp]
+        L.mt_trace_rays.argtypes = [vp, vp, ci, vp, vp, vp]
         ps = C.POINTER(mt_sensor)
         L.mt_render_chunk_adaptive.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
         L.mt_render_chunk_adaptive_device.argtypes = [vp, ps, ps] + [ci] * 9 + [vp, vp, C.POINTER(mt_adaptive_info), vp]
@@ -708,6 +722,78 @@ class HipAbi:
         idx = _i32(light_indices).reshape(-1)
         self.check(self.lib.mt_raytree_update_lights_device(tree, _ptr(idx), len(idx), stream))
 
+    # ---- ray-list trees and linear colours (include/mythtracer_hip.h, mt_raytree_create_rays)
+    @staticmethod
+    def _ray_list(rays, list_w, in_object, coef, device):
+        """(mt_ray_list, what must stay alive, (list_w, list_h)).  Host form: array-likes, (n, 6) / (n,) / (n,).  Device
+        form: tensors on the scene's GPU (anything with data_ptr() and numel(): float64, uint8, float64)."""
+        if device:
+            n = int(rays.numel()) // 6
+            keep = [rays, in_object, coef]
+            ptr = [None if a is None else a.data_ptr() for a in keep]
+            sizes = [int(rays.numel()), None if in_object is None else int(in_object.numel()),
+                     None if coef is None else int(coef.numel())]
+        else:
+            r = _f64(rays).reshape(-1, 6)
+            n = r.shape[0]
+            keep = [r, None if in_object is None else np.ascontiguousarray(np.asarray(in_object, dtype=np.uint8)).reshape(-1),
+                    None if coef is None else _f64(coef).reshape(-1)]
+            ptr = [_ptr(a) for a in keep]
+            sizes = [r.size] + [None if a is None else a.size for a in keep[1:]]
+        if sizes[0] != n * 6 or any(v is not None and v != n for v in sizes[1:]):
+            raise ValueError("rays (n, 6), in_object (n,) and coef (n,) must describe the same n rays")
+        if list_w is None:
+            list_w = n
+        if n == 0 or list_w < 1 or n % list_w:
+            raise ValueError("a list of %d rays cannot be %s wide" % (n, list_w))
+        rl = mt_ray_list(ptr[0], ptr[1], ptr[2], list_w, n // list_w)
+        return rl, keep, (list_w, n // list_w)
+
+    def raytree_create_rays(self, h, rays, list_w=None, in_object=None, coef=None, max_depth=5, device=False):
+        """mt_raytree_create_rays[_device] under the scene's current lights: (tree handle, stats dict).  `rays` (n, 6)
+        in the caller's order, list_w None = an n x 1 list; device=True: tensors on the scene's GPU, finished."""
+        rl, keep, _ = self._ray_list(rays, list_w, in_object, coef, device)
+        st = mt_stats()
+        fn = self.lib.mt_raytree_create_rays_device if device else self.lib.mt_raytree_create_rays
+        t = fn(h, C.addressof(rl), max_depth, C.addressof(st))
+        del keep
+        if not t:
+            raise RuntimeError("mythtracer_hip error: %s: %s" % (
+                "mt_raytree_create_rays_device" if device else "mt_raytree_create_rays", self.last_error()))
+        return t, st.as_dict()
+
+    def raytree_shade_colors(self, tree, lights) -> dict:
+        """mt_raytree_shade_colors under `lights`: dict(color (chunk_h, chunk_w, 3) float64 before V3DtoRGB, stats)."""
+        info = self.raytree_info(tree)
+        l = _f64(lights).reshape(-1, 12)
+        _, _, cw, ch = info["chunk"]
+        color = np.zeros((ch, cw, 3), dtype=np.float64)
+        st = mt_stats()
+        self.check(self.lib.mt_raytree_shade_colors(tree, _ptr(l), l.shape[0], _ptr(color), C.addressof(st)))
+        return dict(color=color, stats=st.as_dict())
+
+    def raytree_shade_colors_device(self, tree, lights, d_color, stream=None):
+        """mt_raytree_shade_colors_device: `lights` a host array (n x 12), d_color a device pointer to n x 3 doubles;
+        asynchronous on `stream`."""
+        l = _f64(lights).reshape(-1, 12)
+        self.check(self.lib.mt_raytree_shade_colors_device(tree, _ptr(l), l.shape[0], d_color, stream))
+
+    def trace_rays(self, h, rays, list_w=None, in_object=None, coef=None, max_depth=5, color=True, rgb=True) -> dict:
+        """mt_trace_rays under the scene's current lights: dict(color (list_h, list_w, 3) float64 and / or rgb
+        (list_h, list_w, 3) uint8 -- whichever was asked for --, stats)."""
+        rl, keep, (w, hh) = self._ray_list(rays, list_w, in_object, coef, False)
+        out = {}
+        if color:
+            out["color"] = np.zeros((hh, w, 3), dtype=np.float64)
+        if rgb:
+            out["rgb"] = np.zeros((hh, w, 3), dtype=np.uint8)
+        st = mt_stats()
+        self.check(self.lib.mt_trace_rays(h, C.addressof(rl), max_depth, _ptr(out.get("color")), _ptr(out.get("rgb")),
+                                          C.addressof(st)))
+        del keep
+        out["stats"] = st.as_dict()
+        return out
+
     def read_stats(self, h) -> dict:
         st = mt_stats()
         self.check(self.lib.mt_scene_read_stats(h, C.byref(st)))
@@ -848,6 +934,10 @@ def host_lib():
     L.mth_raytree_handle.restype = vp
     L.mth_raytree_shade.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.mth_raytree_update.argtypes = [vp, vp, vp, ci, vp, vp]
+    L.mth_raytree_build_rays.restype = vp
+    L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
+    L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.mth_trace_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp, vp, vp]
     L.mth_frame_loop.argtypes = [vp, vp, ci, ci, ci, cd, ci, vp, vp]
     L.mth_intersect.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mth_chunk_serialize_input.argtypes = [vp, vp]
@@ -906,6 +996,19 @@ class RayTree:
         if not self.mt.L.mth_raytree_shade(self.mt.h, self.h, _ptr(rgb), rgb.size, _ptr(ms)):
             raise RuntimeError("ShadeRayTree failed: " + self.mt.last_error())
         return dict(rgb=rgb, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def shade_colors(self, lights=None) -> dict:
+        """MythTracer::ShadeRayTree(tree, &colours): the colours before V3DtoRGB.  `lights` as in shade.  Returns
+        dict(color (chunk_h, chunk_w, 3) float64, kernel_ms, total_ms)."""
+        self._tree()
+        if lights is not None:
+            self.mt.set_lights(lights)
+        _, _, cw, ch = self.info["chunk"]
+        color = np.zeros((ch, cw, 3), dtype=np.float64)
+        ms = np.zeros(2)
+        if not self.mt.L.mth_raytree_shade_colors(self.mt.h, self.h, _ptr(color), cw * ch, _ptr(ms)):
+            raise RuntimeError("ShadeRayTree failed: " + self.mt.last_error())
+        return dict(color=color, kernel_ms=float(ms[0]), total_ms=float(ms[1]))
 
     def update(self, light_indices, lights=None) -> dict:
         """MythTracer::UpdateRayTree: the planes of the lights in `light_indices`, in every layer, traced again under
@@ -1204,6 +1307,41 @@ class MythTracer:
         tree = RayTree(self, t, dict(zip(STAT_NAMES, (int(x) for x in st))), float(ms[0]), float(ms[1]))
         self._trees = [r for r in getattr(self, "_trees", []) if r() is not None] + [weakref.ref(tree)]
         return tree
+
+    def raytree_rays(self, rays, list_width=0, max_depth=None) -> RayTree:
+        """MythTracer::BuildRayTree(rays, list_width, &tree) under the lights of set_lights: `rays` (n, 6) in the
+        caller's order, list_width 0 = an n x 1 list.  Close the RayTree before this MythTracer."""
+        if max_depth is not None:
+            self.set_max_level(int(max_depth))
+        r = _f64(rays).reshape(-1, 6)
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        t = self.L.mth_raytree_build_rays(self.h, _ptr(r), r.shape[0], int(list_width), _ptr(st), _ptr(ms))
+        if not t:
+            raise RuntimeError("BuildRayTree failed: " + self.last_error())
+        tree = RayTree(self, t, dict(zip(STAT_NAMES, (int(x) for x in st))), float(ms[0]), float(ms[1]))
+        self._trees = [r for r in getattr(self, "_trees", []) if r() is not None] + [weakref.ref(tree)]
+        return tree
+
+    def trace_rays(self, rays, list_width=0, max_depth=None, color=True, rgb=True) -> dict:
+        """MythTracer::TraceRays: dict(color (n, 3) float64 and / or rgb (n, 3) uint8 -- whichever was asked for --,
+        counters, kernel_ms, total_ms), in the caller's order."""
+        if max_depth is not None:
+            self.set_max_level(int(max_depth))
+        r = _f64(rays).reshape(-1, 6)
+        n = r.shape[0]
+        out = {}
+        if color:
+            out["color"] = np.zeros((n, 3), dtype=np.float64)
+        if rgb:
+            out["rgb"] = np.zeros((n, 3), dtype=np.uint8)
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        if not self.L.mth_trace_rays(self.h, _ptr(r), n, int(list_width), _ptr(out.get("color")), _ptr(out.get("rgb")),
+                                     _ptr(st), _ptr(ms)):
+            raise RuntimeError("TraceRays failed: " + self.last_error())
+        out.update(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+        return out
 
     def render_image(self, cam, image_w, image_h):
         """MythTracer::RayTrace(int, int, Camera*, vector<uint8_t>*)."""

@@ -2621,6 +2621,8 @@ struct mt_raytree {
   RayTreeLayer layer[MT_MAX_RECURSION + 1] = {};
   unsigned long long *d_count = nullptr;   // the compaction's answer
   uint8_t *d_rgb = nullptr;                // the host shade's bitmap (first use)
+  double *d_out_color = nullptr;           // the host shade's colours (first use)
+  unsigned int *d_bad = nullptr;           // a ray-list tree: raytree_rays_kernel's count and lowest index of refused rays
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_layer[MT_MAX_RECURSION + 1][2] = {};
 };
@@ -2678,8 +2680,36 @@ int check_raytree_create_args(const mt_scene *s, const mt_sensor *sensor, int im
   return MT_OK;
 }
 
-int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_lights, const void *rgb) {
-  if (!rgb) return fail(MT_ERR_ARG, "the output bitmap is NULL");
+// mt_raytree_create_rays[_device]: checked before any device call, in the order of the header.
+int check_raytree_rays_args(const mt_scene *s, const mt_ray_list *rays, int max_depth, bool on_host) {
+  if (!rays || !rays->ray) return fail(MT_ERR_ARG, "the ray list is NULL");
+  if (rays->list_w < 1 || rays->list_h < 1) {
+    return fail(MT_ERR_ARG, "ray list size %dx%d out of range", rays->list_w, rays->list_h);
+  }
+  const long long n = (long long)rays->list_w * (long long)rays->list_h;
+  if (n >= 0x80000000ll) return fail(MT_ERR_ARG, "layer 0 of the ray tree would have %lld rays (2^31 or more)", n);
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (max_depth < 0 || max_depth > MT_MAX_RECURSION) {
+    return fail(MT_ERR_ARG, "max_depth %d outside [0, %d]", max_depth, MT_MAX_RECURSION);
+  }
+  if (!on_host) return MT_OK;
+  // the content of the list: what raytree_rays_kernel refuses, found before anything is copied
+  long long bad = 0, first = -1;
+  for (long long p = 0; p < n; p++) {
+    const double *r = rays->ray + p * 6;
+    bool ok = std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]) &&
+              std::isfinite(r[4]) && std::isfinite(r[5]) && !(r[3] == 0.0 && r[4] == 0.0 && r[5] == 0.0);
+    if (rays->in_object && rays->in_object[p] > 1) ok = false;
+    if (rays->coef && !std::isfinite(rays->coef[p])) ok = false;
+    if (!ok && bad++ == 0) first = p;
+  }
+  if (bad) return fail(MT_ERR_ARG, "%lld rays of the list cannot be traced, the first at index %lld", bad, first);
+  return MT_OK;
+}
+
+int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_lights, const void *out,
+                             const char *no_output = "the output bitmap is NULL") {
+  if (!out) return fail(MT_ERR_ARG, "%s", no_output);
   if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
   if (n_lights < 0 || (n_lights > 0 && !lights)) return fail(MT_ERR_ARG, "bad lights argument");
   if (n_lights != t->info.n_lights) {
@@ -2753,8 +2783,54 @@ int raytree_read_counters(mt_scene *s, hipStream_t stream) {
   return check_status(s->h_counters);
 }
 
-// Layer after layer: trace, compact, (host: size the next layer), spawn.
-int raytree_build(mt_raytree *t, mt_stats *stats) {
+// Layer 0 of a ray-list tree: the caller's rays (host or device pointers in `rays`) through raytree_rays_kernel.
+// Synchronises: no tracing kernel is launched before the kernel's count of refused rays has been read.
+int raytree_import_rays(mt_raytree *t, const mt_ray_list *rays, bool on_device, hipStream_t stream) {
+  const size_t n = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
+  MT_TRY(raytree_malloc((void **)&t->d_bad, 2 * sizeof(unsigned int), "the ray tree's count of refused rays"));
+  RayTreeRaysArgs A{};
+  A.ray = rays->ray; A.in_object = rays->in_object; A.coef = rays->coef;
+  void *staged = nullptr;
+  if (!on_device) {  // one allocation: the rays, the coefficients, the in_object bytes
+    MT_TRY(raytree_malloc(&staged, n * 48 + n * 8 + n, "the caller's ray list"));
+    char *at = (char *)staged;
+    A.ray = (const double *)at;
+    A.coef = rays->coef ? (const double *)(at + n * 48) : nullptr;
+    A.in_object = rays->in_object ? (const uint8_t *)(at + n * 56) : nullptr;
+  }
+  const auto release = [&](int rc) {
+    if (staged) (void)hipFree(staged);
+    return rc;
+  };
+  if (!on_device) {
+    if (hipMemcpyAsync((void *)A.ray, rays->ray, n * 48, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        (A.coef && hipMemcpyAsync((void *)A.coef, rays->coef, n * 8, hipMemcpyHostToDevice, stream) != hipSuccess) ||
+        (A.in_object && hipMemcpyAsync((void *)A.in_object, rays->in_object, n, hipMemcpyHostToDevice, stream) != hipSuccess)) {
+      return release(fail(MT_ERR_HIP, "copying the ray list to the device failed: %s", hipGetErrorString(hipGetLastError())));
+    }
+  }
+  A.list_w = t->info.chunk_w; A.list_h = t->info.chunk_h;
+  A.L = t->layer[0];
+  A.bad = t->d_bad;
+  unsigned int bad[2] = {0u, 0xffffffffu};
+  hipError_t e = hipMemsetAsync(t->d_bad, 0, sizeof(unsigned int), stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bad + 1, 0xff, sizeof(unsigned int), stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(raytree_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(bad, t->d_bad, sizeof bad, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return release(fail(MT_ERR_HIP, "importing the ray list failed: %s", hipGetErrorString(e)));
+  if (bad[0] != 0) {
+    return release(fail(MT_ERR_ARG, "%u rays of the list cannot be traced, the first at index %u", bad[0], bad[1]));
+  }
+  return release(MT_OK);
+}
+
+// Layer after layer: trace, compact, (host: size the next layer), spawn.  Layer 0 comes from the tree's sensor, or from
+// `rays` (a ray-list tree; on_device: its pointers are device pointers).
+int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_stats *stats) {
   mt_scene *s = t->scene;
   const auto w0 = std::chrono::steady_clock::now();
   hipStream_t stream = nullptr;
@@ -2768,7 +2844,9 @@ int raytree_build(mt_raytree *t, mt_stats *stats) {
   MT_TRY(raytree_alloc_layer(t, 0, npx));
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
   HIP_TRY(hipEventRecord(t->ev0, stream));
-  {
+  if (rays) {
+    MT_TRY(raytree_import_rays(t, rays, on_device, stream));
+  } else {
     RayTreePrimaryArgs A{};
     A.sensor = t->sensor;
     A.chunk_x = I.chunk_x; A.chunk_y = I.chunk_y; A.chunk_w = I.chunk_w; A.chunk_h = I.chunk_h;
@@ -2838,8 +2916,10 @@ int raytree_build(mt_raytree *t, mt_stats *stats) {
   return MT_OK;
 }
 
-// raytree_shade_kernel over the layers, deepest first; d_rgb = device pointer
-int launch_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *d_rgb, hipStream_t stream) {
+// raytree_shade_kernel over the layers, deepest first; d_rgb, d_color = device pointers, either may be nullptr: layer 0
+// goes to the bitmap, or to its own colour plane and from there to d_color (raytree_color_kernel), or both
+int launch_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *d_rgb, double *d_color,
+                         hipStream_t stream) {
   mt_scene *s = t->scene;
   RayTreeShadeArgs A{};
   A.n_lights = n_lights;
@@ -2857,10 +2937,23 @@ int launch_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, ui
     A.L = t->layer[k];
     A.child_color = k + 1 < t->info.n_layers ? t->layer[k + 1].color : nullptr;
     A.n_rays = (uint32_t)n;
-    A.out_rgb = k == 0 ? d_rgb : nullptr;
-    hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>, dim3((unsigned)((n + 255) / 256)),
-                       dim3(256), 0, stream, A);
-    HIP_TRY(hipGetLastError());
+    A.out_rgb = nullptr;
+    if (k > 0 || d_color != nullptr) {
+      hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>,
+                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+      HIP_TRY(hipGetLastError());
+    }
+    if (k == 0 && d_color != nullptr) {
+      hipLaunchKernelGGL(raytree_color_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                         (const double *)A.L.color, (const int32_t *)A.L.pixel, (uint32_t)n, d_color);
+      HIP_TRY(hipGetLastError());
+    }
+    if (k == 0 && d_rgb != nullptr) {
+      A.out_rgb = d_rgb;
+      hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>,
+                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+      HIP_TRY(hipGetLastError());
+    }
   }
   return MT_OK;
 }
@@ -2876,6 +2969,8 @@ void mt_raytree_destroy(mt_raytree *t) {
   }
   if (t->d_count) (void)hipFree(t->d_count);
   if (t->d_rgb) (void)hipFree(t->d_rgb);
+  if (t->d_out_color) (void)hipFree(t->d_out_color);
+  if (t->d_bad) (void)hipFree(t->d_bad);
   if (t->ev0) (void)hipEventDestroy(t->ev0);
   if (t->ev1) (void)hipEventDestroy(t->ev1);
   for (auto &e : t->ev_layer) {
@@ -2903,7 +2998,7 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
   t->info.max_depth = max_depth;
   const bool counters_were = s->stats_enabled;
   if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = raytree_build(t, stats);
+  const int rc = raytree_build(t, nullptr, false, stats);
   s->stats_enabled = counters_were;
   if (rc != MT_OK) {
     const std::string why = g_err;  // (the text survives the clean-up)
@@ -2911,6 +3006,48 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
     (void)fail(rc, "%s", why.c_str());
     return nullptr;
   }
+  return t;
+}
+
+namespace {
+
+// *out = the tree, or nullptr with the error's code returned
+int raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_stats *stats, bool on_device,
+                        mt_raytree **out) {
+  *out = nullptr;
+  MT_TRY(check_raytree_rays_args(s, rays, max_depth, !on_device));
+  if (hipSetDevice(s->device) != hipSuccess) return fail(MT_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  mt_raytree *t = new mt_raytree();
+  t->scene = s;
+  t->info.n_lights = s->dev.n_lights;
+  t->info.image_w = t->info.chunk_w = rays->list_w;
+  t->info.image_h = t->info.chunk_h = rays->list_h;
+  t->info.max_depth = max_depth;
+  t->info.from_rays = 1;
+  const bool counters_were = s->stats_enabled;
+  if (stats) s->stats_enabled = true;  // the caller asked for them
+  const int rc = raytree_build(t, rays, on_device, stats);
+  s->stats_enabled = counters_were;
+  if (rc != MT_OK) {
+    const std::string why = g_err;  // (the text survives the clean-up)
+    mt_raytree_destroy(t);
+    return fail(rc, "%s", why.c_str());
+  }
+  *out = t;
+  return MT_OK;
+}
+
+}  // namespace
+
+mt_raytree *mt_raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_stats *stats) {
+  mt_raytree *t = nullptr;
+  (void)raytree_create_rays(s, rays, max_depth, stats, false, &t);
+  return t;
+}
+
+mt_raytree *mt_raytree_create_rays_device(mt_scene *s, const mt_ray_list *d_rays, int max_depth, mt_stats *stats) {
+  mt_raytree *t = nullptr;
+  (void)raytree_create_rays(s, d_rays, max_depth, stats, true, &t);
   return t;
 }
 
@@ -2945,26 +3082,70 @@ int mt_raytree_read_layer(mt_raytree *t, int layer, const mt_raytree_layer *out)
 int mt_raytree_shade_device(mt_raytree *t, const mt_light *lights, int n_lights, void *d_rgb, void *stream) {
   MT_TRY(check_raytree_shade_args(t, lights, n_lights, d_rgb));
   HIP_TRY(hipSetDevice(t->scene->device));
-  return launch_raytree_shade(t, lights, n_lights, (uint8_t *)d_rgb, (hipStream_t)stream);
+  return launch_raytree_shade(t, lights, n_lights, (uint8_t *)d_rgb, nullptr, (hipStream_t)stream);
 }
 
-int mt_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *out_rgb, mt_stats *stats) {
-  MT_TRY(check_raytree_shade_args(t, lights, n_lights, out_rgb));
+int mt_raytree_shade_colors_device(mt_raytree *t, const mt_light *lights, int n_lights, void *d_color, void *stream) {
+  MT_TRY(check_raytree_shade_args(t, lights, n_lights, d_color, "the output colours are NULL"));
+  HIP_TRY(hipSetDevice(t->scene->device));
+  return launch_raytree_shade(t, lights, n_lights, nullptr, (double *)d_color, (hipStream_t)stream);
+}
+
+namespace {
+
+// the host forms of the shade: bytes, colours or both, whichever is not NULL
+int raytree_shade_host(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *out_rgb, double *out_color,
+                       mt_stats *stats) {
   const auto w0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(t->scene->device));
   const size_t npx = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
   hipStream_t stream = nullptr;
-  if (!t->d_rgb) MT_TRY(raytree_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
+  if (out_rgb && !t->d_rgb) MT_TRY(raytree_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
+  if (out_color && !t->d_out_color) MT_TRY(raytree_malloc((void **)&t->d_out_color, npx * 24, "the ray tree's colours"));
   HIP_TRY(hipEventRecord(t->ev0, stream));
-  MT_TRY(launch_raytree_shade(t, lights, n_lights, t->d_rgb, stream));
+  MT_TRY(launch_raytree_shade(t, lights, n_lights, out_rgb ? t->d_rgb : nullptr, out_color ? t->d_out_color : nullptr, stream));
   HIP_TRY(hipEventRecord(t->ev1, stream));
-  HIP_TRY(hipMemcpyAsync(out_rgb, t->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
+  if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, t->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
+  if (out_color) HIP_TRY(hipMemcpyAsync(out_color, t->d_out_color, npx * 24, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   if (stats) {
     memset(stats, 0, sizeof *stats);
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
     stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_raytree_shade_colors(mt_raytree *t, const mt_light *lights, int n_lights, double *out_color, mt_stats *stats) {
+  MT_TRY(check_raytree_shade_args(t, lights, n_lights, out_color, "the output colours are NULL"));
+  return raytree_shade_host(t, lights, n_lights, nullptr, out_color, stats);
+}
+
+int mt_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *out_rgb, mt_stats *stats) {
+  MT_TRY(check_raytree_shade_args(t, lights, n_lights, out_rgb));
+  return raytree_shade_host(t, lights, n_lights, out_rgb, nullptr, stats);
+}
+
+int mt_trace_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, double *out_color, uint8_t *out_rgb,
+                  mt_stats *stats) {
+  if (!out_color && !out_rgb) return fail(MT_ERR_ARG, "out_color and out_rgb are both NULL");
+  const auto w0 = std::chrono::steady_clock::now();
+  mt_stats made{};
+  mt_raytree *t = nullptr;
+  MT_TRY(raytree_create_rays(s, rays, max_depth, stats ? &made : nullptr, false, &t));
+  const std::vector<mt_light> lights = s->lights_host;  // the scene's current lights
+  mt_stats shaded{};
+  const int rc = raytree_shade_host(t, lights.data(), (int)lights.size(), out_rgb, out_color, stats ? &shaded : nullptr);
+  const std::string why = rc != MT_OK ? g_err : std::string();
+  mt_raytree_destroy(t);
+  if (rc != MT_OK) return fail(rc, "%s", why.c_str());
+  if (stats) {
+    *stats = made;
+    stats->kernel_ms = made.kernel_ms + shaded.kernel_ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   }
   return MT_OK;

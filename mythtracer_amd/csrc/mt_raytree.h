@@ -532,4 +532,59 @@ MT_INSTANTIATE_RT(2)
 template __global__ void raytree_shade_kernel<true>(RayTreeShadeArgs);
 template __global__ void raytree_shade_kernel<false>(RayTreeShadeArgs);
 
+// ---- a tree over the CALLER's rays (include/mythtracer_hip.h, mt_raytree_create_rays ff.) ----
+// raytree_rays_kernel  layer 0 from a ray list instead of the sensor: raytree_primary_kernel's shape with the rays read
+//                      from memory.  The list counts as a list_w x list_h chunk: caller's ray p goes to place
+//                      raytree_layer0_index(p % list_w, p / list_w, list_w, list_h) (p itself when list_h == 1) and
+//                      pixel = p.  A ray the walk must never see -- a number that is not finite, the direction
+//                      (0, 0, 0), an in_object byte above 1, a coef that is not finite -- is counted in bad[0] and
+//                      its index kept in bad[1] when it is the lowest (atomicAdd / atomicMin); the host reads the two
+//                      words before the first raytree_trace_kernel launch and launches none when bad[0] != 0.
+// raytree_color_kernel the shade's layer-0 colours, as raytree_shade_kernel leaves them in L.color when out_rgb is
+//                      nullptr, to the rays' places of the caller's [n][3] doubles: out[pixel[i]] = color[i].
+struct RayTreeRaysArgs {
+  const double *ray;         // [n][6], the caller's order
+  const uint8_t *in_object;  // [n] or nullptr = all 0
+  const double *coef;        // [n] or nullptr = all 1.0
+  int32_t list_w, list_h;
+  RayTreeLayer L;
+  unsigned int *bad;         // [2] at launch: 0, 0xffffffff
+};
+
+// neither an infinity nor a NaN (by the exponent's bits: no compiler flag has a say)
+__device__ inline bool raytree_finite(double v) {
+  return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+__global__ __launch_bounds__(256) void raytree_rays_kernel(RayTreeRaysArgs A) {
+  const size_t n = (size_t)A.list_w * (size_t)A.list_h;
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const double *src = A.ray + p * 6;
+  const double r0 = src[0], r1 = src[1], r2 = src[2], r3 = src[3], r4 = src[4], r5 = src[5];
+  const unsigned in_object = A.in_object != nullptr ? A.in_object[p] : 0u;
+  const double coef = A.coef != nullptr ? A.coef[p] : 1.0;
+  const bool finite = raytree_finite(r0) && raytree_finite(r1) && raytree_finite(r2) && raytree_finite(r3) &&
+                      raytree_finite(r4) && raytree_finite(r5);
+  const bool zero = r3 == 0.0 && r4 == 0.0 && r5 == 0.0;
+  if (!finite || zero || in_object > 1u || !raytree_finite(coef)) {
+    atomicAdd(A.bad, 1u);
+    atomicMin(A.bad + 1, (unsigned)p);  // (n < 2^31)
+    return;
+  }
+  const size_t i = raytree_layer0_index((int)(p % (size_t)A.list_w), (int)(p / (size_t)A.list_w), A.list_w, A.list_h);
+  double *r = A.L.ray + i * 6;
+  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3; r[4] = r4; r[5] = r5;
+  A.L.coef[i] = coef;
+  A.L.in_object[i] = (uint8_t)in_object;
+  A.L.pixel[i] = (int32_t)p;
+}
+
+__global__ __launch_bounds__(256) void raytree_color_kernel(const double *color, const int32_t *pixel, uint32_t n_rays,
+                                                            double *out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n_rays) return;
+  store3(out, (size_t)pixel[i], v3_load(color + i * 3));
+}
+
 }  // namespace mt

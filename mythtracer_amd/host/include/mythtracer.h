@@ -205,6 +205,21 @@ class MythTracer {
   // is refused by mt_raytree_update_lights, after the facade has uploaded GetScene()->lights; the tree is untouched in
   // every case.  LastStats() describes the call.
   bool UpdateRayTree(const std::vector<int>& lights, RayTree* tree);
+  // The caller's rays instead of a camera's (mt_raytree_create_rays): TraceRay for a ray list, to the recursion level of
+  // SetMaxRecursionLevel under GetScene()->lights.  list_width 0 means an n x 1 list, whose waves are 64 consecutive
+  // rays of the caller's; otherwise it must divide n and the list is treated as a list_width x (n / list_width) image,
+  // row-major, whose waves are 8x8 blocks.  The directions need not be normalised; a ray with a number that is not
+  // finite or with the direction (0, 0, 0) is refused with a message naming the count and the first index.  The tree
+  // is an ordinary RayTree: ShadeRayTree (bitmap and colours in the caller's order) and UpdateRayTree accept it.
+  // Refused, before anything touches a device: a NULL tree, several devices (SetDevices), an empty list, a list_width
+  // that is negative or does not divide n.  LastStats() describes the call (rays_primary = n).
+  bool BuildRayTree(const std::vector<Ray>& rays, int list_width, RayTree* tree);
+  // ShadeRayTree's colours before V3DtoRGB (mt_raytree_shade_colors), one V3D per layer-0 ray: chunk-local row-major
+  // for a camera's tree, the caller's order for a ray list's.  V3DtoRGB of them is ShadeRayTree's bitmap byte for byte.
+  bool ShadeRayTree(const RayTree& tree, std::vector<V3D>* colours);
+  // BuildRayTree(rays, list_width), the shade under GetScene()->lights, and the tree is gone (mt_trace_rays): the
+  // colours, the RGB8 bitmap (n x 3 bytes) or both, in the caller's order.  Either output may be NULL, not both.
+  bool TraceRays(const std::vector<Ray>& rays, int list_width, std::vector<V3D>* colours, std::vector<uint8_t>* bitmap);
   void SetQuiet(bool quiet) {                                   // no progress text on stdout
     quiet_ = quiet;
     scene.tree.SetQuiet(quiet);

@@ -11,7 +11,9 @@ class Ray {
  public:
   Ray(V3D org, V3D dir) : origin(org), direction(dir) {}
   V3D origin;
-  V3D direction;  // expected to be normalised
+  // Normalised where the facade makes the ray (Sensor::GetRay).  BuildRayTree(rays, ...) and TraceRays take any
+  // direction but (0, 0, 0): a caller's ray is handed to the walk as it is, like a reflected child ray.
+  V3D direction;
 };
 
 }  // namespace raytracer

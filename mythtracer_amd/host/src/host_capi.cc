@@ -451,6 +451,76 @@ int mth_raytree_shade(void* p, void* t, uint8_t* rgb, size_t rgb_bytes, double* 
   return 1;
 }
 
+namespace {
+// n rays of 6 doubles as the facade's vector (empty for NULL or n <= 0)
+std::vector<raytracer::Ray> RaysOf(const double* rays6, long long n) {
+  std::vector<raytracer::Ray> rays;
+  for (long long i = 0; rays6 != nullptr && i < n; i++) {
+    const double* r = rays6 + i * 6;
+    rays.emplace_back(V3D{r[0], r[1], r[2]}, V3D{r[3], r[4], r[5]});
+  }
+  return rays;
+}
+
+void StatsOut(const raytracer::RenderStats& s, uint64_t* stats8, double* ms2) {
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+}
+}  // namespace
+
+// MythTracer::BuildRayTree(rays, list_width, RayTree*) at the facade's recursion level and lights; rays6 = n x 6
+// doubles.  A new RayTree on the heap (mth_raytree_free), NULL on failure.
+void* mth_raytree_build_rays(void* p, const double* rays6, long long n, int list_width, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  raytracer::RayTree* t = new raytracer::RayTree();
+  if (!h->mt.BuildRayTree(RaysOf(rays6, n), list_width, t)) {
+    delete t;
+    return nullptr;
+  }
+  StatsOut(h->mt.LastStats(), stats8, ms2);
+  return t;
+}
+
+// MythTracer::ShadeRayTree(tree, &colours) under the facade's current lights; colors holds n_colors x 3 doubles.
+int mth_raytree_shade_colors(void* p, void* t, double* colors, size_t n_colors, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  if (t == nullptr) {
+    h->shim_error = "the RayTree is NULL";
+    return 0;
+  }
+  std::vector<V3D> colours;
+  if (!h->mt.ShadeRayTree(*static_cast<raytracer::RayTree*>(t), &colours)) return 0;
+  if (colours.size() != n_colors) {
+    h->shim_error = "the colours were sized for " + std::to_string(n_colors) + " rays, the tree's layer 0 has " +
+                    std::to_string(colours.size());
+    return 0;
+  }
+  memcpy(colors, colours.data(), colours.size() * sizeof(V3D));
+  StatsOut(h->mt.LastStats(), nullptr, ms2);
+  return 1;
+}
+
+// MythTracer::TraceRays(rays, list_width, colours, bitmap): colors (n x 3 doubles) and rgb (n x 3 bytes), either may
+// be NULL.
+int mth_trace_rays(void* p, const double* rays6, long long n, int list_width, double* colors, uint8_t* rgb,
+                   uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  std::vector<V3D> colours;
+  std::vector<uint8_t> bitmap;
+  if (!h->mt.TraceRays(RaysOf(rays6, n), list_width, colors ? &colours : nullptr, rgb ? &bitmap : nullptr)) return 0;
+  if (colors) memcpy(colors, colours.data(), colours.size() * sizeof(V3D));
+  if (rgb) memcpy(rgb, bitmap.data(), bitmap.size());
+  StatsOut(h->mt.LastStats(), stats8, ms2);
+  return 1;
+}
+
 // MythTracer::UpdateRayTree(lights, tree) under the facade's lights; `t` as mth_raytree_build returned it (NULL is
 // refused by the facade, after the checks that need no tree).
 int mth_raytree_update(void* p, void* t, const int* light_idx, int n_idx, uint64_t* stats8, double* ms2) {

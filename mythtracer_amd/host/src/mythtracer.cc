@@ -735,6 +735,136 @@ bool MythTracer::UpdateRayTree(const std::vector<int>& lights, RayTree* tree) {
   return true;
 }
 
+namespace {
+static_assert(sizeof(Ray) == 6 * sizeof(double) && sizeof(V3D) == 3 * sizeof(double),
+              "a vector of Ray is the C ABI's [n][6] doubles, a vector of V3D its [n][3]");
+
+// the list's shape, or the reason it has none
+bool RayListOf(const std::vector<Ray>& rays, int list_width, mt_ray_list* out, std::string* why) {
+  const size_t n = rays.size();
+  if (n == 0) {
+    *why = "the ray list is empty";
+    return false;
+  }
+  if (list_width < 0 || (list_width > 0 && n % (size_t)list_width != 0)) {
+    *why = "list_width " + std::to_string(list_width) + " does not divide the " + std::to_string(n) + " rays";
+    return false;
+  }
+  const size_t w = list_width > 0 ? (size_t)list_width : n;
+  if (n >= 0x80000000ull) {
+    *why = "a list of " + std::to_string(n) + " rays (2^31 or more)";
+    return false;
+  }
+  memset(out, 0, sizeof *out);
+  out->ray = reinterpret_cast<const double*>(rays.data());
+  out->list_w = (int32_t)w;
+  out->list_h = (int32_t)(n / w);
+  return true;
+}
+
+void CopyStats(const mt_stats& st, RenderStats* out) {
+  *out = RenderStats{};
+  out->rays_primary = st.rays_primary;
+  out->rays_secondary = st.rays_secondary;
+  out->rays_shadow = st.rays_shadow;
+  out->box_tests = st.box_tests;
+  out->node_visits = st.node_visits;
+  out->tri_tests = st.tri_tests;
+  out->mt_tests = st.mt_tests;
+  out->shaded_hits = st.shaded_hits;
+  out->kernel_ms = st.kernel_ms;
+  out->total_ms = st.total_ms;
+}
+}  // namespace
+
+bool MythTracer::BuildRayTree(const std::vector<Ray>& rays, int list_width, RayTree* tree) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device, as in BuildRayTree(WorkChunk*, ...))
+  if (tree == nullptr) return refuse("RayTree is NULL");
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  mt_ray_list list;
+  std::string why;
+  if (!RayListOf(rays, list_width, &list, &why)) return refuse(why);
+  if (max_level_ < 0 || max_level_ > MT_MAX_RECURSION) {
+    return refuse("recursion level " + std::to_string(max_level_) + " outside 0 .. " + std::to_string(MT_MAX_RECURSION));
+  }
+  tree->Reset();
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("ray tree failed: ") + mt_last_error());
+  }
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  tree->tree_ = mt_raytree_create_rays(dev_, &list, max_level_, &st);
+  if (tree->tree_ == nullptr) return refuse(std::string("ray tree failed: ") + mt_last_error());
+  CopyStats(st, &stats_);
+  return true;
+}
+
+bool MythTracer::ShadeRayTree(const RayTree& tree, std::vector<V3D>* colours) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (colours == nullptr) return refuse("the output colours are NULL");
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (tree.Empty()) return refuse("the RayTree is empty: BuildRayTree first");
+  const mt_raytree_desc d = DescOf(tree.Get());
+  if ((size_t)d.n_lights != scene.lights.size()) {
+    return refuse("the RayTree was made with another number of lights: a new BuildRayTree is needed");
+  }
+  colours->resize((size_t)d.chunk_w * (size_t)d.chunk_h);
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  if (mt_raytree_shade_colors(tree.Get(), reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size(),
+                              reinterpret_cast<double*>(colours->data()), &st) != MT_OK) {
+    return refuse(std::string("ray-tree shade failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
+bool MythTracer::TraceRays(const std::vector<Ray>& rays, int list_width, std::vector<V3D>* colours,
+                           std::vector<uint8_t>* bitmap) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (checked before anything touches a device)
+  if (colours == nullptr && bitmap == nullptr) return refuse("the output colours and the output bitmap are both NULL");
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  mt_ray_list list;
+  std::string why;
+  if (!RayListOf(rays, list_width, &list, &why)) return refuse(why);
+  if (max_level_ < 0 || max_level_ > MT_MAX_RECURSION) {
+    return refuse("recursion level " + std::to_string(max_level_) + " outside 0 .. " + std::to_string(MT_MAX_RECURSION));
+  }
+  if (!Prepare()) return false;
+  if (mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("tracing the rays failed: ") + mt_last_error());
+  }
+  if (colours) colours->resize(rays.size());
+  if (bitmap) bitmap->resize(rays.size() * 3);
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_trace_rays(dev_, &list, max_level_, colours ? reinterpret_cast<double*>(colours->data()) : nullptr,
+                    bitmap ? bitmap->data() : nullptr, &st) != MT_OK) {
+    return refuse(std::string("tracing the rays failed: ") + mt_last_error());
+  }
+  CopyStats(st, &stats_);
+  return true;
+}
+
 bool MythTracer::UpdateLightBuffer(const GBuffer& gbuffer, const std::vector<int>& lights, LightBuffer* lightbuffer) {
   auto refuse = [&](const std::string& why) {
     error_ = why;
