@@ -158,6 +158,30 @@ void mt_scene_destroy(mt_scene *scene);
  * by the caller between frames (main_local.cc:79-110). */
 int mt_scene_set_lights(mt_scene *scene, const mt_light *lights, int n);
 
+/* scene.materials edited in place: the constants of ALL materials replaced -- the same count, the textures untouched;
+ * `tex` may point at another existing texture.  (No reference counterpart: its drivers load a scene once.)  For a
+ * look-dev session that changes a wall's colour or a mirror's reflectance between frames without flattening and
+ * uploading the triangles again.  Every kernel reads the material table at run time and nothing derived from it is
+ * baked into the uploaded scene, so the call is one copy.
+ * mt_scene_set_materials is synchronous: it waits until the scene's device is idle, then copies.  "One call in flight
+ * per scene" holds for it like for every other call.  The scene keeps a host copy of its current materials and a
+ * generation number: mt_scene_create fills both, the generation starts at 0 and is bumped by every successful set that
+ * changes at least one byte.  A set that changes nothing changes no state and makes no device call.
+ * mt_scene_get_materials returns the host copy.  Zero materials and n = 0 is MT_OK and does nothing, in both.
+ * CONTRACT: after mt_scene_set_materials(B), every call that renders or shades -- mt_render_chunk[_device], _ss,
+ * _adaptive, the tile and tile-list forms, mt_render_gbuffer, mt_render_lightbuffer, mt_shade_direct,
+ * mt_update_lightbuffer, mt_raytree_create[_rays], mt_trace_rays, mt_intersect_rays -- gives, byte for byte and plane
+ * for plane, what the same call gives on a scene newly created from the same description with materials B.
+ * Cost history, forecasts and engine choice are left as they are: they are forecasts, not results, and a frame under
+ * edited materials is scheduled by the costs of the frames before it.  G-buffer and light-buffer planes are the
+ * caller's: planes rendered before the edit describe the old materials.  Ray trees of the scene become STALE, see
+ * mt_raytree_update_materials.
+ * Argument checks come before any device call, in this order: the scene (NULL); n unequal to the scene's material
+ * count; a NULL array with n > 0; set only: a `tex` outside -1 .. n_textures - 1 (mt_scene_create's message).  All
+ * MT_ERR_ARG. */
+int mt_scene_set_materials(mt_scene *scene, const mt_material *materials, int n);
+int mt_scene_get_materials(const mt_scene *scene, mt_material *out, int n);
+
 /* MythTracer::RayTrace(WorkChunk*) (mythtracer.cc:280-312): renders the chunk
  * [chunk_x, chunk_x+chunk_w) x [chunk_y, chunk_y+chunk_h) of an image_w x
  * image_h image.  out_rgb: chunk_w*chunk_h*3 bytes, chunk-local row-major
@@ -530,7 +554,7 @@ int mt_update_lightbuffer_device(mt_scene *scene, int chunk_w, int chunk_h,
  * (mt_render_chunk's limits and messages), scene, sensor, max_depth in 0 .. MT_MAX_RECURSION.  mt_raytree_info: tree,
  * out.  mt_raytree_read_layer: tree, layer in 0 .. n_layers - 1, out, `pixel` for a layer other than 0.
  * mt_raytree_shade[_device]: the bitmap, tree, then the lights (n_lights < 0 or a NULL array of n_lights > 0; n_lights
- * unequal to the tree's). */
+ * unequal to the tree's), and last a tree that is stale after mt_scene_set_materials (mt_raytree_update_materials). */
 typedef struct mt_raytree mt_raytree;
 typedef struct mt_raytree_desc {
   int32_t n_layers, n_lights;
@@ -587,10 +611,57 @@ int mt_raytree_shade_device(mt_raytree *tree, const mt_light *lights, int n_ligh
  * call in flight per scene and per tree, as for the siblings (they share the work counter and the statistics); cost
  * history, engine choice, forecasts and mt_scene_kernel_times are left alone.
  * Argument checks come before any device call, in this order: the tree (NULL), the list (n_idx <= 0 or NULL), the
- * scene's current light count unequal to the tree's, an index outside 0 .. n_lights - 1, an index listed twice.  All
- * are MT_ERR_ARG; a tree of zero lights refuses every list. */
+ * scene's current light count unequal to the tree's, an index outside 0 .. n_lights - 1, an index listed twice, and
+ * last a tree that is stale after mt_scene_set_materials (mt_raytree_update_materials).  All are MT_ERR_ARG; a tree of
+ * zero lights refuses every list. */
 int mt_raytree_update_lights(mt_raytree *tree, const int32_t *light_idx, int n_idx, mt_stats *stats);
 int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, int n_idx, void *stream);
+
+/* Edited materials: a ray tree brought to the scene's CURRENT materials (mt_scene_set_materials) without tracing a
+ * primary or secondary ray -- or refused, and then left exactly as it was.  (No reference counterpart.)
+ * What a stored tree holds that depends on a material: albedo (the material's ambient, times the texel where it has a
+ * texture), coef (products of reflectance along the path), the child conditions (reflectance > 0, coef > 0.01,
+ * transparency > 0) and the light planes (transparency and transmission_filter of whatever a shadow ray crosses).
+ * Rays, hits, point, normal, material, in_object and pixel depend on no material.
+ * A tree remembers the materials it is valid for -- a host snapshot and the scene's generation, taken at creation and
+ * after each successful update.  After a mt_scene_set_materials that changed something, every tree of the scene is
+ * STALE: mt_raytree_shade[_device], mt_raytree_shade_colors[_device] and mt_raytree_update_lights[_device] refuse it with
+ * MT_ERR_ARG -- the LAST of each call's checks, after those listed above --; mt_raytree_info, _read_layer and _destroy
+ * keep working, and its planes are still the old materials' planes, untouched.
+ * The call: (1) tree NULL is MT_ERR_ARG; (2) equal generations: MT_OK, no device call, stats all zero; (3) the
+ * snapshot is compared with the scene's host copy, per material, doubles by their bits.
+ *   diffuse, specular, specular_exp, refraction_index, and transmission_filter of a material whose transparency is 0
+ *     before and after: nothing to do, the shade reads them from the scene.  No kernel is launched.
+ *   ambient or tex: where the material has a texture before or after the edit, MT_ERR_UNSUPPORTED before any device
+ *     call (the tree keeps neither the texel nor the primitive).  Otherwise every ray whose material it is gets
+ *     albedo = ambient, which is what the tracing kernel stores for an untextured material.
+ *   reflectance or transparency, of any material: the tree's shape may or may not survive.  A CHECK pass
+ *     (mt::raytree_recoef_kernel, one launch per layer, top-down) carries every ray's coefficient under the new
+ *     materials down the tree in the tree's scratch colours and evaluates the two child conditions exactly as the
+ *     tracing kernel does; a ray whose conditions differ from the children it has, in either direction, is counted.
+ *     The host reads the count: non-zero is MT_ERR_UNSUPPORTED with the count, and the layer and index of the first
+ *     such ray (the lowest layer, in it the lowest index), in the message; nothing but scratch has been written.
+ *   then the COMMIT (mt::raytree_recommit_kernel, one launch per layer that has something to take): the new
+ *     coefficients into coef of layers >= 1, the new ambient into albedo.
+ *   transparency of any material, or transmission_filter of one whose transparency is not 0 before or after: a shadow
+ *     ray may cross it whether or not a ray of the tree hits it, so after the commit the planes of ALL lights are
+ *     traced again in all layers under the scene's current lights, by mt_raytree_update_lights's kernel over the
+ *     indices 0 .. n_lights - 1 (the scene's light count must be the tree's: MT_ERR_ARG before any device call).  A
+ *     tree of zero lights skips this.
+ * CONTRACT: the update succeeds exactly when mt_raytree_create[_rays] under the new materials has the same rays per
+ * layer and the same child indices, and no textured material changed ambient or tex.  After a successful update the
+ * tree is bit-identical in every plane of every layer to that fresh tree (doubles with NaN = NaN, bytes and indices
+ * exactly), so mt_raytree_shade on it is mt_render_chunk(..., max_depth, ...) under the new materials byte for byte.
+ * After a refused update the tree's planes are bit-identical to what they were and the tree is still stale; setting
+ * the old materials back and updating again succeeds, with no launch beyond what that second comparison asks for.
+ * Synchronous; there is no _device form (the check pass needs its read-back, as mt_raytree_create does).  The scratch
+ * colours are the shade's: one shade OR one update in flight per tree, one call in flight per scene.  stats (nullable):
+ * rays_shadow and the traversal's counters from the light re-trace, if one ran (the counters are switched on for
+ * it); rays_primary = rays_secondary = shaded_hits = 0; kernel_ms = from the first to the last kernel by the tree's
+ * events (the check's read-back included), 0 when none ran; total_ms = wall time.  A tripped loop bound in the
+ * re-trace is MT_ERR_INTERNAL (a kernel logic error: the tree stays stale).  Cost history, engine choice and
+ * forecasts are left alone. */
+int mt_raytree_update_materials(mt_raytree *tree, mt_stats *stats);
 
 /* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
  * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour

@@ -36,6 +36,7 @@ HIP_SYMBOLS = [
     "mt_raytree_update_lights", "mt_raytree_update_lights_device",
     "mt_raytree_create_rays", "mt_raytree_create_rays_device", "mt_raytree_shade_colors",
     "mt_raytree_shade_colors_device", "mt_trace_rays",
+    "mt_scene_set_materials", "mt_scene_get_materials", "mt_raytree_update_materials",
 ]
 MT_MAX_RECURSION = 16
 
@@ -281,6 +282,9 @@ class HipAbi:
         L.mt_scene_destroy.argtypes = [vp]
         L.mt_scene_destroy.restype = None
         L.mt_scene_set_lights.argtypes = [vp, vp, ci]
+        L.mt_scene_set_materials.argtypes = [vp, vp, ci]
+        L.mt_scene_get_materials.argtypes = [vp, vp, ci]
+        L.mt_raytree_update_materials.argtypes = [vp, vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_chunk_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_tiles_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
@@ -355,6 +359,23 @@ class HipAbi:
                 getattr(out, name)[k] = s[i * 3 + k]
         return out
 
+    @staticmethod
+    def _material_array(mats):
+        """mt_material[max(n, 1)] from a list of dict(values = ka kd ks ns refl tr tf ni (16 doubles), tex = index or
+        -1): the `materials` of MythTracer.flatten()."""
+        marr = (mt_material * max(len(mats), 1))()
+        for i, m in enumerate(mats):
+            v = _f64(m["values"])  # ka kd ks ns refl tr tf ni
+            for k in range(3):
+                marr[i].ambient[k] = v[k]
+                marr[i].diffuse[k] = v[3 + k]
+                marr[i].specular[k] = v[6 + k]
+                marr[i].transmission_filter[k] = v[12 + k]
+            marr[i].specular_exp, marr[i].reflectance, marr[i].transparency = v[9], v[10], v[11]
+            marr[i].refraction_index = v[15]
+            marr[i].tex = int(m.get("tex", -1))
+        return marr
+
     def scene_create(self, flat: dict, device: int = 0):
         """flat: dict of numpy arrays in the layout of mt_scene_desc (see
         MythTracer.flatten()).  Returns an opaque handle."""
@@ -385,17 +406,7 @@ class HipAbi:
         d.tri_line_no = arr("tri_line_no", np.int32)
         d.tri_id = arr("tri_id", np.int32)
         mats = flat.get("materials", [])
-        marr = (mt_material * max(len(mats), 1))()
-        for i, m in enumerate(mats):
-            v = _f64(m["values"])  # ka kd ks ns refl tr tf ni
-            for k in range(3):
-                marr[i].ambient[k] = v[k]
-                marr[i].diffuse[k] = v[3 + k]
-                marr[i].specular[k] = v[6 + k]
-                marr[i].transmission_filter[k] = v[12 + k]
-            marr[i].specular_exp, marr[i].reflectance, marr[i].transparency = v[9], v[10], v[11]
-            marr[i].refraction_index = v[15]
-            marr[i].tex = int(m.get("tex", -1))
+        marr = self._material_array(mats)
         texs = flat.get("textures", [])
         tarr = (mt_texture * max(len(texs), 1))()
         for i, t in enumerate(texs):
@@ -420,6 +431,26 @@ class HipAbi:
     def set_lights(self, h, lights):
         l = _f64(lights).reshape(-1, 12)
         self.check(self.lib.mt_scene_set_lights(h, _ptr(l), l.shape[0]))
+
+    def set_materials(self, h, mats):
+        """mt_scene_set_materials: the constants of ALL the scene's materials replaced.  `mats` as flat["materials"] of
+        MythTracer.flatten(): a list, in the scene's order, of dict(values = 16 doubles, tex = index or -1)."""
+        mats = list(mats)
+        marr = self._material_array(mats)
+        self.check(self.lib.mt_scene_set_materials(h, C.cast(marr, C.c_void_p) if mats else None, len(mats)))
+
+    def get_materials(self, h, n):
+        """mt_scene_get_materials: the scene's current `n` materials in set_materials' form."""
+        marr = (mt_material * max(n, 1))()
+        self.check(self.lib.mt_scene_get_materials(h, C.cast(marr, C.c_void_p), n))
+        out = []
+        for i in range(n):
+            m = marr[i]
+            v = np.array(list(m.ambient) + list(m.diffuse) + list(m.specular) +
+                         [m.specular_exp, m.reflectance, m.transparency] + list(m.transmission_filter) +
+                         [m.refraction_index], dtype=np.float64)
+            out.append(dict(values=v, tex=int(m.tex)))
+        return out
 
     def set_traversal_mode(self, h, mode: int):
         self.check(self.lib.mt_scene_set_traversal_mode(h, mode))
@@ -717,6 +748,14 @@ class HipAbi:
         self.check(self.lib.mt_raytree_update_lights(tree, _ptr(idx), len(idx), C.addressof(st)))
         return st.as_dict()
 
+    def raytree_update_materials(self, tree) -> dict:
+        """mt_raytree_update_materials after set_materials: `tree` brought to the scene's current materials, or a
+        RuntimeError (code -3: the edit changes the tree's shape or a textured material's ambient) with the tree as it
+        was.  Returns the stats dict."""
+        st = mt_stats()
+        self.check(self.lib.mt_raytree_update_materials(tree, C.addressof(st)))
+        return st.as_dict()
+
     def raytree_update_lights_device(self, tree, light_indices, stream=None):
         """mt_raytree_update_lights_device: `light_indices` a host list; asynchronous on `stream`."""
         idx = _i32(light_indices).reshape(-1)
@@ -934,6 +973,8 @@ def host_lib():
     L.mth_raytree_handle.restype = vp
     L.mth_raytree_shade.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.mth_raytree_update.argtypes = [vp, vp, vp, ci, vp, vp]
+    L.mth_update_materials.argtypes = [vp, cs, vp]
+    L.mth_raytree_update_materials.argtypes = [vp, vp, vp, vp]
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1022,6 +1063,17 @@ class RayTree:
         ms = np.zeros(2)
         if not self.mt.L.mth_raytree_update(self.mt.h, self.h, _ptr(idx), len(idx), _ptr(st), _ptr(ms)):
             raise RuntimeError("UpdateRayTree failed: " + self.mt.last_error())
+        return dict(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def update_materials(self) -> dict:
+        """MythTracer::UpdateRayTreeMaterials after MythTracer.update_materials: the tree brought to the edited
+        materials without a primary or secondary ray, or a RuntimeError with the tree as it was (the edit changes its
+        shape, or a textured material's ambient).  Returns dict(counters, kernel_ms, total_ms)."""
+        self._tree()
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        if not self.mt.L.mth_raytree_update_materials(self.mt.h, self.h, _ptr(st), _ptr(ms)):
+            raise RuntimeError("UpdateRayTreeMaterials failed: " + self.mt.last_error())
         return dict(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
 
     def close(self):
@@ -1187,6 +1239,32 @@ class MythTracer:
         if not self.L.mth_get_material(self.h, name.encode(), _ptr(d), C.addressof(has_tex)):
             return None
         return d, bool(has_tex.value)
+
+    MATERIAL_FIELDS = dict(ka=(0, 3), kd=(3, 3), ks=(6, 3), ns=(9, 1), refl=(10, 1), tr=(11, 1), tf=(12, 3), ni=(15, 1))
+
+    def update_materials(self, edits=None):
+        """MythTracer::UpdateMaterials after an edit by material name and field: `edits` = {name: {field: value}} with
+        the fields ka kd ks (3 numbers each) ns refl tr (one) tf (3) ni (one) -- add_material's names; the other fields
+        keep their values.  None or {} only pushes the scene's current materials.  The constants are replaced on every
+        device replica without uploading the geometry again; RayTrees made before are stale until their
+        update_materials().  RuntimeError for an unknown name or field."""
+        edits = edits or {}
+        staged = []
+        for name, fields in edits.items():
+            got = self.get_material(name)
+            if got is None:
+                raise RuntimeError("UpdateMaterials failed: no material named %s" % name)
+            v = got[0].copy()
+            for field, value in fields.items():
+                if field not in self.MATERIAL_FIELDS:
+                    raise RuntimeError("UpdateMaterials failed: no material field %r (fields: %s)"
+                                       % (field, " ".join(self.MATERIAL_FIELDS)))
+                at, k = self.MATERIAL_FIELDS[field]
+                v[at:at + k] = _f64(value).reshape(k)
+            staged.append((name, v))
+        for name, v in staged or [(None, None)]:
+            if not self.L.mth_update_materials(self.h, name.encode() if name is not None else None, _ptr(v)):
+                raise RuntimeError("UpdateMaterials failed: " + self.last_error())
 
     @property
     def num_materials(self):

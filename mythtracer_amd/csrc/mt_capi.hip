@@ -267,6 +267,11 @@ struct mt_scene {
   Buf<mt_light> d_shade_lights;
   Buf<int32_t> d_update_idx;  // mt_update_lightbuffer: a list of more than kUpdateArgLights light indices
   int n_materials = 0;  // of dev.mtls (shade_direct_kernel checks the caller's material plane against it)
+  // mt_scene_set_materials: what dev.mtls holds, how often it has changed since mt_scene_create, and the texture count
+  // a material's `tex` is checked against
+  std::vector<mt_material> mtls_host;
+  unsigned long long mtl_generation = 0;
+  int n_textures = 0;
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -1453,6 +1458,8 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   }
   if ((rc = upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls)) != MT_OK) return rc;
   s->n_materials = d->n_materials;
+  s->n_textures = d->n_textures;
+  if (d->n_materials > 0) s->mtls_host.assign(d->materials, d->materials + d->n_materials);
   std::vector<DevTexture> texs((size_t)d->n_textures);
   for (int i = 0; i < d->n_textures; i++) {
     const mt_texture &t = d->textures[i];
@@ -1541,6 +1548,37 @@ int mt_scene_set_lights(mt_scene *s, const mt_light *lights, int n) {
   }
   s->dev.lights = s->d_lights;
   s->dev.n_lights = n;
+  return MT_OK;
+}
+
+// checked before any device call, in the order of the header
+static int check_materials_args(const mt_scene *s, const void *materials, int n) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (n != s->n_materials) return fail(MT_ERR_ARG, "%d materials for a scene made with %d", n, s->n_materials);
+  if (n > 0 && !materials) return fail(MT_ERR_ARG, "the material array is NULL");
+  return MT_OK;
+}
+
+int mt_scene_set_materials(mt_scene *s, const mt_material *materials, int n) {
+  MT_TRY(check_materials_args(s, materials, n));
+  for (int i = 0; i < n; i++) {
+    const int t = materials[i].tex;
+    if (t < -1 || t >= s->n_textures) {
+      return fail(MT_ERR_ARG, "material %d: texture index %d outside -1..%d", i, t, s->n_textures - 1);
+    }
+  }
+  if (n == 0 || memcmp(s->mtls_host.data(), materials, (size_t)n * sizeof(mt_material)) == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the table while it changes
+  HIP_TRY(hipMemcpy(const_cast<mt_material *>(s->dev.mtls), materials, (size_t)n * sizeof(mt_material), hipMemcpyHostToDevice));
+  s->mtls_host.assign(materials, materials + n);
+  s->mtl_generation++;
+  return MT_OK;
+}
+
+int mt_scene_get_materials(const mt_scene *s, mt_material *out, int n) {
+  MT_TRY(check_materials_args(s, out, n));
+  if (n > 0) memcpy(out, s->mtls_host.data(), (size_t)n * sizeof(mt_material));
   return MT_OK;
 }
 
@@ -2623,6 +2661,13 @@ struct mt_raytree {
   uint8_t *d_rgb = nullptr;                // the host shade's bitmap (first use)
   double *d_out_color = nullptr;           // the host shade's colours (first use)
   unsigned int *d_bad = nullptr;           // a ray-list tree: raytree_rays_kernel's count and lowest index of refused rays
+  // mt_raytree_update_materials: the materials the planes are valid for (the scene's at creation or at the last
+  // successful update) and the scene's generation then; raytree_recoef_kernel's two words and raytree_recommit_kernel's
+  // byte per material (first use)
+  std::vector<mt_material> mtls;
+  unsigned long long mtl_generation = 0;
+  unsigned long long *d_mismatch = nullptr;
+  uint8_t *d_albedo_changed = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_layer[MT_MAX_RECURSION + 1][2] = {};
 };
@@ -2707,6 +2752,16 @@ int check_raytree_rays_args(const mt_scene *s, const mt_ray_list *rays, int max_
   return MT_OK;
 }
 
+// a tree whose scene's materials were edited since it was made or last updated is stale (the last check of every
+// call that shades or re-traces it)
+int check_raytree_fresh(const mt_raytree *t) {
+  if (t->mtl_generation != t->scene->mtl_generation) {
+    return fail(MT_ERR_ARG, "the scene's materials were edited after the ray tree was made: mt_raytree_update_materials "
+                            "or a new tree is needed");
+  }
+  return MT_OK;
+}
+
 int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_lights, const void *out,
                              const char *no_output = "the output bitmap is NULL") {
   if (!out) return fail(MT_ERR_ARG, "%s", no_output);
@@ -2715,7 +2770,7 @@ int check_raytree_shade_args(const mt_raytree *t, const mt_light *lights, int n_
   if (n_lights != t->info.n_lights) {
     return fail(MT_ERR_ARG, "%d lights for a ray tree made with %d", n_lights, t->info.n_lights);
   }
-  return MT_OK;
+  return check_raytree_fresh(t);
 }
 
 // mt_raytree_update_lights[_device]: checked before any device call, in the order of the header.
@@ -2737,7 +2792,7 @@ int check_raytree_update_args(const mt_raytree *t, const int32_t *light_idx, int
     if (seen[(size_t)light_idx[i]]) return fail(MT_ERR_ARG, "light index %d is listed twice", light_idx[i]);
     seen[(size_t)light_idx[i]] = true;
   }
-  return MT_OK;
+  return check_raytree_fresh(t);
 }
 
 // raytree_update_kernel over all layers x the listed lights, one launch; light_idx = host array
@@ -2905,6 +2960,8 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
     HIP_TRY(hipEventElapsedTime(&ms, t->ev_layer[k][0], t->ev_layer[k][1]));
     t->info.trace_ms[k] = ms;
   }
+  t->mtls = s->mtls_host;
+  t->mtl_generation = s->mtl_generation;
   if (stats) {
     memset(stats, 0, sizeof *stats);
     fill_stats(s->h_counters, stats);
@@ -2971,6 +3028,8 @@ void mt_raytree_destroy(mt_raytree *t) {
   if (t->d_rgb) (void)hipFree(t->d_rgb);
   if (t->d_out_color) (void)hipFree(t->d_out_color);
   if (t->d_bad) (void)hipFree(t->d_bad);
+  if (t->d_mismatch) (void)hipFree(t->d_mismatch);
+  if (t->d_albedo_changed) (void)hipFree(t->d_albedo_changed);
   if (t->ev0) (void)hipEventDestroy(t->ev0);
   if (t->ev1) (void)hipEventDestroy(t->ev1);
   for (auto &e : t->ev_layer) {
@@ -3185,6 +3244,141 @@ int mt_raytree_update_lights(mt_raytree *t, const int32_t *light_idx, int n_idx,
     stats->kernel_ms = ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   }
+  return MT_OK;
+}
+
+namespace {
+
+bool same_bits(const double *a, const double *b, int n) { return memcmp(a, b, (size_t)n * sizeof(double)) == 0; }
+
+// what the edit from `was` to `now` asks of a stored tree
+struct MaterialDiff {
+  bool shape = false;    // a reflectance or transparency changed: the check pass
+  bool shadow = false;   // a shadow ray may see the change: the light planes again
+  bool albedo = false;   // some ambient changed
+  int textured = -1;     // the first textured material whose ambient or tex changed
+  std::vector<uint8_t> albedo_changed;
+};
+
+void diff_materials(const std::vector<mt_material> &was, const std::vector<mt_material> &now, MaterialDiff *out) {
+  MaterialDiff &D = *out;
+  D.albedo_changed.assign(now.size(), 0);
+  for (size_t i = 0; i < now.size(); i++) {
+    const mt_material &a = was[i], &b = now[i];
+    if (!same_bits(a.ambient, b.ambient, 3) || a.tex != b.tex) {
+      D.albedo = true;
+      D.albedo_changed[i] = 1;
+      if ((a.tex >= 0 || b.tex >= 0) && D.textured < 0) D.textured = (int)i;
+    }
+    const bool refl = !same_bits(&a.reflectance, &b.reflectance, 1);
+    const bool tr = !same_bits(&a.transparency, &b.transparency, 1);
+    if (refl || tr) D.shape = true;
+    const bool opaque = a.transparency == 0.0 && b.transparency == 0.0;  // (the shadow loop's own test)
+    if (tr || (!same_bits(a.transmission_filter, b.transmission_filter, 3) && !opaque)) D.shadow = true;
+  }
+}
+
+}  // namespace
+
+int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  const auto w0 = std::chrono::steady_clock::now();
+  mt_scene *s = t->scene;
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (t->mtl_generation == s->mtl_generation) return MT_OK;
+  MaterialDiff D;
+  diff_materials(t->mtls, s->mtls_host, &D);
+  if (D.textured >= 0) {
+    return fail(MT_ERR_UNSUPPORTED, "material %d has a texture and its ambient or tex changed: the ray tree keeps neither "
+                                    "the texel nor the primitive, a new tree is needed", D.textured);
+  }
+  const mt_raytree_desc &I = t->info;
+  const bool retrace = D.shadow && I.n_lights > 0;
+  if (retrace && s->dev.n_lights != I.n_lights) {
+    return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", s->dev.n_lights, I.n_lights);
+  }
+  if (D.shape || D.albedo || retrace) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = nullptr;
+    const int n_mtl = s->n_materials;
+    HIP_TRY(hipEventRecord(t->ev0, stream));
+    if (D.shape) {
+      if (!t->d_mismatch) {
+        MT_TRY(raytree_malloc((void **)&t->d_mismatch, 2 * sizeof(unsigned long long), "the ray tree's mismatch count"));
+      }
+      HIP_TRY(hipMemsetAsync(t->d_mismatch, 0, sizeof(unsigned long long), stream));
+      HIP_TRY(hipMemsetAsync(t->d_mismatch + 1, 0xff, sizeof(unsigned long long), stream));
+      for (int k = 0; k < I.n_layers; k++) {
+        const size_t n = (size_t)I.n_rays[k];
+        RayTreeRecoefArgs A{};
+        A.L = t->layer[k];
+        A.child_scratch = k + 1 < I.n_layers ? t->layer[k + 1].color : nullptr;
+        A.mtls = s->dev.mtls;
+        A.n_rays = (uint32_t)n;
+        A.n_materials = n_mtl;
+        A.layer = k;
+        A.may_spawn = k < I.max_depth ? 1 : 0;
+        A.mismatch = t->d_mismatch;
+        hipLaunchKernelGGL(raytree_recoef_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+        HIP_TRY(hipGetLastError());
+      }
+      unsigned long long found[2] = {0, 0};
+      HIP_TRY(hipMemcpyAsync(found, t->d_mismatch, sizeof found, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      if (found[0] != 0) {
+        return fail(MT_ERR_UNSUPPORTED, "the new materials change the shape of the ray tree: %llu rays spawn other "
+                                        "children, the first in layer %d at ray %llu; a new tree is needed",
+                    found[0], (int)(found[1] >> 32), found[1] & 0xffffffffull);
+      }
+    }
+    if (D.albedo) {
+      if (!t->d_albedo_changed) {
+        MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
+      }
+      HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
+    }
+    for (int k = 0; k < I.n_layers; k++) {
+      const size_t n = (size_t)I.n_rays[k];
+      RayTreeRecommitArgs A{};
+      A.L = t->layer[k];
+      A.mtls = s->dev.mtls;
+      A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+      A.n_rays = (uint32_t)n;
+      A.n_materials = n_mtl;
+      A.copy_coef = D.shape && k > 0 ? 1 : 0;
+      if (!A.copy_coef && !A.albedo_changed) continue;
+      hipLaunchKernelGGL(raytree_recommit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+      HIP_TRY(hipGetLastError());
+    }
+    if (retrace) {
+      std::vector<int32_t> all((size_t)I.n_lights);
+      for (int i = 0; i < I.n_lights; i++) all[(size_t)i] = i;
+      MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+      HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+      const bool counters_were = s->stats_enabled;
+      if (stats) s->stats_enabled = true;  // the caller asked for them
+      const int rc = launch_raytree_update(t, all.data(), I.n_lights, stream);
+      s->stats_enabled = counters_were;
+      if (rc != MT_OK) return rc;
+      HIP_TRY(hipEventRecord(t->ev1, stream));
+      HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      MT_TRY(check_status(s->h_counters));
+      if (stats) fill_stats(s->h_counters, stats);
+    } else {
+      HIP_TRY(hipEventRecord(t->ev1, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (stats) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+      stats->kernel_ms = ms;
+    }
+  }
+  t->mtls = s->mtls_host;
+  t->mtl_generation = s->mtl_generation;
+  if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   return MT_OK;
 }
 

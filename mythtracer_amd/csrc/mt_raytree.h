@@ -587,4 +587,84 @@ __global__ __launch_bounds__(256) void raytree_color_kernel(const double *color,
   store3(out, (size_t)pixel[i], v3_load(color + i * 3));
 }
 
+// ---- edited materials (include/mythtracer_hip.h, mt_raytree_update_materials) ----
+// What a stored tree holds that depends on a material: albedo (the material's ambient), coef (products of reflectance
+// along the path), the child conditions (reflectance, transparency, coef) and the light planes.  The last are
+// raytree_update_kernel's, unchanged; the first three are these two kernels', plain grids, one thread per ray.
+// raytree_recoef_kernel    the CHECK pass, one launch per layer, top-down.  The ray's coefficient c under the new
+//                          materials is coef[i] in layer 0 (nothing above it) and, deeper, what its parent's thread
+//                          left in color[i][0] -- the shade's scratch plane: one shade OR one update in flight per
+//                          tree.  The two child conditions exactly as raytree_trace_kernel evaluates them, from the NEW
+//                          materials, c, in_object[i], may_spawn and lit (point[i][0] not NaN, 0 <= material[i] <
+//                          n_materials), are compared with child_refl[i] >= 0 and child_refr[i] >= 0: a mismatch in
+//                          either direction adds one to mismatch[0] and offers (layer << 32 | i) to mismatch[1]
+//                          (atomicMin).  Where the TREE has a child, its new coefficient goes to the child's scratch
+//                          with raytree_spawn_kernel's expressions.  Writes nothing but scratch and the two words.
+// raytree_recommit_kernel  the COMMIT, one launch per layer that has something to take: coef[i] = the scratch's
+//                          coefficient (copy_coef: layers >= 1 after a clean check), and albedo[i] = the new ambient for
+//                          the rays whose material's byte in `albedo_changed` is set -- what write_gbuffer_planes
+//                          stores for an untextured material, no arithmetic.
+struct RayTreeRecoefArgs {
+  RayTreeLayer L;
+  double *child_scratch;         // the next layer's color plane, nullptr: there is no next layer
+  const mt_material *mtls;       // the scene's CURRENT materials
+  uint32_t n_rays;
+  int32_t n_materials;
+  int32_t layer;
+  int32_t may_spawn;             // layer < max_depth
+  unsigned long long *mismatch;  // [2] at the first layer's launch: 0, ~0
+};
+
+__global__ __launch_bounds__(256) void raytree_recoef_kernel(RayTreeRecoefArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_rays) return;
+  const double c = A.layer == 0 ? A.L.coef[i] : A.L.color[i * 3];
+  const double p0 = A.L.point[i * 3];
+  const int mtl = A.L.material[i];
+  const bool lit = p0 == p0 && mtl >= 0 && mtl < A.n_materials;
+  const int cr = A.L.child_refl[i], ct = A.L.child_refr[i];
+  // the child conditions, :181-184 and :192, as raytree_trace_kernel states them
+  unsigned spawn = 0;
+  double reflectance = 0.0;
+  if (lit && A.may_spawn) {
+    const mt_material *m = A.mtls + mtl;
+    const bool in_object = A.L.in_object[i] != 0;
+    reflectance = m->reflectance;
+    if (m->reflectance > 0.0 && c > 0.01 && !in_object) spawn |= 1u;
+    if (m->transparency > 0.0) spawn |= 2u;
+  }
+  const unsigned has = (cr >= 0 ? 1u : 0u) | (ct >= 0 ? 2u : 0u);
+  if (spawn != has) {
+    atomicAdd(A.mismatch, 1ull);
+    atomicMin(A.mismatch + 1, ((unsigned long long)(unsigned)A.layer << 32) | (unsigned long long)i);
+  }
+  if (A.child_scratch != nullptr) {
+    // (a child of a ray that is not lit cannot exist; `reflectance` is then 0 and nothing is stored)
+    if (cr >= 0) A.child_scratch[(size_t)cr * 3] = c * reflectance;  // :187
+    if (ct >= 0) A.child_scratch[(size_t)ct * 3] = c;                // :223
+  }
+}
+
+struct RayTreeRecommitArgs {
+  RayTreeLayer L;
+  const mt_material *mtls;        // the scene's CURRENT materials
+  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
+  uint32_t n_rays;
+  int32_t n_materials;
+  int32_t copy_coef;
+};
+
+__global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_rays) return;
+  if (A.copy_coef) A.L.coef[i] = A.L.color[i * 3];
+  if (A.albedo_changed != nullptr) {
+    const int mtl = A.L.material[i];
+    if (mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
+      const mt_material *m = A.mtls + mtl;
+      store3(A.L.albedo, i, v3(m->ambient[0], m->ambient[1], m->ambient[2]));
+    }
+  }
+}
+
 }  // namespace mt

@@ -15,6 +15,10 @@ struct FlatScene {
   std::vector<double> vertex, normal, uvw, aabb;
   std::vector<int32_t> material, line_no;
   std::vector<mt_material> materials;
+  // the dense tables' sources, in the tables' order (order of first use): MythTracer::UpdateMaterials flattens the
+  // same materials again
+  std::vector<const Material*> material_of;
+  std::vector<const Texture*> texture_of;
   std::vector<mt_texture> textures;            // texels point into the two below / the Scene
   std::vector<std::vector<uint8_t>> rgb8;      // packed 8-bit texels, one per texture (or empty)
   std::string error;
@@ -24,6 +28,8 @@ struct FlatScene {
   bool Build(const Scene& scene);
   // A descriptor whose pointers refer to this object and to scene.tree.Flat().
   mt_scene_desc Describe(const Scene& scene, int device) const;
+  // One entry of `materials` from a Material; tex = its texture's index in `textures`, or -1.
+  static mt_material FlatMaterial(const Material& m, int32_t tex);
 };
 
 }  // namespace raytracer

@@ -205,6 +205,19 @@ class MythTracer {
   // is refused by mt_raytree_update_lights, after the facade has uploaded GetScene()->lights; the tree is untouched in
   // every case.  LastStats() describes the call.
   bool UpdateRayTree(const std::vector<int>& lights, RayTree* tree);
+  // After materials were EDITED in GetScene()->materials (a wall's colour, a mirror's reflectance): flattens them into
+  // the dense table in its uploaded order (order of first use) and replaces the constants on every device replica
+  // (mt_scene_set_materials), without uploading a triangle again; every later RayTrace, G-buffer, light buffer and
+  // BuildRayTree sees them.  Refused with a message when the set of material NAMES differs from the uploaded one (the
+  // call edits, it neither adds nor removes) or a material points at a texture that was not uploaded.  Before the
+  // first upload it is Prepare.  RayTrees built before the edit are stale until UpdateRayTreeMaterials.
+  bool UpdateMaterials();
+  // Brings `tree` to the materials of the last UpdateMaterials without tracing a primary or secondary ray
+  // (mt_raytree_update_materials): new albedo and coefficients, and the light planes again where a shadow ray can see
+  // the edit (under GetScene()->lights).  Fails, with the tree exactly as it was, when the edit changes which rays
+  // spawn children or touches the ambient of a textured material: a new BuildRayTree is needed then.  Refused with
+  // several devices, like BuildRayTree, and for a NULL or empty RayTree.  LastStats() describes the call.
+  bool UpdateRayTreeMaterials(RayTree* tree);
   // The caller's rays instead of a camera's (mt_raytree_create_rays): TraceRay for a ray list, to the recursion level of
   // SetMaxRecursionLevel under GetScene()->lights.  list_width 0 means an n x 1 list, whose waves are 64 consecutive
   // rays of the caller's; otherwise it must divide n and the list is treated as a list_width x (n / list_width) image,
@@ -242,6 +255,8 @@ class MythTracer {
   std::vector<int> devices_;           // empty = {device_}
   int device_ = 0;
   void DropDeviceScenes();
+  std::vector<std::string> uploaded_names_, dense_names_;  // UpdateMaterials: all names at the upload; the dense table's
+  std::vector<const Texture*> uploaded_textures_;          // ... and the texture table's sources
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
   int adaptive_ss_ = 1, adaptive_threshold_ = 16;

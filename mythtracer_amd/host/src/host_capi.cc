@@ -540,6 +540,48 @@ int mth_raytree_update(void* p, void* t, const int* light_idx, int n_idx, uint64
   return 1;
 }
 
+// MythTracer::UpdateMaterials after an edit of one material by name: values16 = ka kd ks ns refl tr tf ni (mth_get_material's
+// order), NULL = no edit, only the update.  0 with the facade's message when it refuses; an unknown name is the shim's.
+int mth_update_materials(void* p, const char* name, const double* values16) {
+  Handle* h = static_cast<Handle*>(p);
+  if (name != nullptr && values16 != nullptr) {
+    auto& mats = h->mt.GetScene()->materials;
+    auto it = mats.find(name);
+    if (it == mats.end()) {
+      h->shim_error = std::string("no material named ") + name;
+      return 0;
+    }
+    Material& m = *it->second;
+    const double* v = values16;
+    m.ambient = {v[0], v[1], v[2]};
+    m.diffuse = {v[3], v[4], v[5]};
+    m.specular = {v[6], v[7], v[8]};
+    m.specular_exp = v[9];
+    m.reflectance = v[10];
+    m.transparency = v[11];
+    m.transmission_filter = {v[12], v[13], v[14]};
+    m.refraction_index = v[15];
+  }
+  return h->mt.UpdateMaterials() ? 1 : 0;
+}
+
+// MythTracer::UpdateRayTreeMaterials; stats8 / ms2 as mth_raytree_update fills them
+int mth_raytree_update_materials(void* p, void* t, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  if (!h->mt.UpdateRayTreeMaterials(static_cast<raytracer::RayTree*>(t))) return 0;
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::UpdateLightBuffer(GBuffer, lights, LightBuffer*) under the facade's lights.  gb_planes[2] = point
 // (doubles), material (int32) of the cw x ch chunk; lb_channels = LightBuffer::k* bits, lb_planes[2] = power, in_shadow
 // for n_lights lights (each NULL or sized for them), updated in place: the planes of the listed lights only.

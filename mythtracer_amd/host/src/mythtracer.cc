@@ -3,6 +3,7 @@
 // loop (mythtracer.cc:292-305) is one kernel launch behind mt_render_chunk.
 #include "mythtracer.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -110,19 +111,9 @@ bool FlatScene::Build(const Scene& scene) {
     line_no[s] = t->debug_line_no;
   }
   materials.assign(mtls.size(), mt_material{});
-  for (size_t i = 0; i < mtls.size(); i++) {
-    const Material& m = *mtls[i];
-    mt_material& o = materials[i];
-    memcpy(o.ambient, m.ambient.v, 24);
-    memcpy(o.diffuse, m.diffuse.v, 24);
-    memcpy(o.specular, m.specular.v, 24);
-    memcpy(o.transmission_filter, m.transmission_filter.v, 24);
-    o.specular_exp = m.specular_exp;
-    o.reflectance = m.reflectance;
-    o.transparency = m.transparency;
-    o.refraction_index = m.refraction_index;
-    o.tex = m.tex ? tex_index[m.tex] : -1;
-  }
+  for (size_t i = 0; i < mtls.size(); i++) materials[i] = FlatMaterial(*mtls[i], mtls[i]->tex ? tex_index[mtls[i]->tex] : -1);
+  material_of = mtls;
+  texture_of = texs;
   textures.assign(texs.size(), mt_texture{});
   rgb8.assign(texs.size(), {});
   for (size_t i = 0; i < texs.size(); i++) {
@@ -143,6 +134,20 @@ bool FlatScene::Build(const Scene& scene) {
     }
   }
   return true;
+}
+
+mt_material FlatScene::FlatMaterial(const Material& m, int32_t tex) {
+  mt_material o{};
+  memcpy(o.ambient, m.ambient.v, 24);
+  memcpy(o.diffuse, m.diffuse.v, 24);
+  memcpy(o.specular, m.specular.v, 24);
+  memcpy(o.transmission_filter, m.transmission_filter.v, 24);
+  o.specular_exp = m.specular_exp;
+  o.reflectance = m.reflectance;
+  o.transparency = m.transparency;
+  o.refraction_index = m.refraction_index;
+  o.tex = tex;
+  return o;
 }
 
 mt_scene_desc FlatScene::Describe(const Scene& scene, int device) const {
@@ -202,6 +207,84 @@ bool MythTracer::Prepare() {
     if (r == 0) dev_ = s;
     else replicas_.push_back(s);
   }
+  // what UpdateMaterials needs of this upload: every material's name, the dense table's names in its order, the
+  // uploaded textures
+  uploaded_names_.clear();
+  for (const auto& kv : scene.materials) uploaded_names_.push_back(kv.first);
+  std::sort(uploaded_names_.begin(), uploaded_names_.end());
+  dense_names_.assign(flat.material_of.size(), std::string());
+  for (const auto& kv : scene.materials) {
+    for (size_t i = 0; i < flat.material_of.size(); i++) {
+      if (flat.material_of[i] == kv.second.get()) dense_names_[i] = kv.first;
+    }
+  }
+  uploaded_textures_ = flat.texture_of;
+  return true;
+}
+
+bool MythTracer::UpdateMaterials() {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes them as they are
+  std::vector<std::string> names;
+  for (const auto& kv : scene.materials) names.push_back(kv.first);
+  std::sort(names.begin(), names.end());
+  if (names != uploaded_names_) {
+    return refuse("the scene's materials are not the uploaded ones by name: UpdateMaterials edits, it neither adds nor removes");
+  }
+  std::vector<mt_material> table(dense_names_.size());
+  for (size_t i = 0; i < dense_names_.size(); i++) {
+    const Material& m = *scene.materials.at(dense_names_[i]);
+    int32_t tex = -1;
+    if (m.tex != nullptr) {
+      for (size_t k = 0; k < uploaded_textures_.size(); k++) {
+        if (uploaded_textures_[k] == m.tex) tex = (int32_t)k;
+      }
+      if (tex < 0) return refuse("material " + dense_names_[i] + " points at a texture that was not uploaded");
+    }
+    table[i] = FlatScene::FlatMaterial(m, tex);
+  }
+  std::vector<mt_scene*> all(1, dev_);
+  all.insert(all.end(), replicas_.begin(), replicas_.end());
+  for (mt_scene* s : all) {
+    if (mt_scene_set_materials(s, table.data(), (int)table.size()) != MT_OK) {
+      return refuse(std::string("material update failed: ") + mt_last_error());
+    }
+  }
+  return true;
+}
+
+bool MythTracer::UpdateRayTreeMaterials(RayTree* tree) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (the facade's own refusals, before anything touches a device)
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (tree == nullptr) return refuse("RayTree is NULL");
+  if (tree->Empty()) return refuse("the RayTree is empty: BuildRayTree first");
+  if (dev_ != nullptr &&
+      mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("ray-tree material update failed: ") + mt_last_error());
+  }
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  if (dev_ != nullptr) (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_raytree_update_materials(tree->Get(), &st) != MT_OK) {
+    return refuse(std::string("ray-tree material update failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
   return true;
 }
 
