@@ -87,9 +87,11 @@ def oracle_intersector(orc):
     return intersect
 
 
-def shadow_loops(intersect, point, lit, lights):
+def shadow_loops(intersect, point, lit, lights, info=None):
     """point (ch, cw, 3), lit (ch, cw) = the pixels for which the reference enters the light loop.  Returns
-    power (n_lights, ch, cw, 3), in_shadow (n_lights, ch, cw) uint8 with 255 where not lit, iterations (n_lights, ch, cw)."""
+    power (n_lights, ch, cw, 3), in_shadow (n_lights, ch, cw) uint8 with 255 where not lit, iterations (n_lights, ch, cw).
+    info: a dict that receives how often each way out of the loop was taken and what kind of occluder was met (for
+    tests/hostile_scenes.py, which counts the iterations an unusual value decides)."""
     ch, cw = lit.shape
     n = ch * cw
     P = np.ascontiguousarray(point, dtype=np.float64).reshape(n, 3)
@@ -99,6 +101,9 @@ def shadow_loops(intersect, point, lit, lights):
     shadow = np.full((len(L), n), 255, dtype=np.uint8)
     iterations = np.zeros((len(L), n), dtype=np.int32)
     idx0 = np.nonzero(lit)[0]
+    ends = dict.fromkeys(("ended_behind_the_light", "ended_past_the_light", "ended_opaque", "light_within_1e-5_of_start",
+                          "occluders_negative_tr", "occluders_negative_zero_tr", "occluders_hostile_tr",
+                          "dim_at_exactly_0.001", "one_channel_above_0.001", "t_equals_light_distance"), 0)
     for li, light in enumerate(L):
         lpos = np.broadcast_to(light[0:3], (len(idx0), 3))
         Pt = P[idx0]
@@ -129,11 +134,25 @@ def shadow_loops(intersect, point, lit, lights):
             start[t] = r["point"][through] + (ld[t] * 0.0000001)  # :137
             past = _sqr_distance(Pt[t], start[t]) > _sqr_distance(Pt[t], lpos[t])  # :141-145
             dim = ~past & (lp[t] <= 0.001).all(axis=1)            # :149-155
+            dim_exact = int((dim & (lp[t] == 0.001).any(axis=1)).sum())
             lp[t[dim]] = 0.0
             in_shadow[t[dim]] = True
             running[t[past | dim]] = False
+            tr_ = r["transparency"]
+            ends["ended_behind_the_light"] += int(behind.sum())
+            ends["ended_past_the_light"] += int(past.sum())
+            ends["ended_opaque"] += int(opaque.sum())
+            ends["light_within_1e-5_of_start"] += int((light_distance < 0.00001).sum())
+            ends["occluders_negative_tr"] += int((through & (tr_ < 0.0)).sum())
+            ends["occluders_negative_zero_tr"] += int((opaque & np.signbit(tr_)).sum())
+            ends["occluders_hostile_tr"] += int((through & ((tr_ >= 1.0) | (tr_ < 1e-3) | (r["filter"] == 0.0).any(axis=1))).sum())
+            ends["dim_at_exactly_0.001"] += dim_exact
+            ends["t_equals_light_distance"] += int((hit & (r["t"] == light_distance)).sum())
+            ends["one_channel_above_0.001"] += int((~past & ~dim & ((lp[t] <= 0.001).sum(axis=1) == 2)).sum())
         power[li, idx0] = lp
         shadow[li, idx0] = in_shadow
+    if info is not None:
+        info.update(ends)
     return dict(power=power.reshape(len(L), ch, cw, 3), in_shadow=shadow.reshape(len(L), ch, cw),
                 iterations=iterations.reshape(len(L), ch, cw))
 

@@ -242,8 +242,9 @@ RAYOUT_DTYPE = np.dtype([("line", "<i4"), ("t", "<f8"), ("point", "<f8", 3),
 
 def run_ref(workdir, obj, image=None, chunk=None, cam=None, lights=(),
             want_rgb=True, want_debug=False, rays=None, want_sensor=False,
-            repeat=1, threads=None):
-    """Runs one job through the compiled reference; returns a dict."""
+            repeat=1, threads=None, timeout=None):
+    """Runs one job through the compiled reference; returns a dict.  A run that takes longer than `timeout` seconds is
+    killed and reported with returncode None."""
     os.makedirs(workdir, exist_ok=True)
     job = ["obj %s" % obj]
     W, H = image if image else (0, 0)
@@ -273,7 +274,10 @@ def run_ref(workdir, obj, image=None, chunk=None, cam=None, lights=(),
     env = dict(os.environ)
     if threads:
         env["OMP_NUM_THREADS"] = str(threads)
-    r = subprocess.run([REF_DRIVER, jpath], env=env, stderr=subprocess.PIPE)
+    try:
+        r = subprocess.run([REF_DRIVER, jpath], env=env, stderr=subprocess.PIPE, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        return dict(returncode=None, stderr="no end within %s s" % timeout)
     out["returncode"] = r.returncode
     out["stderr"] = r.stderr.decode(errors="replace")
     if r.returncode != 0:

@@ -350,6 +350,12 @@ def orc_bytes(color):
     return np.array([orclib.v3d_to_rgb(c) for c in color.reshape(-1, 3)], dtype=np.uint8)
 
 
+def specular_bound(ref):
+    """The bound test_linear_colours derives for a colour with specular terms below it (tests/test_gpu_hostile.py imports
+    it): ulps x lights x layers with factors of order one, 1e-12 max(1, |c|)."""
+    return 1e-12 * np.maximum(1.0, np.abs(ref))
+
+
 @pytest.mark.parametrize("kind", ["sensor", "panorama"])
 def test_linear_colours(kind, make, two_way):
     """V3DtoRGB of mt_raytree_shade_colors[_device] is mt_raytree_shade's bitmap exactly.  Against the restatement's
@@ -395,7 +401,7 @@ def test_linear_colours(kind, make, two_way):
         plain = same_bits(c[~spec], ref[~spec], "%s edit %s: rays without a specular term" % (kind, k))
         assert plain == 0 and (~spec).any() and spec.any()
         d = np.abs(c[spec] - ref[spec])
-        bound = 1e-12 * np.maximum(1.0, np.abs(ref[spec]))
+        bound = specular_bound(ref[spec])
         largest = max(largest, float(d.max()))
         print("%s edit %s: %d rays with a specular term, largest |d| %.3e (largest colour %.3f), %d channels not bit-equal"
               % (kind, k, int(spec.sum()), d.max(), np.abs(ref[spec]).max(), int((d > 0).sum())))
