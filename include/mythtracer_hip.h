@@ -861,6 +861,10 @@ enum {
   MT_TUNE_SM_CELL_TIME, MT_TUNE_SM_CELL_WORK, /* a cell's expected time / the cells' summed cost, over the block as one unit */
   MT_TUNE_HYBRID_CELL_FACTOR, /* engine 3: the pool's pieces of a block are 2x2 cells when a quarter is expected above this
                                  multiple of the pool's threshold (0.85; the ray pool by itself: MT_TUNE_POOL_CELL_FACTOR) */
+  MT_TUNE_LEAN_KERNEL,        /* state-machine launches with a cost history, traversal mode 0, a scene the hit-set walk takes:
+                                 the LEAN frame kernel (the walk alone; a unit that meets a ray the walk cannot take is
+                                 abandoned and rendered by the full kernel in a launch behind it).  0 = never; 1 (default)
+                                 = unless a primary ray of the frame has a zero direction component; 2 = even then (tests) */
   MT_TUNE_COUNT
 };
 int mt_scene_set_tuning(mt_scene *scene, int knob, double value);
@@ -877,6 +881,18 @@ int mt_scene_set_tuning(mt_scene *scene, int knob, double value);
  * reference times a frame with wall clocks, main_local.cc:86-101.) */
 int mt_scene_kernel_times(mt_scene *scene, int max_n, double *primary_ms,
                           double *render_ms);
+
+/* What the scene's last launch was (MT_TUNE_LEAN_KERNEL).  lean = 1: its frame kernel was the lean one, and then:
+ * units = work units of its order; redo_units = those the full kernel rendered in the redo launch (abandoned by the
+ * lean kernel, or all of them: handed_over = 1, the lean kernel opened none because earlier lean launches of the scene
+ * abandoned too many); lean_ms / redo_ms = device durations of the two launches (render_ms of mt_scene_kernel_times
+ * is their sum).  Waits for the device.  (No reference counterpart.) */
+typedef struct mt_lean_info {
+  int32_t lean, handed_over;
+  uint32_t units, redo_units;
+  double lean_ms, redo_ms;
+} mt_lean_info;
+int mt_scene_lean_info(mt_scene *scene, mt_lean_info *out);
 
 /* OctTree::IntersectRay (octtree.cc:26-40) for a batch: rays = n x 6 doubles
  * (origin, direction).  Outputs (each nullable): tri = stream-order triangle

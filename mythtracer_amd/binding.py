@@ -21,7 +21,7 @@ HIP_SYMBOLS = [
     "mt_scene_destroy", "mt_scene_set_lights", "mt_render_chunk",
     "mt_render_chunk_device", "mt_render_tiles_device", "mt_blit_tiles_device",
     "mt_scene_read_stats", "mt_intersect_rays", "mt_scene_set_traversal_mode",
-    "mt_scene_kernel_times", "mt_scene_set_scheduling", "mt_scene_set_engine",
+    "mt_scene_kernel_times", "mt_scene_lean_info", "mt_scene_set_scheduling", "mt_scene_set_engine",
     "mt_scene_set_stats", "mt_set_default_engine", "mt_scene_set_tuning",
     "mt_render_frame_multi", "mt_scene_export_costs_device", "mt_scene_import_costs_device",
     "mt_order_tiles_device", "mt_dealt_tile_count", "mt_deal_tiles_device",
@@ -47,7 +47,7 @@ TUNE = {name: i for i, name in enumerate([
     "POOL_CELL_FACTOR", "QUAD_SHARE", "QUAD_SHARE_MOVING", "QUAD_KEEP", "QUAD_WORK", "QUAD_WORK_MOVING",
     "POOL_SCRATCH_MB", "HYBRID_POOL_SHARE", "HYBRID_QUAD_SHARE", "HYBRID_WORK1", "HYBRID_WORK2", "FORECAST_STEP",
     "HYBRID_STARTER_SHARE", "DEEP_LAYOUT", "MULTI_FORCE_PEER_COPY", "MULTI_BALANCE", "XCD_QUEUES",
-    "ORDER_GROUPS", "SM_CELL_SHARE", "SM_CELL_TIME", "SM_CELL_WORK", "HYBRID_CELL_FACTOR"])}
+    "ORDER_GROUPS", "SM_CELL_SHARE", "SM_CELL_TIME", "SM_CELL_WORK", "HYBRID_CELL_FACTOR", "LEAN_KERNEL"])}
 
 STAT_NAMES = ["rays_primary", "rays_secondary", "rays_shadow", "box_tests",
               "node_visits", "tri_tests", "mt_tests", "shaded_hits"]
@@ -96,6 +96,14 @@ class mt_adaptive_info(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class mt_lean_info(C.Structure):
+    _fields_ = [("lean", C.c_int32), ("handed_over", C.c_int32), ("units", C.c_uint32), ("redo_units", C.c_uint32),
+                ("lean_ms", C.c_double), ("redo_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class mt_scene_desc(C.Structure):
@@ -293,6 +301,7 @@ class HipAbi:
         L.mt_intersect_rays.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
         L.mt_scene_set_traversal_mode.argtypes = [vp, ci]
         L.mt_scene_kernel_times.argtypes = [vp, ci, vp, vp]
+        L.mt_scene_lean_info.argtypes = [vp, C.POINTER(mt_lean_info)]
         L.mt_scene_set_scheduling.argtypes = [vp, ci]
         L.mt_scene_set_engine.argtypes = [vp, ci]
         L.mt_scene_set_stats.argtypes = [vp, ci]
@@ -885,6 +894,13 @@ class HipAbi:
         if n < 0:
             self.check(n)
         return a[:n].copy(), b[:n].copy()
+
+    def lean_info(self, h):
+        """mt_scene_lean_info: what the scene's last launch was (dict: lean, handed_over, units, redo_units, lean_ms,
+        redo_ms).  Waits for the device."""
+        info = mt_lean_info()
+        self.check(self.lib.mt_scene_lean_info(h, C.byref(info)))
+        return info.as_dict()
 
     def intersect_rays(self, h, rays):
         rays = _f64(rays).reshape(-1, 6)

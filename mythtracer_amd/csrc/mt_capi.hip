@@ -131,8 +131,18 @@ struct Tuning {
     v[MT_TUNE_SM_CELL_WORK] = 3.0;
     v[MT_TUNE_ORDER_GROUPS] = (double)kOrdGroups;  // workgroups of the work-order kernels (mt_order.h)
     v[MT_TUNE_XCD_QUEUES] = 2.0;  // one work order per XCD over a 4 x 2 grid of regions of equal forecast cost (L2 hit rate 0.82 -> 0.92 room, 0.66 -> 0.82 loft)
+    v[MT_TUNE_LEAN_KERNEL] = 1.0;  // the lean frame kernel where decide_launch finds its conditions met (0 never, 2 whatever the primary rays)
   }
 };
+
+// The lean frame kernel's guard (order_forecast_kernel): when a lean launch abandoned more than this share of its
+// units, the scene's next kLeanHandoverFrames lean launches hand their whole order to the redo launch.  An abandoned
+// unit costs the passes it ran before the ray the walk cannot take came up -- half of the unit when such rays come
+// anywhere in it -- on top of its redo, which costs what the unit costs without a lean kernel: with a share f of the
+// units abandoned the frame pays 0.5 f and gains g (1 - f), g being what the lean kernel saves on a unit it finishes.
+// Break-even at f = g / (0.5 + g) = 0.07 for the g = 3.7 % measured on the room's panning frame (LABBOOK section D);
+// the guard stays on the safe side of it.
+constexpr float kLeanRedoShare = 0.04f;
 
 // process-wide default of mt_scene_set_engine for scenes created from now on (mt_set_default_engine)
 std::atomic<int> g_default_engine{0};
@@ -152,6 +162,8 @@ struct ForecastBank {
   Buf<unsigned short> d_item_cell;
   Buf<unsigned int> d_order_item;      // [4 n_items]
   Buf<signed char> d_order_sub;        // [4 n_items]
+  Buf<unsigned int> d_redo_item;       // the lean frame kernel's abandoned units, sized like the order (first lean launch)
+  Buf<signed char> d_redo_sub;
   // tile-list launches (mt_render_tile_list_device): the launch's own copy of the list, and tile -> slot (last_P
   // points at them)
   Buf<int32_t> d_tile_list;
@@ -196,7 +208,13 @@ struct mt_scene {
   void forget_histories() {  // other settings, other order: start from a first frame
     bank0.cost_signature = 0;
     if (bank1) bank1->cost_signature = 0;
+    lean_fresh = true;
   }
+  // The lean frame kernel (render_kernel<.., LEAN>): its device words (d_work + kLeanCtl) start afresh with the next
+  // lean launch; what the last launch was (mt_scene_lean_info); the event between the lean and the redo launch.
+  bool lean_fresh = true;
+  bool last_lean = false;
+  long long last_lean_slot = -1;  // ev_k row of the last lean launch
   bool use_history = true;
   Buf<uint8_t> d_rgb;
   Buf<uint8_t> d_samples;  // supersampled chunks: the sample frame on its way to resolve_kernel (mt_resolve.h)
@@ -217,9 +235,10 @@ struct mt_scene {
   int grid_blocks = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // per-launch kernel timing (mt_scene_kernel_times): [i][0] before the primary
-  // kernel, [1] between the two kernels, [2] after the render kernel
+  // kernel, [1] between the two kernels, [2] after the render kernel (a lean launch: after its redo launch; [3] between
+  // the two)
   static constexpr int kTimedLaunches = 64;
-  hipEvent_t ev_k[kTimedLaunches][3] = {};
+  hipEvent_t ev_k[kTimedLaunches][4] = {};
   unsigned long long launches_timed = 0, launches_read = 0;
   int n_cu = 0;
   bool stats_enabled = true;
@@ -338,6 +357,7 @@ struct LayoutKernels {
   void (*lightbuffer_update[2])(DevScene, LightUpdateArgs);
   void (*raytree_trace[2])(DevScene, RayTreeTraceArgs);
   void (*raytree_update[2])(DevScene, RayTreeUpdateArgs);
+  SceneKernel lean[2];  // render_kernel<.., LEAN>
 };
 template <int D>
 LayoutKernels layout_kernels() {
@@ -347,7 +367,8 @@ LayoutKernels layout_kernels() {
           {lightbuffer_kernel<false, D>, lightbuffer_kernel<true, D>},
           {lightbuffer_update_kernel<false, D>, lightbuffer_update_kernel<true, D>},
           {raytree_trace_kernel<false, D>, raytree_trace_kernel<true, D>},
-          {raytree_update_kernel<false, D>, raytree_update_kernel<true, D>}};
+          {raytree_update_kernel<false, D>, raytree_update_kernel<true, D>},
+          {render_kernel<false, D, true>, render_kernel<true, D, true>}};
 }
 const LayoutKernels &kernels_of(int deep) {
   static const LayoutKernels k[3] = {layout_kernels<0>(), layout_kernels<1>(), layout_kernels<2>()};
@@ -375,7 +396,7 @@ int configure_launch(mt_scene *s) {
       constexpr hipFuncAttribute kLdsAttr = hipFuncAttributeMaxDynamicSharedMemorySize;
       for (int d = 0; d < 3; d++) {
         const LayoutKernels &k = kernels_of(d);
-        for (const SceneKernel *f : {k.render, k.primary, k.pool, k.hybrid}) {
+        for (const SceneKernel *f : {k.render, k.primary, k.pool, k.hybrid, k.lean}) {
           for (int st = 0; st < 2; st++) HIP_TRY(hipFuncSetAttribute((const void *)f[st], kLdsAttr, (int)bytes));
         }
         HIP_TRY(hipFuncSetAttribute((const void *)k.probe, kLdsAttr, (int)bytes));
@@ -458,6 +479,7 @@ struct LaunchPlan {
   int reproject = 0, radius = 0;  // forecast_kernel: the camera moved since the costs were measured
   float blend = 0.0f;
   int old_irr = 0, new_irr = 0;   // zero-component pixels in the frame that measured the costs / in this one
+  bool lean = false;              // the frame kernel is render_kernel<.., LEAN>, with a redo launch of the full one behind it
 };
 
 int decide_launch(mt_scene *s, ForecastBank &B, const RenderParams &P, const mt_sensor *sensor, bool debug, const int32_t *d_list,
@@ -569,6 +591,18 @@ int decide_launch(mt_scene *s, ForecastBank &B, const RenderParams &P, const mt_
     const float cap = (float)s->tune.v[MT_TUNE_BLEND];
     L.blend = std::min(cap, (float)B.forecasts_in_a_row / (float)(B.forecasts_in_a_row + 1));
   }
+  // ---- which frame kernel?  The lean one (the hit-set walk alone; units it cannot finish are redone by the full kernel
+  // behind it) where nothing but the walk is expected to run: a state-machine launch with a cost history, traversal mode
+  // 0, a scene within the walk's limits (trace_wave's own conditions), no debug facility -- and no pixel whose primary
+  // ray has a zero direction component: those units are the frame's longest (a pixel column on the golden camera), and
+  // started only behind the lean launch they would double the frame.  MT_TUNE_LEAN_KERNEL = 2 waives the last condition.
+  const int lean_knob = (int)s->tune.v[MT_TUNE_LEAN_KERNEL];
+  const int hs_depth = s->deep >= 2 ? kHsMaxDepthDeep : kHsMaxDepth;
+  L.lean = lean_knob != 0 && L.engine == 1 && (s->engine == 0 || s->engine == 1) && &B == &s->bank0 &&
+           s->dev.force_mode == 0 && s->dev.scene_regular != 0 && s->dev.tree_depth <= hs_depth &&
+           s->dev.n_tris < (1 << 28) && s->dev.bmax[0] <= 0x1p200 && s->dev.bmax[1] <= 0x1p200 && s->dev.bmax[2] <= 0x1p200 &&
+           !s->hb_host && s->dbg_item_cycles.empty() && s->dbg_print_units == 0 && s->dev.prof == nullptr &&
+           (lean_knob == 2 || !L.new_irr);
   return MT_OK;
 }
 
@@ -590,6 +624,13 @@ int size_buffers(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const int32_
   P.order_item = B.d_order_item;
   P.order_sub = B.d_order_sub;
   P.n_work = s->d_work + 7;
+  if (L.lean) {
+    MT_TRY(B.d_redo_item.ensure(n * 64));
+    MT_TRY(B.d_redo_sub.ensure(n * 16));
+    P.redo_item = B.d_redo_item;
+    P.redo_sub = B.d_redo_sub;
+    P.lean_ctl = s->d_work + kLeanCtl;
+  }
   // the combined cost map of all ranks, if one was imported after the previous launch (else nullptr: own costs only)
   P.cost_map = B.cost_map_for_launch == B.launches ? s->d_cost_map.p : nullptr;
   P.cost_map_w = s->cost_map_w;
@@ -707,6 +748,9 @@ void launch_work_order(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const 
     oa.new_irr = L.reproject ? 0 : L.new_irr;
     oa.cell_time = (float)tv[MT_TUNE_SM_CELL_TIME];
     oa.queue_mode = (int)tv[MT_TUNE_XCD_QUEUES];
+    oa.lean = L.lean ? (s->lean_fresh ? 2 : 1) : 0;
+    oa.lean_share = kLeanRedoShare;
+    if (L.lean) s->lean_fresh = false;
     launch_order<0>(P, fa, oa, groups, stream);
   }
 }
@@ -729,7 +773,7 @@ int launch_kernels(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const Rend
     s->dev_uploaded_valid = true;
   }
   hipEvent_t *ek = s->ev_k[s->launches_timed % mt_scene::kTimedLaunches];
-  for (int i = 0; i < 3; i++) {
+  for (int i = 0; i < (L.lean ? 4 : 3); i++) {
     if (!ek[i]) HIP_TRY(hipEventCreate(&ek[i]));
   }
   HIP_TRY(hipEventRecord(ek[0], stream));
@@ -746,8 +790,24 @@ int launch_kernels(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const Rend
   else hipLaunchKernelGGL(k.primary[stats], grid, block, s->lds_bytes, stream, s->dev, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ek[1], stream));
-  const SceneKernel *frame = L.engine == 2 ? k.pool : (L.engine == 3 ? k.hybrid : k.render);
+  const SceneKernel *frame = L.engine == 2 ? k.pool : (L.engine == 3 ? k.hybrid : (L.lean ? k.lean : k.render));
   hipLaunchKernelGGL(frame[stats], grid, block, s->lds_bytes, stream, s->dev, P);
+  s->last_lean = L.lean;
+  if (L.lean) {
+    // The redo launch: the full kernel over the units the lean one abandoned -- one order for the chip, its count and
+    // its unit counter among the lean words (zeroed by order_forecast_kernel).  Mostly empty: every wave fetches once.
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ek[3], stream));
+    s->last_lean_slot = (long long)(s->launches_timed % mt_scene::kTimedLaunches);
+    RenderParams R = P;
+    R.order_item = P.redo_item;
+    R.order_sub = P.redo_sub;
+    R.n_work = P.lean_ctl + kLeanRedoCount;
+    R.work_counter = P.lean_ctl;  // (the frame kernel counts through work_counter[1] = kLeanRedoCounter)
+    R.queues = nullptr;
+    R.from_primary = 0;
+    hipLaunchKernelGGL(k.render[stats], grid, block, s->lds_bytes, stream, s->dev, R);
+  }
   HIP_TRY(hipEventRecord(ek[2], stream));
   HIP_TRY(hipGetLastError());
   return MT_OK;
@@ -1482,7 +1542,8 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   s->dev.lights = nullptr;
   MT_TRY(s->d_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long)));
-  MT_TRY(s->d_work.ensure(64));
+  MT_TRY(s->d_work.ensure((kLeanCtl + 8) * sizeof(unsigned)));  // 16 words of counters, 8 of the lean frame kernel's
+  HIP_TRY(hipMemset(s->d_work, 0, (kLeanCtl + 8) * sizeof(unsigned)));
   MT_TRY(s->d_queues.ensure(kQueueWords * sizeof(unsigned)));
   MT_TRY(s->d_order_ctl.ensure(kOrdWords * sizeof(unsigned)));
   HIP_TRY(hipMemset(s->d_order_ctl, 0, kOrdWords * sizeof(unsigned)));
@@ -1648,6 +1709,9 @@ int mt_scene_set_tuning(mt_scene *s, int knob, double value) {
     case MT_TUNE_XCD_QUEUES:
       if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(MT_ERR_ARG, "XCD queues: 0 (off), 1 (stripes) or 2 (grid)");
       break;
+    case MT_TUNE_LEAN_KERNEL:
+      if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(MT_ERR_ARG, "lean frame kernel: 0 (never), 1 (automatic) or 2 (forced)");
+      break;
     default: break;  // switches: any finite value (0 / non-zero)
   }
   s->tune.v[knob] = value;
@@ -1750,6 +1814,27 @@ int mt_scene_kernel_times(mt_scene *s, int max_n, double *primary_ms, double *re
   }
   s->launches_read = s->launches_timed;
   return n;
+}
+
+int mt_scene_lean_info(mt_scene *s, mt_lean_info *out) {
+  if (!s || !out) return fail(MT_ERR_ARG, "NULL argument");
+  memset(out, 0, sizeof *out);
+  HIP_TRY(hipSetDevice(s->device));
+  out->lean = s->last_lean ? 1 : 0;
+  if (!s->last_lean || s->last_lean_slot < 0) return MT_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned w[8];
+  HIP_TRY(hipMemcpy(w, s->d_work + kLeanCtl, sizeof w, hipMemcpyDeviceToHost));
+  out->redo_units = w[kLeanRedoCount];
+  out->units = w[kLeanUnits];
+  out->handed_over = w[kLeanHandover] != 0u ? 1 : 0;
+  hipEvent_t *ek = s->ev_k[s->last_lean_slot];
+  float a = 0, b = 0;
+  HIP_TRY(hipEventElapsedTime(&a, ek[1], ek[3]));
+  HIP_TRY(hipEventElapsedTime(&b, ek[3], ek[2]));
+  out->lean_ms = a;
+  out->redo_ms = b;
+  return MT_OK;
 }
 
 int mt_render_chunk_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h,

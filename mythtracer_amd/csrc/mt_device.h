@@ -181,6 +181,9 @@ enum {
 // instead of hanging the GPU.
 enum { DEV_OK = 0, DEV_ERR_TRAVERSAL_BOUND = 1, DEV_ERR_UNWIND_BOUND = 2, DEV_ERR_PIXEL_BOUND = 3,
        DEV_ERR_POOL = 4 };
+// Not an error and never written to ST_STATUS: what the LEAN traversal (mt_trace.h: the hit-set walk and nothing else)
+// answers for a wave it cannot take; the lean frame kernel then leaves the unit to the full kernel (redo list).
+enum { DEV_NEEDS_FULL = 64 };
 
 // Tiling of one launch (see mt_render_tiles_device in the C ABI).
 struct RenderParams {
@@ -240,7 +243,16 @@ struct RenderParams {
   unsigned int *order_ctl;    // the order kernels' forecast sums, histograms, region grids (kOrdWords; never reset by the host)
   unsigned int *item_unit;    // [n_items] what the block becomes in this launch, packed (order_count_kernel -> order_scatter_kernel)
   unsigned int *order_whist;  // [workgroups][kOrdKeysMax] every workgroup's histogram over the sort keys
+  // The lean frame kernel (render_kernel<.., LEAN>): units it abandons (DEV_NEEDS_FULL) are appended here, redo_item /
+  // redo_sub in the layout of order_item / order_sub, and rendered by the full kernel in a launch behind it.
+  // lean_ctl = work_counter + kLeanCtl (words kLean*); nullptr in launches without a lean kernel.
+  unsigned int *redo_item;
+  signed char *redo_sub;
+  unsigned int *lean_ctl;
 };
+// lean_ctl words: the redo launch's unit counter sits at [1] because the frame kernel counts through work_counter[1]
+enum { kLeanCtl = 16, kLeanRedoCounter = 1, kLeanRedoCount = 2, kLeanHandover = 3, kLeanPrevRedo = 4, kLeanUnits = 6 };
+constexpr unsigned kLeanHandoverFrames = 15u;  // lean launches a scene's orders go to the redo launch whole before the lean kernel is tried again
 constexpr int kQueues = 8, kQueueStride = 32, kQueueStart = kQueues * kQueueStride;  // (a counter per 128-byte line)
 constexpr int kGridW = 64, kGridH = 32;            // the region grid: forecast cost per cell (order_kernel's area)
 constexpr int kQueueWords = kQueueStart + 32;

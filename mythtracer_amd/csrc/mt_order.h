@@ -57,6 +57,11 @@ struct OrderArgs {
   unsigned max_starters;
   unsigned char *form_out;
   SchedParams sp;          // ray pool
+  // state machine, launches rendered by the lean frame kernel (0: not one; 2: the scene's histories were forgotten,
+  // the lean words start afresh): its redo words are zeroed with the other counters, and when the previous lean launch
+  // abandoned more than lean_share of its units the coming ones hand their whole order to the redo launch
+  int lean;
+  float lean_share;
 };
 
 // a / b and a % b for 0 <= a < 2^22, b >= 1 through the divisor's reciprocal (eight instructions instead of the thirty
@@ -319,6 +324,16 @@ __global__ __launch_bounds__(kOrdThreads) void order_forecast_kernel(RenderParam
   for (unsigned c = (unsigned)wg * kOrdThreads + (unsigned)tid; c < (unsigned)kOrdAreaWords; c += G * kOrdThreads) area_next[c] = 0u;
   if (wg == 0) {
     if (tid < 16) P.work_counter[tid] = 0u;  // (the frame kernel's counters, the class counts, n_work)
+    if (KIND == 0 && O.lean != 0 && tid == 16) {  // the lean frame kernel's words (mt_device.h, kLean*)
+      unsigned *lc = P.work_counter + kLeanCtl;
+      const unsigned redo = O.lean == 2 ? 0u : lc[kLeanRedoCount], units = lc[kLeanUnits];
+      const unsigned left = O.lean == 2 ? 0u : lc[kLeanHandover];
+      // (after a run of handed-over launches one launch is the lean kernel's again: the next decision needs its count)
+      lc[kLeanHandover] = left > 0u ? left - 1u : ((float)redo > O.lean_share * (float)units ? kLeanHandoverFrames : 0u);
+      lc[kLeanPrevRedo] = redo;
+      lc[kLeanRedoCount] = 0u;
+      lc[kLeanRedoCounter] = 0u;
+    }
     if (queues) {
       for (int c = tid; c < kQueueWords; c += kOrdThreads) P.queues[c] = 0u;
     }
@@ -484,6 +499,7 @@ __global__ __launch_bounds__(kOrdThreads) void order_scatter_kernel(RenderParams
     if (tid == 0) {
       if (queues) P.queues[kQueueStart + kQueues] = all;
       P.n_work[0] = all;
+      if (KIND == 0 && O.lean != 0) P.work_counter[kLeanCtl + kLeanUnits] = all;
     }
   }
   __syncthreads();

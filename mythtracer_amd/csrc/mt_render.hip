@@ -68,6 +68,7 @@ struct ItemGeom {
   bool inside;       // lane has a pixel
   size_t px_index;   // position in the output / hit buffers
 };
+template <bool CELLS = true>  // CELLS = false: sub < 4 by construction (the lean frame kernel renders no cells)
 __device__ __forceinline__ ItemGeom item_geometry(const RenderParams &P, unsigned item, int sub, int lane) {
   const int items_per_tile = P.blocks_x * P.blocks_y;
   const int j = (int)(item / (unsigned)items_per_tile);
@@ -82,7 +83,7 @@ __device__ __forceinline__ ItemGeom item_geometry(const RenderParams &P, unsigne
   if (sub < 0) {
     ox = lane & 7;
     oy = lane >> 3;
-  } else if (sub < 4) {
+  } else if (!CELLS || sub < 4) {
     const int q = lane >> 2;
     ox = (sub & 1) * 4 + (q & 3);
     oy = (sub >> 1) * 4 + (q >> 2);
@@ -378,7 +379,13 @@ namespace mt {
 // pixel, i.e. with the pixel's shadow loops running side by side.)
 // sm_engine is the body shared by render_kernel and hybrid_kernel (below); `carry` and the return value as for
 // pool_engine (mt_pool.h).
-template <bool STATS, bool MIXED, int DEEP>
+// LEAN (launches with a cost history only, never MIXED): the traversal is the hit-set walk alone (trace_wave<.., LEAN>);
+// no primary-kernel hand-over, no 2x2 cells, no heartbeat or per-unit cycle dump.  A unit whose wave meets a ray the
+// walk cannot take (DEV_NEEDS_FULL) is ABANDONED: no cost, no work counters, its (item, sub) appended to the redo list
+// that the full kernel renders in a launch of its own behind this one.  Pixels it had stored stay -- the redo writes
+// the same bytes.  Cells in the order, and every unit while lean_ctl[kLeanHandover] is set (the previous lean
+// launches abandoned too much: order_forecast_kernel), go to the redo list unopened.
+template <bool STATS, bool MIXED, int DEEP, bool LEAN = false>
 __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderParams &P, unsigned carry) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -404,8 +411,12 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
   const V3 s_ds = v3_load(P.sensor.delta_scanline);
   const V3 s_dp = v3_load(P.sensor.delta_pixel);
   unsigned result = kCarryDone;
-  const bool from_primary = P.from_primary != 0;
-  const unsigned n2 = P.class_count[2], n1 = P.class_count[1], n0 = P.class_count[0];
+  static_assert(!(LEAN && MIXED), "the hybrid kernel has no lean form");
+  const bool from_primary = !LEAN && P.from_primary != 0;
+  const bool heartbeat = !LEAN && S.hb != nullptr;
+  const bool handover = LEAN && P.lean_ctl[kLeanHandover] != 0u;
+  unsigned n2 = 0u, n1 = 0u, n0 = 0u;
+  if (!LEAN) { n2 = P.class_count[2]; n1 = P.class_count[1]; n0 = P.class_count[0]; }
   const unsigned n_work = from_primary ? 4u * n2 + n1 + n0 : *P.n_work;
   // (hybrid launches: the state machine's units lie behind the pool's n_work[1] and have a counter of their own)
   const unsigned w_base = MIXED ? P.n_work[1] : 0u;
@@ -420,7 +431,7 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     if (xcd_queues) w = qf.next(P, lane, n_work);
     else if (carry == kCarryNone) w = w_base + fetch_work(P.work_counter + (MIXED ? 2 : 1), lane);
     carry = kCarryNone;
-    if (S.hb) {
+    if (heartbeat) {
       const unsigned long long ex = __builtin_amdgcn_read_exec();
       if (lane == 0) { S.hb[wave_id * 4 + 0] = 1 | ((unsigned long long)w << 8); S.hb[wave_id * 4 + 1] = ex; }
     }
@@ -455,11 +466,18 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     sub = __builtin_amdgcn_readfirstlane(sub);
     item = (unsigned)__builtin_amdgcn_readfirstlane((int)item);
 
+    bool abandon = LEAN && (handover || sub >= 4);
+    if (LEAN && abandon) {  // (wave-uniform)
+      const unsigned at = fetch_work(P.lean_ctl + kLeanRedoCount, lane);
+      if (lane == 0) { P.redo_item[at] = item; P.redo_sub[at] = (signed char)sub; }
+      continue;
+    }
+
     const unsigned long long item_t0 = __builtin_amdgcn_s_memtime();
 #ifdef MT_DIAG
     unsigned long long diag_trace_ticks = 0;
 #endif
-    const ItemGeom g = item_geometry(P, item, sub, lane);
+    const ItemGeom g = item_geometry<!LEAN>(P, item, sub, lane);
     bool alive = g.inside;
     const size_t px_index = g.px_index;
 
@@ -503,7 +521,7 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     while (__ballot(alive) != 0ull) {
       int prim = -1;
       double t = 0.0;
-      if (S.hb) {
+      if (heartbeat) {
         const unsigned long long am = __ballot(alive);
         const unsigned long long ex = __builtin_amdgcn_read_exec();
         if (lane == 0) {
@@ -521,7 +539,7 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
 #ifdef MT_DIAG
         const unsigned long long diag_tt0 = __builtin_amdgcn_s_memtime();
 #endif
-        const TraceOut to = trace_wave<STATS, DEEP>(S.self, stk.base, lane, tracing, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z);
+        const TraceOut to = trace_wave<STATS, DEEP, LEAN>(S.self, stk.base, lane, tracing, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z);
 #ifdef MT_DIAG
         asm volatile("" :: "v"(to.prim));
         diag_trace_ticks += __builtin_amdgcn_s_memtime() - diag_tt0;
@@ -530,9 +548,12 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
         prim = to.prim;
         t = to.t;
         trc = to.status;
-
+        if (LEAN && __builtin_amdgcn_readfirstlane(trc) == DEV_NEEDS_FULL) {  // not for the walk: the full kernel renders the unit
+          abandon = true;
+          break;
+        }
       }
-      if (S.hb) {
+      if (heartbeat) {
         const unsigned long long ex = __builtin_amdgcn_read_exec();
         if (lane == 0) { S.hb[wave_id * 4 + 0] = 3 | ((unsigned long long)passes << 8); S.hb[wave_id * 4 + 3] = ex; }
       }
@@ -839,13 +860,19 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
       }
     }
 
-    if (S.hb && lane == 0) S.hb[wave_id * 4 + 0] = 4;
+    if (LEAN && abandon) {
+      st.clear();
+      const unsigned at = fetch_work(P.lean_ctl + kLeanRedoCount, lane);
+      if (lane == 0) { P.redo_item[at] = item; P.redo_sub[at] = (signed char)sub; }
+      continue;
+    }
+    if (heartbeat && lane == 0) S.hb[wave_id * 4 + 0] = 4;
     {
       const unsigned long long ticks = __builtin_amdgcn_s_memtime() - item_t0;
       if (lane == 0) {
         const unsigned long long c = ticks >> 6;  // quarters of a block add up
         atomicAdd(P.item_cost + item, c > 0x0fffffffull ? 0x0fffffffu : (unsigned)c);
-        if (P.item_cycles) {
+        if (!LEAN && P.item_cycles) {
           P.item_cycles[(size_t)w * 2] = ticks;
           P.item_cycles[(size_t)(P.n_items * 48u + w) * 2] = item_t0;  // start stamp (scripts/unit_timeline.py)
           P.item_cycles[(size_t)(P.n_items * 48u + w) * 2 + 1] = (unsigned long long)wave_id;
@@ -859,14 +886,14 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     }
     flush_item_stats<STATS>(st, P.counters, lane);
   }
-  if (S.hb && lane == 0) S.hb[wave_id * 4 + 0] = 5;
+  if (heartbeat && lane == 0) S.hb[wave_id * 4 + 0] = 5;
   __builtin_amdgcn_s_setprio(0);
   return result;
 }
 
-template <bool STATS, int DEEP>
+template <bool STATS, int DEEP, bool LEAN = false>
 __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void render_kernel(DevScene S, RenderParams P) {
-  (void)sm_engine<STATS, false, DEEP>(S, P, kCarryNone);
+  (void)sm_engine<STATS, false, DEEP, LEAN>(S, P, kCarryNone);
 }
 
 // The HYBRID frame kernel (engine 3): the work order starts with the longest blocks, cut into pieces for the ray
@@ -967,6 +994,8 @@ __global__ void blit_tiles_kernel(int image_w, int image_h, int tile_w, int tile
 #define MT_INSTANTIATE(DEEP_)                                                                    \
   template __global__ void render_kernel<true, DEEP_>(DevScene, RenderParams);                   \
   template __global__ void render_kernel<false, DEEP_>(DevScene, RenderParams);                  \
+  template __global__ void render_kernel<true, DEEP_, true>(DevScene, RenderParams);             \
+  template __global__ void render_kernel<false, DEEP_, true>(DevScene, RenderParams);            \
   template __global__ void primary_kernel<true, DEEP_>(DevScene, RenderParams);                  \
   template __global__ void primary_kernel<false, DEEP_>(DevScene, RenderParams);                 \
   template __global__ void pool_kernel<true, DEEP_>(DevScene, RenderParams);                     \

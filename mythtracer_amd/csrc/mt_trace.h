@@ -1825,7 +1825,11 @@ struct TraceOut {
 #else
 #define MT_TRACE_ATTR __forceinline__
 #endif
-template <bool STATS, int DEEP = 0>
+// LEAN: the hit-set walk and nothing else -- no ordered descent with its noinline callees, no run-time traversal
+// mode (force_mode is 0 by construction), no second round for a wave that mixes regular and irregular rays.  The
+// walk's preconditions are checked once per call; a wave that fails them gets the wave-uniform status DEV_NEEDS_FULL
+// and no result.  For a wave that passes, the same instructions run on the same data as in the full instantiation.
+template <bool STATS, int DEEP = 0, bool LEAN = false>
 __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned stack_base, int lane,
                                                          bool want_all, double ox, double oy, double oz,
                                                          double dx, double dy, double dz) {
@@ -1850,7 +1854,7 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
   S.n_tris = G->n_tris;
   S.n_nodes = G->n_nodes;
   S.tree_depth = G->tree_depth;
-  S.force_mode = G->force_mode;
+  S.force_mode = LEAN ? 0 : G->force_mode;
   S.scene_regular = G->scene_regular;
   S.pack_shift = G->pack_shift;
   S.hb = nullptr;
@@ -1913,7 +1917,7 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
   // one ray with a zero direction component (a pixel row level with the
   // camera, say) must not push the other 63 onto the exact path, which has
   // neither the fp32 filter nor the block / subtree boxes.
-  const int rounds = (S.scene_regular != 0 && S.force_mode != 1 && __ballot(want_all && !fin) != 0ull &&
+  const int rounds = (!LEAN && S.scene_regular != 0 && S.force_mode != 1 && __ballot(want_all && !fin) != 0ull &&
                       __ballot(want_all && fin) != 0ull) ? 2 : 1;
   int status = DEV_OK;
   for (int round = 0; round < rounds; round++) {
@@ -1963,7 +1967,9 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
     cur_pb = q[1];
     cur_pc = q[2];
   };
-  if (cur >= 0) load_record(cur);
+  if constexpr (!LEAN) {
+    if (cur >= 0) load_record(cur);
+  }
 
   // The tail of PrimitiveIntersectRay for one node (octtree.cc:199-256): order
   // the children the ray enters, then descend into the next one or hand the
@@ -2065,8 +2071,10 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
   const bool tame = __builtin_fabs(dx) <= 0x1p100 && __builtin_fabs(dy) <= 0x1p100 && __builtin_fabs(dz) <= 0x1p100 &&
                     __builtin_fabs(ox) <= 0x1p200 && __builtin_fabs(oy) <= 0x1p200 && __builtin_fabs(oz) <= 0x1p200;
   bool hs_done = false;
-  if (cull && S.force_mode == 0 && S.tree_depth <= (WIDE ? kHsMaxDepthDeep : kHsMaxDepth) && S.n_tris < (1 << 28) &&
-      S.bmax[0] <= 0x1p200 && S.bmax[1] <= 0x1p200 && S.bmax[2] <= 0x1p200 && __ballot(want && !tame) == 0ull) {
+  const bool hs_ok = cull && S.force_mode == 0 && S.tree_depth <= (WIDE ? kHsMaxDepthDeep : kHsMaxDepth) && S.n_tris < (1 << 28) &&
+      S.bmax[0] <= 0x1p200 && S.bmax[1] <= 0x1p200 && S.bmax[2] <= 0x1p200 && __ballot(want && !tame) == 0ull;
+  if (LEAN && !hs_ok) status = DEV_NEEDS_FULL;  // (wave-uniform: the caller hands the unit to the full kernel)
+  if (hs_ok) {
     hs_done = true;
     const int L = S.tree_depth > 1 ? S.tree_depth - 1 : 0;  // levels that can hold a node with children
     const int Lf = (DEEP && L > kHsLdsLevels) ? kHsLdsLevels : L;  // ... whose frames are in LDS (DEEP: the others in deep_area)
@@ -2628,6 +2636,7 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
     }
     cur = -1;
   }
+  if constexpr (!LEAN)
   if (!hs_done)
   // Main loop of the ordered descent.  (A) every lane works through the small nodes on its path by itself.
   // (B) When all lanes wait at big nodes, the wave takes the LOWEST-NUMBERED one (breadth-first numbering: the top
