@@ -663,6 +663,67 @@ int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, 
  * forecasts are left alone. */
 int mt_raytree_update_materials(mt_raytree *tree, mt_stats *stats);
 
+/* Edited materials that change the tree's SHAPE: a stale ray tree brought to the scene's CURRENT materials whatever the
+ * edit does to the child conditions -- a matte surface made reflective, a mirror switched off, a pane made opaque, a
+ * reflectance lowered until a deep bounce falls under coef > 0.01.  Where mt_raytree_update_materials refuses, this call
+ * keeps the rays that survive, drops the dead subtrees, traces only the new ones and knits the layers back into the
+ * order mt_raytree_create produces (by parent index, the reflected child before the refracted one).  (No reference
+ * counterpart.)  mt_raytree_update_materials itself is unchanged and keeps refusing such an edit.
+ * A ray of the new tree is KEPT when its path exists in the old tree: every ray of layer 0; a child whose parent is kept
+ * and whose OLD parent had a child in the same slot (reflected / refracted).  Every other ray of the new tree is TRACED.
+ * A kept ray takes ray, in_object, point, normal, material and its light planes from the old tree, its coef and child
+ * conditions from the new materials, its albedo from the old tree or -- where its material's ambient changed -- the new
+ * ambient.  A traced ray is spawned from its parent's stored hit and traced by the kernel mt_raytree_create uses, in a
+ * dense list of the layer's traced rays (a work item is 64 consecutive ones).
+ * Steps and checks, in this order; the first four come before any device call.
+ *   (1) tree NULL: MT_ERR_ARG.
+ *   (2) equal generations: MT_OK, no device call; info and stats all zero except n_layers_before = n_layers_after.
+ *   (3) ambient or tex of a material that has a texture before or after the edit: MT_ERR_UNSUPPORTED with
+ *       mt_raytree_update_materials's message (kept rays hold neither the texel nor the primitive).
+ *   (4) a reflectance or transparency changed, or the edit is one a shadow ray may see (mt_raytree_update_materials's
+ *       rule), the tree has lights, and the scene's light count is not the tree's: MT_ERR_ARG with
+ *       mt_raytree_update_materials's message.  Stricter than that call: traced rays get their light planes from the
+ *       scene's current lights.
+ *   (5) mt_raytree_update_materials's check pass, where a reflectance or transparency changed.  With no mismatch the
+ *       call continues exactly as mt_raytree_update_materials does (commit, light re-trace where a shadow ray may see
+ *       the edit): regrown = 0, kept = the rays per layer, traced = dropped = 0.
+ *   (6) otherwise the tree is regrown (a tree of ZERO lights under a scene that now has lights is MT_ERR_ARG here, with
+ *       (4)'s message and the tree untouched: the tracing kernel would run the scene's lights): regrown = 1; and where a shadow ray may see the edit, the planes of ALL lights
+ *       are then traced again over the whole new tree (mt_raytree_update_lights's kernel, one launch), the traced
+ *       rays' a second time.
+ * CONTRACT: after MT_OK the tree is bit-identical to mt_raytree_create[_rays] under the new materials and the scene's
+ * current lights, for the same sensor / ray list, chunk and max_depth: every plane of every layer (doubles with
+ * NaN = NaN, bytes and indices exactly, `pixel` in layer 0), and n_layers, n_rays and bytes of mt_raytree_info.  The
+ * tree is fresh: mt_raytree_shade on it is mt_render_chunk(..., max_depth, ...) under the new materials byte for byte,
+ * and mt_raytree_update_lights works on it.  trace_ms[k] becomes the device time of this call's tracing launch for
+ * layer k, 0 where no ray of that layer was traced.
+ * Light POSITIONS cannot be checked, as everywhere in this family.  If lights moved between the tree's last valid state
+ * and the call, kept rays hold the old positions' planes and traced rays the new ones; mt_raytree_update_lights over
+ * the moved indices after the regrow makes the tree the fresh tree under the new lights.
+ * Failure: the new layers >= 1 are built ASIDE, and so are layer 0's child indices; its albedo waits.  The old tree's
+ * planes are written only after the last step that can fail for size -- an allocation that does not fit is
+ * MT_ERR_NOMEM, a layer of 2^31 rays or more MT_ERR_UNSUPPORTED with mt_raytree_create's message --, and after such a
+ * failure the tree is bit-identical to what it was and still stale.  A tripped loop bound in a tracing launch is
+ * MT_ERR_INTERNAL with the tree as it was; in the light re-trace it is MT_ERR_INTERNAL and the tree stays stale, as for
+ * mt_raytree_update_materials.
+ * info (nullable): kept and traced per layer of the NEW tree (kept + traced = the new n_rays), dropped per layer of the
+ * OLD tree (its rays with no place in the new one).  stats (nullable; the counters are switched on for the call):
+ * rays_primary = 0, rays_secondary = the sum of traced, shaded_hits = the hits among the traced rays, rays_shadow = the
+ * shadow-loop iterations of the traced rays plus, where it ran, those of the all-lights re-trace; kernel_ms = from the
+ * first to the last kernel by the tree's events, read-backs included; total_ms = wall time.
+ * Synchronous; there is no _device form (the layer sizes need a read-back, as in mt_raytree_create).  The tree keeps
+ * the scratch it needed (an index per ray of the two largest new layers, layer 0's child indices, the dense list) for
+ * the next call; mt_raytree_info's bytes does not count it.  One call in flight per tree and per scene; cost history,
+ * engine choice, forecasts and mt_scene_kernel_times are left alone.  (mt::raytree_regrow_*_kernel in mt_raytree.h.) */
+typedef struct mt_raytree_regrow_info {
+  int32_t regrown;                       /* 0: the shape survived, the call did what mt_raytree_update_materials does */
+  int32_t n_layers_before, n_layers_after;
+  int64_t kept[MT_MAX_RECURSION + 1];    /* per layer of the NEW tree: rays taken over from the old tree */
+  int64_t traced[MT_MAX_RECURSION + 1];  /* ... rays newly spawned and traced; kept + traced = new n_rays */
+  int64_t dropped[MT_MAX_RECURSION + 1]; /* per layer of the OLD tree: rays with no place in the new one */
+} mt_raytree_regrow_info;
+int mt_raytree_regrow_materials(mt_raytree *tree, mt_raytree_regrow_info *info, mt_stats *stats);
+
 /* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
  * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour
  * of.  Everything after layer 0 of a ray tree already runs over a ray list and never looks at a sensor or an image, so

@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "mt_raytree_create_rays", "mt_raytree_create_rays_device", "mt_raytree_shade_colors",
     "mt_raytree_shade_colors_device", "mt_trace_rays",
     "mt_scene_set_materials", "mt_scene_get_materials", "mt_raytree_update_materials",
+    "mt_raytree_regrow_materials",
 ]
 MT_MAX_RECURSION = 16
 
@@ -96,6 +97,19 @@ class mt_adaptive_info(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class mt_raytree_regrow_info(C.Structure):
+    _fields_ = [("regrown", C.c_int32), ("n_layers_before", C.c_int32), ("n_layers_after", C.c_int32),
+                ("kept", C.c_int64 * (MT_MAX_RECURSION + 1)), ("traced", C.c_int64 * (MT_MAX_RECURSION + 1)), ("dropped", C.c_int64 * (MT_MAX_RECURSION + 1))]
+
+    def as_dict(self):
+        """kept / traced per layer of the new tree, dropped per layer of the old one."""
+        return dict(regrown=int(self.regrown), n_layers_before=int(self.n_layers_before),
+                    n_layers_after=int(self.n_layers_after),
+                    kept=[int(v) for v in self.kept][:self.n_layers_after],
+                    traced=[int(v) for v in self.traced][:self.n_layers_after],
+                    dropped=[int(v) for v in self.dropped][:self.n_layers_before])
 
 
 class mt_lean_info(C.Structure):
@@ -293,6 +307,7 @@ class HipAbi:
         L.mt_scene_set_materials.argtypes = [vp, vp, ci]
         L.mt_scene_get_materials.argtypes = [vp, vp, ci]
         L.mt_raytree_update_materials.argtypes = [vp, vp]
+        L.mt_raytree_regrow_materials.argtypes = [vp, vp, vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_chunk_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_tiles_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
@@ -765,6 +780,18 @@ class HipAbi:
         self.check(self.lib.mt_raytree_update_materials(tree, C.addressof(st)))
         return st.as_dict()
 
+    def raytree_regrow(self, tree) -> dict:
+        """mt_raytree_regrow_materials after set_materials: `tree` brought to the scene's current materials whatever
+        the edit does to its shape -- surviving rays kept, dead subtrees dropped, new rays traced.  Returns
+        mt_raytree_regrow_info's fields (regrown, n_layers_before / _after, kept, traced, dropped per layer) and the
+        stats, in one dict."""
+        st = mt_stats()
+        info = mt_raytree_regrow_info()
+        self.check(self.lib.mt_raytree_regrow_materials(tree, C.addressof(info), C.addressof(st)))
+        out = info.as_dict()
+        out.update(st.as_dict())
+        return out
+
     def raytree_update_lights_device(self, tree, light_indices, stream=None):
         """mt_raytree_update_lights_device: `light_indices` a host list; asynchronous on `stream`."""
         idx = _i32(light_indices).reshape(-1)
@@ -991,6 +1018,7 @@ def host_lib():
     L.mth_raytree_update.argtypes = [vp, vp, vp, ci, vp, vp]
     L.mth_update_materials.argtypes = [vp, cs, vp]
     L.mth_raytree_update_materials.argtypes = [vp, vp, vp, vp]
+    L.mth_raytree_regrow.argtypes = [vp, vp, vp, vp]
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1090,6 +1118,18 @@ class RayTree:
         ms = np.zeros(2)
         if not self.mt.L.mth_raytree_update_materials(self.mt.h, self.h, _ptr(st), _ptr(ms)):
             raise RuntimeError("UpdateRayTreeMaterials failed: " + self.mt.last_error())
+        return dict(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+
+    def regrow(self) -> dict:
+        """MythTracer::RegrowRayTree after MythTracer.update_materials: like update_materials, but an edit that changes
+        the tree's shape is followed -- surviving rays kept, dead subtrees dropped, new rays traced -- instead of
+        refused; `.info` follows.  Returns dict(counters, kernel_ms, total_ms); counters["rays_secondary"] is the
+        number of rays traced."""
+        self._tree()
+        st = np.zeros(8, dtype=np.uint64)
+        ms = np.zeros(2)
+        if not self.mt.L.mth_raytree_regrow(self.mt.h, self.h, _ptr(st), _ptr(ms)):
+            raise RuntimeError("RegrowRayTree failed: " + self.mt.last_error())
         return dict(counters=dict(zip(STAT_NAMES, (int(x) for x in st))), kernel_ms=float(ms[0]), total_ms=float(ms[1]))
 
     def close(self):

@@ -2753,6 +2753,11 @@ struct mt_raytree {
   unsigned long long mtl_generation = 0;
   unsigned long long *d_mismatch = nullptr;
   uint8_t *d_albedo_changed = nullptr;
+  // mt_raytree_regrow_materials (first use, grown when a call needs more): `src` of the new layers k and k + 1 in turn,
+  // layer 0's child indices and spawn bytes while the new tree is built aside, the temporary layer of the traced rays
+  int32_t *d_src[2] = {};
+  void *d_regrow0 = nullptr, *d_tmp = nullptr;
+  size_t src_cap[2] = {}, regrow0_cap = 0, tmp_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_layer[MT_MAX_RECURSION + 1][2] = {};
 };
@@ -2769,28 +2774,34 @@ int raytree_malloc(void **p, size_t bytes, const char *what) {
   return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
 }
 
-// One allocation holds a layer's planes, each at a multiple of 256 bytes.
-int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
-  const size_t n_l = (size_t)t->info.n_lights;
+// One allocation holds a layer's planes, each at a multiple of 256 bytes: the planes of layer k with n rays and n_l
+// lights laid out from `base` (nullptr: only the size is wanted).  Returns the bytes.
+size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, RayTreeLayer *out) {
   struct Part { void **at; size_t bytes; };
-  RayTreeLayer &L = t->layer[k];
+  RayTreeLayer &L = *out;
   const Part parts[] = {
       {(void **)&L.ray, n * 48}, {(void **)&L.coef, n * 8}, {(void **)&L.point, n * 24}, {(void **)&L.normal, n * 24},
       {(void **)&L.albedo, n * 24}, {(void **)&L.power, n_l * n * 24}, {(void **)&L.color, n * 24},
       {(void **)&L.material, n * 4}, {(void **)&L.child_refl, n * 4}, {(void **)&L.child_refr, n * 4},
       {(void **)&L.pixel, k == 0 ? n * 4 : 0}, {(void **)&L.in_object, n}, {(void **)&L.in_shadow, n_l * n},
       {(void **)&L.spawn, n}};
-  size_t total = 0;
-  for (const Part &p : parts) total += (p.bytes + 255) & ~(size_t)255;
-  char what[64];
-  snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
-  MT_TRY(raytree_malloc(&t->alloc[k], total, what));
   size_t at = 0;
   for (const Part &p : parts) {
-    *p.at = (char *)t->alloc[k] + at;
+    if (base != nullptr) *p.at = (char *)base + at;
     at += (p.bytes + 255) & ~(size_t)255;
   }
   if (k != 0) L.pixel = nullptr;
+  return at;
+}
+
+int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
+  const size_t n_l = (size_t)t->info.n_lights;
+  RayTreeLayer &L = t->layer[k];
+  const size_t total = raytree_carve_layer(nullptr, n_l, k, n, &L);
+  char what[64];
+  snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
+  MT_TRY(raytree_malloc(&t->alloc[k], total, what));
+  (void)raytree_carve_layer(t->alloc[k], n_l, k, n, &L);
   t->info.bytes += total;
   t->info.n_rays[k] = (int64_t)n;
   t->info.n_layers = k + 1;
@@ -2968,6 +2979,30 @@ int raytree_import_rays(mt_raytree *t, const mt_ray_list *rays, bool on_device, 
   return release(MT_OK);
 }
 
+// raytree_trace_kernel over the n rays of L as rays of the tree's layer k (a layer of the tree, or a dense list of some of
+// its rays), between that layer's two events
+int launch_raytree_trace(mt_raytree *t, const RayTreeLayer &L, size_t n, int k, hipStream_t stream) {
+  mt_scene *s = t->scene;
+  RayTreeTraceArgs A{};
+  A.L = L;
+  A.n_rays = (uint32_t)n;
+  A.n_items = (uint32_t)((n + 63) / 64);
+  A.secondary = k > 0 ? 1 : 0;
+  A.may_spawn = k < t->info.max_depth ? 1 : 0;
+  unsigned grid = 0;
+  MT_TRY(prepare_persistent_launch(s, A.n_items, &grid, stream));
+  A.counters = s->d_counters;
+  A.work_counter = s->d_gb_work;
+  if (!t->ev_layer[k][0]) HIP_TRY(hipEventCreate(&t->ev_layer[k][0]));
+  if (!t->ev_layer[k][1]) HIP_TRY(hipEventCreate(&t->ev_layer[k][1]));
+  HIP_TRY(hipEventRecord(t->ev_layer[k][0], stream));
+  hipLaunchKernelGGL(kernels_of(s->deep).raytree_trace[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
+                     s->lds_bytes, stream, s->dev, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(t->ev_layer[k][1], stream));
+  return MT_OK;
+}
+
 // Layer after layer: trace, compact, (host: size the next layer), spawn.  Layer 0 comes from the tree's sensor, or from
 // `rays` (a ray-list tree; on_device: its pointers are device pointers).
 int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_stats *stats) {
@@ -2996,23 +3031,7 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
   }
   for (int k = 0;; k++) {
     const size_t n = (size_t)I.n_rays[k];
-    RayTreeTraceArgs A{};
-    A.L = t->layer[k];
-    A.n_rays = (uint32_t)n;
-    A.n_items = (uint32_t)((n + 63) / 64);
-    A.secondary = k > 0 ? 1 : 0;
-    A.may_spawn = k < I.max_depth ? 1 : 0;
-    unsigned grid = 0;
-    MT_TRY(prepare_persistent_launch(s, A.n_items, &grid, stream));
-    A.counters = s->d_counters;
-    A.work_counter = s->d_gb_work;
-    HIP_TRY(hipEventCreate(&t->ev_layer[k][0]));
-    HIP_TRY(hipEventCreate(&t->ev_layer[k][1]));
-    HIP_TRY(hipEventRecord(t->ev_layer[k][0], stream));
-    hipLaunchKernelGGL(kernels_of(s->deep).raytree_trace[s->stats_enabled ? 1 : 0], dim3(grid), dim3(s->waves_per_block * 64),
-                       s->lds_bytes, stream, s->dev, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t->ev_layer[k][1], stream));
+    MT_TRY(launch_raytree_trace(t, t->layer[k], n, k, stream));
     if (k == I.max_depth) {  // no ray of the deepest layer has a child
       HIP_TRY(hipMemsetAsync(t->layer[k].child_refl, 0xff, n * 4, stream));
       HIP_TRY(hipMemsetAsync(t->layer[k].child_refr, 0xff, n * 4, stream));
@@ -3115,6 +3134,11 @@ void mt_raytree_destroy(mt_raytree *t) {
   if (t->d_bad) (void)hipFree(t->d_bad);
   if (t->d_mismatch) (void)hipFree(t->d_mismatch);
   if (t->d_albedo_changed) (void)hipFree(t->d_albedo_changed);
+  for (int32_t *p : t->d_src) {
+    if (p) (void)hipFree(p);
+  }
+  if (t->d_regrow0) (void)hipFree(t->d_regrow0);
+  if (t->d_tmp) (void)hipFree(t->d_tmp);
   if (t->ev0) (void)hipEventDestroy(t->ev0);
   if (t->ev1) (void)hipEventDestroy(t->ev1);
   for (auto &e : t->ev_layer) {
@@ -3363,13 +3387,220 @@ void diff_materials(const std::vector<mt_material> &was, const std::vector<mt_ma
   }
 }
 
-}  // namespace
+// scratch of a tree that only grows: at least `bytes` at *p
+int raytree_scratch(void **p, size_t *cap, size_t bytes, const char *what) {
+  if (*p != nullptr && *cap >= bytes) return MT_OK;
+  if (*p != nullptr) {
+    (void)hipFree(*p);  // (waits for whatever still reads it)
+    *p = nullptr;
+    *cap = 0;
+  }
+  MT_TRY(raytree_malloc(p, bytes, what));
+  *cap = bytes;
+  return MT_OK;
+}
 
-int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) {
+// mt_raytree_regrow_materials after a check pass that found mismatches: the new tree under the scene's current
+// materials, built layer by layer next to the old one (mt_raytree.h, "edited materials that change the tree's shape"),
+// then swapped in.  Until the swap only scratch and the new allocations are written: a failure before it leaves every
+// plane of the tree as it was.  The scene's counters are zero at entry and hold the tracing launches' sums at exit.
+int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info *info, hipStream_t stream) {
+  mt_scene *s = t->scene;
+  mt_raytree_desc &I = t->info;
+  const int n_mtl = s->n_materials;
+  const size_t n_l = (size_t)I.n_lights;
+  const int old_layers = I.n_layers;
+  void *alloc[MT_MAX_RECURSION + 1] = {};  // the new layers >= 1, aside
+  RayTreeLayer NL[MT_MAX_RECURSION + 1] = {};
+  size_t n_new[MT_MAX_RECURSION + 1] = {}, n_traced[MT_MAX_RECURSION + 1] = {};
+  const auto release = [&](int rc) {
+    for (void *p : alloc) {
+      if (p) (void)hipFree(p);
+    }
+    return rc;
+  };
+  const auto grid_of = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
+  // layer 0 stays where it is; its child indices and spawn bytes are built in scratch and its albedo waits for the commit
+  const size_t n0 = (size_t)I.n_rays[0];
+  const size_t idx_bytes = (n0 * 4 + 255) & ~(size_t)255;
+  MT_TRY(raytree_scratch(&t->d_regrow0, &t->regrow0_cap, 2 * idx_bytes + n0, "the ray tree's regrow scratch of layer 0"));
+  NL[0] = t->layer[0];
+  NL[0].child_refl = (int32_t *)t->d_regrow0;
+  NL[0].child_refr = (int32_t *)((char *)t->d_regrow0 + idx_bytes);
+  NL[0].spawn = (uint8_t *)t->d_regrow0 + 2 * idx_bytes;
+  n_new[0] = n0;
+  if (D.albedo) {
+    if (!t->d_albedo_changed) {
+      MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
+    }
+    HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
+  }
+  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  int new_layers = 0;
+  for (int k = 0;; k++) {
+    const size_t n = n_new[k];
+    const int32_t *src = k == 0 ? nullptr : t->d_src[k & 1];
+    {
+      RayTreeRegrowFlagsArgs A{};
+      A.L = NL[k];
+      A.src = src;
+      A.mtls = s->dev.mtls;
+      A.n_rays = (uint32_t)n;
+      A.n_materials = n_mtl;
+      A.may_spawn = k < I.max_depth ? 1 : 0;
+      hipLaunchKernelGGL(raytree_regrow_flags_kernel, grid_of(n), dim3(256), 0, stream, A);
+      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's flags kernel failed"));
+    }
+    new_layers = k + 1;
+    if (k == I.max_depth) {  // no ray of the deepest layer has a child
+      if (hipMemsetAsync(NL[k].child_refl, 0xff, n * 4, stream) != hipSuccess ||
+          hipMemsetAsync(NL[k].child_refr, 0xff, n * 4, stream) != hipSuccess) {
+        return release(fail(MT_ERR_HIP, "clearing the deepest layer's child indices failed"));
+      }
+      break;
+    }
+    hipLaunchKernelGGL(raytree_compact_kernel, dim3(1), dim3(kRayTreeCompactThreads), 0, stream, NL[k], (uint32_t)n,
+                       t->d_count);
+    unsigned long long children = 0;
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(&children, t->d_count, sizeof children, hipMemcpyDeviceToHost, stream) != hipSuccess) {
+      return release(fail(MT_ERR_HIP, "the regrow's compaction of layer %d failed", k));
+    }
+    // (synchronises: `children` has arrived; a tripped bound in layer k's tracing launch ends the call here)
+    if (const int rc = raytree_read_counters(s, stream)) return release(rc);
+    if (children == 0) break;
+    if (children >= 0x80000000ull) {
+      return release(fail(MT_ERR_UNSUPPORTED, "layer %d of the ray tree would have %llu rays (2^31 or more)", k + 1, children));
+    }
+    const size_t n1 = (size_t)children;
+    n_new[k + 1] = n1;
+    const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, &NL[k + 1]);
+    char what[64];
+    snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k + 1, n1);
+    if (const int rc = raytree_malloc(&alloc[k + 1], total, what)) return release(rc);
+    (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, &NL[k + 1]);
+    const int to = (k + 1) & 1;
+    if (const int rc = raytree_scratch((void **)&t->d_src[to], &t->src_cap[to], n1 * 4, "the ray tree's regrow indices")) {
+      return release(rc);
+    }
+    {
+      RayTreeRegrowLinkArgs A{};
+      A.parent = NL[k];
+      A.child = NL[k + 1];
+      A.parent_src = src;
+      // (past the old tree's last layer every parent is a traced ray: src < 0, the old indices are not read)
+      A.old_child_refl = k < old_layers ? t->layer[k].child_refl : nullptr;
+      A.old_child_refr = k < old_layers ? t->layer[k].child_refr : nullptr;
+      A.child_src = t->d_src[to];
+      A.mtls = s->dev.mtls;
+      A.n_parent = (uint32_t)n;
+      hipLaunchKernelGGL(raytree_regrow_link_kernel, grid_of(n), dim3(256), 0, stream, A);
+      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's link kernel failed"));
+    }
+    if (k + 1 < old_layers) {  // (else no ray of layer k + 1 has an old index)
+      RayTreeRegrowCopyArgs A{};
+      A.from = t->layer[k + 1];
+      A.to = NL[k + 1];
+      A.src = t->d_src[to];
+      A.n_from = (uint32_t)I.n_rays[k + 1];
+      A.n_to = (uint32_t)n1;
+      A.n_lights = I.n_lights;
+      A.n_materials = n_mtl;
+      A.mtls = s->dev.mtls;
+      A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+      hipLaunchKernelGGL(raytree_regrow_copy_kernel, grid_of(n1), dim3(256), 0, stream, A);
+      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
+    }
+    // the traced rays of layer k + 1: the link kernel left 1 in their spawn bytes, so the layer's own compaction gives
+    // their places in the dense list (child_refl) and their number
+    hipLaunchKernelGGL(raytree_compact_kernel, dim3(1), dim3(kRayTreeCompactThreads), 0, stream, NL[k + 1], (uint32_t)n1,
+                       t->d_count);
+    unsigned long long listed = 0;
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(&listed, t->d_count, sizeof listed, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
+      return release(fail(MT_ERR_HIP, "listing the traced rays of layer %d failed", k + 1));
+    }
+    const size_t m = (size_t)listed;  // (<= n1 < 2^31)
+    n_traced[k + 1] = m;
+    if (m == 0) continue;
+    RayTreeRegrowListArgs A{};
+    const size_t tmp_bytes = raytree_carve_layer(nullptr, n_l, k + 1, m, &A.tmp);
+    if (const int rc = raytree_scratch(&t->d_tmp, &t->tmp_cap, tmp_bytes, "the ray tree's list of traced rays")) {
+      return release(rc);
+    }
+    (void)raytree_carve_layer(t->d_tmp, n_l, k + 1, m, &A.tmp);
+    A.L = NL[k + 1];
+    A.n_rays = (uint32_t)n1;
+    A.n_list = (uint32_t)m;
+    A.n_lights = I.n_lights;
+    hipLaunchKernelGGL(raytree_regrow_gather_kernel, grid_of(n1), dim3(256), 0, stream, A);
+    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's gather kernel failed"));
+    if (const int rc = launch_raytree_trace(t, A.tmp, m, k + 1, stream)) return release(rc);
+    hipLaunchKernelGGL(raytree_regrow_scatter_kernel, grid_of(n1), dim3(256), 0, stream, A);
+    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's scatter kernel failed"));
+  }
+  // the last tracing launch's status; nothing of the old tree has been written so far, and nothing below fails for size
+  if (const int rc = raytree_read_counters(s, stream)) return release(rc);
+  // ---- the commit: layer 0 in place, the layers below swapped
+  if (hipMemcpyAsync(t->layer[0].child_refl, NL[0].child_refl, n0 * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
+      hipMemcpyAsync(t->layer[0].child_refr, NL[0].child_refr, n0 * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+    return release(fail(MT_ERR_HIP, "writing layer 0's child indices failed"));
+  }
+  if (D.albedo) {
+    RayTreeRecommitArgs A{};
+    A.L = t->layer[0];
+    A.mtls = s->dev.mtls;
+    A.albedo_changed = t->d_albedo_changed;
+    A.n_rays = (uint32_t)n0;
+    A.n_materials = n_mtl;
+    A.copy_coef = 0;
+    hipLaunchKernelGGL(raytree_recommit_kernel, grid_of(n0), dim3(256), 0, stream, A);
+    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching layer 0's commit failed"));
+  }
+  if (hipStreamSynchronize(stream) != hipSuccess) return release(fail(MT_ERR_HIP, "the regrow's commit failed"));
+  if (info) {
+    info->regrown = 1;
+    info->n_layers_before = old_layers;
+    info->n_layers_after = new_layers;
+    for (int k = 0; k <= MT_MAX_RECURSION; k++) {
+      info->traced[k] = (int64_t)n_traced[k];
+      info->kept[k] = (int64_t)(n_new[k] - n_traced[k]);
+      info->dropped[k] = I.n_rays[k] - info->kept[k];  // (0 from the old tree's last layer on)
+    }
+  }
+  RayTreeLayer none{};
+  for (int k = 1; k <= MT_MAX_RECURSION; k++) {
+    if (t->alloc[k]) {
+      I.bytes -= raytree_carve_layer(nullptr, n_l, k, (size_t)I.n_rays[k], &none);
+      (void)hipFree(t->alloc[k]);
+    }
+    t->alloc[k] = alloc[k];
+    t->layer[k] = NL[k];
+    I.n_rays[k] = (int64_t)n_new[k];
+    if (alloc[k]) I.bytes += raytree_carve_layer(nullptr, n_l, k, n_new[k], &none);
+  }
+  I.n_layers = new_layers;
+  for (int k = 0; k <= MT_MAX_RECURSION; k++) {
+    float ms = 0;
+    if (n_traced[k] != 0) HIP_TRY(hipEventElapsedTime(&ms, t->ev_layer[k][0], t->ev_layer[k][1]));
+    I.trace_ms[k] = ms;
+  }
+  return MT_OK;
+}
+
+// mt_raytree_update_materials, and mt_raytree_regrow_materials when `regrow` is set: the two calls differ in the light
+// count check and in what a check pass with mismatches leads to.
+int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytree_regrow_info *info) {
   if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
   const auto w0 = std::chrono::steady_clock::now();
   mt_scene *s = t->scene;
+  const mt_raytree_desc &I = t->info;
   if (stats) memset(stats, 0, sizeof *stats);
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->n_layers_before = info->n_layers_after = I.n_layers;
+  }
   if (t->mtl_generation == s->mtl_generation) return MT_OK;
   MaterialDiff D;
   diff_materials(t->mtls, s->mtls_host, &D);
@@ -3377,11 +3608,13 @@ int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) {
     return fail(MT_ERR_UNSUPPORTED, "material %d has a texture and its ambient or tex changed: the ray tree keeps neither "
                                     "the texel nor the primitive, a new tree is needed", D.textured);
   }
-  const mt_raytree_desc &I = t->info;
   const bool retrace = D.shadow && I.n_lights > 0;
-  if (retrace && s->dev.n_lights != I.n_lights) {
+  // (a regrow may trace new rays, whose light planes come from the scene's current lights)
+  const bool lights_read = regrow ? (D.shape || D.shadow) && I.n_lights > 0 : retrace;
+  if (lights_read && s->dev.n_lights != I.n_lights) {
     return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", s->dev.n_lights, I.n_lights);
   }
+  bool regrown = false;
   if (D.shape || D.albedo || retrace) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = nullptr;
@@ -3410,41 +3643,63 @@ int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) {
       unsigned long long found[2] = {0, 0};
       HIP_TRY(hipMemcpyAsync(found, t->d_mismatch, sizeof found, hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
-      if (found[0] != 0) {
+      if (found[0] != 0 && !regrow) {
         return fail(MT_ERR_UNSUPPORTED, "the new materials change the shape of the ray tree: %llu rays spawn other "
                                         "children, the first in layer %d at ray %llu; a new tree is needed",
                     found[0], (int)(found[1] >> 32), found[1] & 0xffffffffull);
       }
-    }
-    if (D.albedo) {
-      if (!t->d_albedo_changed) {
-        MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
+      if (found[0] != 0) {
+        // (only a tree of zero lights gets here with another count: the tracing kernel runs the SCENE's lights' loops,
+        // and the new layers have planes for the tree's)
+        if (s->dev.n_lights != I.n_lights) {
+          return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", s->dev.n_lights, I.n_lights);
+        }
+        HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+        const bool counters_were = s->stats_enabled;
+        if (stats) s->stats_enabled = true;  // the caller asked for them
+        const int rc = raytree_regrow(t, D, info, stream);
+        s->stats_enabled = counters_were;
+        if (rc != MT_OK) return rc;
+        regrown = true;
       }
-      HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
     }
-    for (int k = 0; k < I.n_layers; k++) {
-      const size_t n = (size_t)I.n_rays[k];
-      RayTreeRecommitArgs A{};
-      A.L = t->layer[k];
-      A.mtls = s->dev.mtls;
-      A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
-      A.n_rays = (uint32_t)n;
-      A.n_materials = n_mtl;
-      A.copy_coef = D.shape && k > 0 ? 1 : 0;
-      if (!A.copy_coef && !A.albedo_changed) continue;
-      hipLaunchKernelGGL(raytree_recommit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-      HIP_TRY(hipGetLastError());
+    if (!regrown) {  // the commit of a tree that keeps its shape (a regrown tree has taken everything already)
+      if (D.albedo) {
+        if (!t->d_albedo_changed) {
+          MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
+        }
+        HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
+      }
+      for (int k = 0; k < I.n_layers; k++) {
+        const size_t n = (size_t)I.n_rays[k];
+        RayTreeRecommitArgs A{};
+        A.L = t->layer[k];
+        A.mtls = s->dev.mtls;
+        A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+        A.n_rays = (uint32_t)n;
+        A.n_materials = n_mtl;
+        A.copy_coef = D.shape && k > 0 ? 1 : 0;
+        if (!A.copy_coef && !A.albedo_changed) continue;
+        hipLaunchKernelGGL(raytree_recommit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
+        HIP_TRY(hipGetLastError());
+      }
+      if (info) {
+        for (int k = 0; k < I.n_layers; k++) info->kept[k] = I.n_rays[k];
+      }
     }
-    if (retrace) {
-      std::vector<int32_t> all((size_t)I.n_lights);
-      for (int i = 0; i < I.n_lights; i++) all[(size_t)i] = i;
+    if (retrace || regrown) {
       MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-      const bool counters_were = s->stats_enabled;
-      if (stats) s->stats_enabled = true;  // the caller asked for them
-      const int rc = launch_raytree_update(t, all.data(), I.n_lights, stream);
-      s->stats_enabled = counters_were;
-      if (rc != MT_OK) return rc;
+      // (a regrown tree's tracing launches have counted already)
+      if (!regrown) HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+      if (retrace) {
+        std::vector<int32_t> all((size_t)I.n_lights);
+        for (int i = 0; i < I.n_lights; i++) all[(size_t)i] = i;
+        const bool counters_were = s->stats_enabled;
+        if (stats) s->stats_enabled = true;  // the caller asked for them
+        const int rc = launch_raytree_update(t, all.data(), I.n_lights, stream);
+        s->stats_enabled = counters_were;
+        if (rc != MT_OK) return rc;
+      }
       HIP_TRY(hipEventRecord(t->ev1, stream));
       HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
@@ -3460,11 +3715,21 @@ int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) {
       HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
       stats->kernel_ms = ms;
     }
+  } else if (info) {
+    for (int k = 0; k < I.n_layers; k++) info->kept[k] = I.n_rays[k];
   }
   t->mtls = s->mtls_host;
   t->mtl_generation = s->mtl_generation;
   if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   return MT_OK;
+}
+
+}  // namespace
+
+int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) { return raytree_take_materials(t, stats, false, nullptr); }
+
+int mt_raytree_regrow_materials(mt_raytree *t, mt_raytree_regrow_info *info, mt_stats *stats) {
+  return raytree_take_materials(t, stats, true, info);
 }
 
 // ---- one frame on several GPUs of this process (main_net_master.cc:195-236) --------------------------

@@ -667,4 +667,179 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
   }
 }
 
+// ---- edited materials that change the tree's shape (include/mythtracer_hip.h, mt_raytree_regrow_materials) ----
+// The NEW tree is built layer by layer, top-down, next to the old one.  A ray of the new tree is KEPT when its path from
+// the pixel exists in the old tree -- every ray of layer 0; a child whose parent is kept and had a child in the same
+// slot -- and TRACED otherwise.  Every new layer k carries src[i]: the ray's index in the OLD layer k, -1 for a traced
+// ray (layer 0: src = nullptr, meaning src[i] = i).  A kept ray takes everything that depends on no material from the
+// old tree; a traced ray goes through the unchanged raytree_trace_kernel in a dense temporary layer.  Per layer k, over
+// plain 256-thread grids (the scans are raytree_compact_kernel's, unchanged):
+//   raytree_regrow_flags_kernel    one thread per ray: the spawn byte of a KEPT ray from the NEW materials, the ray's new
+//                                  coef, in_object, may_spawn and lit-ness -- raytree_trace_kernel's expressions, with
+//                                  lit as raytree_recoef_kernel states it.  A traced ray has its byte from its trace.
+//   (raytree_compact_kernel)       the spawn bytes become layer k's child indices and layer k + 1's ray count.
+//   raytree_regrow_link_kernel     one thread per parent, per child slot: the old child index -- the old parent's, where
+//                                  the parent is kept and had that child -- goes to src of layer k + 1; the child's coef
+//                                  with raytree_spawn_kernel's expressions under the new materials; a child WITHOUT an
+//                                  old index also gets its ray and in_object, raytree_spawn_kernel's expressions again.
+//                                  The child's spawn byte becomes 1 for "to be traced", 0 for kept:
+//   (raytree_compact_kernel)       run over layer k + 1 itself, it leaves every traced ray's place in the dense list in
+//                                  child_refl (-1 for a kept ray; child_refr is all -1) and the list's length in the
+//                                  count.  The order is the layer's, so a work item is 64 consecutive traced rays.  The
+//                                  places live in child_refl until layer k + 1's own compaction overwrites them.
+//   raytree_regrow_copy_kernel     one thread per kept ray of layer k + 1, by the destination index: ray, in_object,
+//                                  point, normal, material, every light's power and in_shadow from the old layer at
+//                                  src; albedo too, or the new ambient where the material's byte in albedo_changed is
+//                                  set (raytree_recommit_kernel's rule).
+//   raytree_regrow_gather_kernel   ray, coef and in_object of the traced rays to their places in the temporary layer;
+//   (raytree_trace_kernel)         over the temporary layer, secondary = 1, may_spawn = (k + 1 < max_depth);
+//   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow and spawn back to the new layer.
+// That regrouping the traced rays changes no bit is the ray-list contract: layer k handed in as an n x 1 list gives the
+// tree's layers k onwards.  None of these kernels writes a plane of the OLD tree.
+struct RayTreeRegrowFlagsArgs {
+  RayTreeLayer L;
+  const int32_t *src;       // nullptr: layer 0, every ray is kept
+  const mt_material *mtls;  // the scene's CURRENT materials
+  uint32_t n_rays;
+  int32_t n_materials;
+  int32_t may_spawn;        // layer < max_depth
+};
+
+__global__ __launch_bounds__(256) void raytree_regrow_flags_kernel(RayTreeRegrowFlagsArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_rays) return;
+  if (A.src != nullptr && A.src[i] < 0) return;  // (traced: raytree_trace_kernel left its byte)
+  const double p0 = A.L.point[i * 3];
+  const int mtl = A.L.material[i];
+  const bool lit = p0 == p0 && mtl >= 0 && mtl < A.n_materials;
+  // the child conditions, :181-184 and :192, as raytree_trace_kernel states them
+  unsigned spawn = 0;
+  if (lit && A.may_spawn) {
+    const mt_material *m = A.mtls + mtl;
+    const bool in_object = A.L.in_object[i] != 0;
+    if (m->reflectance > 0.0 && A.L.coef[i] > 0.01 && !in_object) spawn |= 1u;
+    if (m->transparency > 0.0) spawn |= 2u;
+  }
+  A.L.spawn[i] = (uint8_t)spawn;
+}
+
+struct RayTreeRegrowLinkArgs {
+  RayTreeLayer parent, child;                      // layers k and k + 1 of the NEW tree
+  const int32_t *parent_src;                       // nullptr: layer 0
+  const int32_t *old_child_refl, *old_child_refr;  // of the OLD layer k
+  int32_t *child_src;                              // [the child layer's rays]
+  const mt_material *mtls;                         // the scene's CURRENT materials
+  uint32_t n_parent;
+};
+
+__global__ __launch_bounds__(256) void raytree_regrow_link_kernel(RayTreeRegrowLinkArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_parent) return;
+  const int cr = A.parent.child_refl[i], ct = A.parent.child_refr[i];
+  if (cr < 0 && ct < 0) return;
+  const int s = A.parent_src != nullptr ? A.parent_src[i] : (int)i;
+  const int ocr = s >= 0 ? A.old_child_refl[s] : -1, oct = s >= 0 ? A.old_child_refr[s] : -1;
+  const V3 dir = v3_load(A.parent.ray + i * 6 + 3);
+  const V3 Pt = v3_load(A.parent.point + i * 3);
+  const double coef = A.parent.coef[i];
+  const bool in_object = A.parent.in_object[i] != 0;
+  if (cr >= 0) {
+    A.child_src[cr] = ocr;
+    A.child.spawn[cr] = ocr < 0 ? 1 : 0;
+    A.child.coef[cr] = coef * A.mtls[A.parent.material[i]].reflectance;  // :187
+    if (ocr < 0) {  // raytree_spawn_kernel's reflected child
+      V3 Nn = v3_load(A.parent.normal + i * 3);  // as GetNormal returned it, :38
+      if (dot(Nn, -dir) < 0.0) Nn = -Nn;         // :42-45
+      const V3 Rd = dir - Nn * (2 * dot(dir, Nn));  // :68-69
+      const V3 ro = Pt + (Rd * 0.0001);             // :70-74
+      double *r = A.child.ray + (size_t)cr * 6;
+      r[0] = ro.x; r[1] = ro.y; r[2] = ro.z; r[3] = Rd.x; r[4] = Rd.y; r[5] = Rd.z;
+      A.child.in_object[cr] = in_object ? 1 : 0;
+    }
+  }
+  if (ct >= 0) {
+    A.child_src[ct] = oct;
+    A.child.spawn[ct] = oct < 0 ? 1 : 0;
+    A.child.coef[ct] = coef;  // :223
+    if (oct < 0) {  // raytree_spawn_kernel's refracted child
+      const V3 rdir = normalized(dir);  // :208-212 (direction unchanged, re-normalised)
+      const V3 ro = Pt + rdir * 0.00001;
+      double *r = A.child.ray + (size_t)ct * 6;
+      r[0] = ro.x; r[1] = ro.y; r[2] = ro.z; r[3] = rdir.x; r[4] = rdir.y; r[5] = rdir.z;
+      A.child.in_object[ct] = in_object ? 0 : 1;  // :222
+    }
+  }
+}
+
+struct RayTreeRegrowCopyArgs {
+  RayTreeLayer from, to;          // the OLD layer and the new one
+  const int32_t *src;             // [n_to]
+  uint32_t n_from, n_to;
+  int32_t n_lights;
+  int32_t n_materials;
+  const mt_material *mtls;        // the scene's CURRENT materials
+  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
+};
+
+__global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowCopyArgs A) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (size_t)A.n_to) return;
+  const int src = A.src[j];
+  if (src < 0) return;
+  const size_t s = (size_t)src, n_from = (size_t)A.n_from, n_to = (size_t)A.n_to;
+  store3(A.to.ray, j * 2, v3_load(A.from.ray + s * 6));
+  store3(A.to.ray, j * 2 + 1, v3_load(A.from.ray + s * 6 + 3));
+  A.to.in_object[j] = A.from.in_object[s];
+  store3(A.to.point, j, v3_load(A.from.point + s * 3));
+  store3(A.to.normal, j, v3_load(A.from.normal + s * 3));
+  const int mtl = A.from.material[s];
+  A.to.material[j] = mtl;
+  if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
+    const mt_material *m = A.mtls + mtl;
+    store3(A.to.albedo, j, v3(m->ambient[0], m->ambient[1], m->ambient[2]));
+  } else {
+    store3(A.to.albedo, j, v3_load(A.from.albedo + s * 3));
+  }
+  for (int li = 0; li < A.n_lights; li++) {
+    store3(A.to.power, (size_t)li * n_to + j, v3_load(A.from.power + ((size_t)li * n_from + s) * 3));
+    A.to.in_shadow[(size_t)li * n_to + j] = A.from.in_shadow[(size_t)li * n_from + s];
+  }
+}
+
+struct RayTreeRegrowListArgs {
+  RayTreeLayer L, tmp;  // the new layer (child_refl = the traced rays' places in tmp, -1 = kept) and the dense list
+  uint32_t n_rays;      // of L
+  uint32_t n_list;      // of tmp
+  int32_t n_lights;
+};
+
+__global__ __launch_bounds__(256) void raytree_regrow_gather_kernel(RayTreeRegrowListArgs A) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (size_t)A.n_rays) return;
+  const int place = A.L.child_refl[j];
+  if (place < 0) return;
+  const size_t p = (size_t)place;
+  store3(A.tmp.ray, p * 2, v3_load(A.L.ray + j * 6));
+  store3(A.tmp.ray, p * 2 + 1, v3_load(A.L.ray + j * 6 + 3));
+  A.tmp.coef[p] = A.L.coef[j];
+  A.tmp.in_object[p] = A.L.in_object[j];
+}
+
+__global__ __launch_bounds__(256) void raytree_regrow_scatter_kernel(RayTreeRegrowListArgs A) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (size_t)A.n_rays) return;
+  const int place = A.L.child_refl[j];
+  if (place < 0) return;
+  const size_t p = (size_t)place, n = (size_t)A.n_rays, m = (size_t)A.n_list;
+  store3(A.L.point, j, v3_load(A.tmp.point + p * 3));
+  store3(A.L.normal, j, v3_load(A.tmp.normal + p * 3));
+  store3(A.L.albedo, j, v3_load(A.tmp.albedo + p * 3));
+  A.L.material[j] = A.tmp.material[p];
+  for (int li = 0; li < A.n_lights; li++) {
+    store3(A.L.power, (size_t)li * n + j, v3_load(A.tmp.power + ((size_t)li * m + p) * 3));
+    A.L.in_shadow[(size_t)li * n + j] = A.tmp.in_shadow[(size_t)li * m + p];
+  }
+  A.L.spawn[j] = A.tmp.spawn[p];
+}
+
 }  // namespace mt

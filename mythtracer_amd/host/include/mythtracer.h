@@ -218,6 +218,13 @@ class MythTracer {
   // spawn children or touches the ambient of a textured material: a new BuildRayTree is needed then.  Refused with
   // several devices, like BuildRayTree, and for a NULL or empty RayTree.  LastStats() describes the call.
   bool UpdateRayTreeMaterials(RayTree* tree);
+  // The same after an edit that changes which rays spawn children -- a matte surface made reflective, a mirror switched
+  // off, a pane made opaque (mt_raytree_regrow_materials): the rays whose path survives are kept, the dead subtrees
+  // dropped and only the new rays traced, under GetScene()->lights; Layers() and Rays() follow.  The tree is then what a
+  // new BuildRayTree gives, and ShadeRayTree gives RayTrace's frame.  Where the shape survives the call is
+  // UpdateRayTreeMaterials.  Still fails for the ambient of a textured material.  Refused with several devices and for a
+  // NULL or empty RayTree.  LastStats() describes the call (rays_secondary = the rays traced).
+  bool RegrowRayTree(RayTree* tree);
   // The caller's rays instead of a camera's (mt_raytree_create_rays): TraceRay for a ray list, to the recursion level of
   // SetMaxRecursionLevel under GetScene()->lights.  list_width 0 means an n x 1 list, whose waves are 64 consecutive
   // rays of the caller's; otherwise it must divide n and the list is treated as a list_width x (n / list_width) image,

@@ -582,6 +582,23 @@ int mth_raytree_update_materials(void* p, void* t, uint64_t* stats8, double* ms2
   return 1;
 }
 
+// MythTracer::RegrowRayTree; stats8 / ms2 as mth_raytree_update fills them
+int mth_raytree_regrow(void* p, void* t, uint64_t* stats8, double* ms2) {
+  Handle* h = static_cast<Handle*>(p);
+  if (!h->mt.RegrowRayTree(static_cast<raytracer::RayTree*>(t))) return 0;
+  const raytracer::RenderStats& s = h->mt.LastStats();
+  if (stats8) {
+    const uint64_t v[8] = {s.rays_primary, s.rays_secondary, s.rays_shadow, s.box_tests,
+                           s.node_visits,  s.tri_tests,      s.mt_tests,    s.shaded_hits};
+    memcpy(stats8, v, sizeof v);
+  }
+  if (ms2) {
+    ms2[0] = s.kernel_ms;
+    ms2[1] = s.total_ms;
+  }
+  return 1;
+}
+
 // MythTracer::UpdateLightBuffer(GBuffer, lights, LightBuffer*) under the facade's lights.  gb_planes[2] = point
 // (doubles), material (int32) of the cw x ch chunk; lb_channels = LightBuffer::k* bits, lb_planes[2] = power, in_shadow
 // for n_lights lights (each NULL or sized for them), updated in place: the planes of the listed lights only.

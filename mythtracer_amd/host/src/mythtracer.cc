@@ -288,6 +288,40 @@ bool MythTracer::UpdateRayTreeMaterials(RayTree* tree) {
   return true;
 }
 
+bool MythTracer::RegrowRayTree(RayTree* tree) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  // (the facade's own refusals, before anything touches a device)
+  if (devices_.size() > 1) return refuse("the ray tree is not supported with several devices (SetDevices)");
+  if (tree == nullptr) return refuse("RayTree is NULL");
+  if (tree->Empty()) return refuse("the RayTree is empty: BuildRayTree first");
+  if (dev_ != nullptr &&
+      mt_scene_set_lights(dev_, reinterpret_cast<const mt_light*>(scene.lights.data()), (int)scene.lights.size()) != MT_OK) {
+    return refuse(std::string("ray-tree regrow failed: ") + mt_last_error());
+  }
+  mt_stats st;
+  memset(&st, 0, sizeof st);
+  mt_raytree_regrow_info info;
+  if (dev_ != nullptr) (void)mt_scene_set_stats(dev_, collect_stats_ ? 1 : 0);
+  if (mt_raytree_regrow_materials(tree->Get(), &info, &st) != MT_OK) {
+    return refuse(std::string("ray-tree regrow failed: ") + mt_last_error());
+  }
+  stats_ = RenderStats{};
+  stats_.rays_secondary = st.rays_secondary;
+  stats_.rays_shadow = st.rays_shadow;
+  stats_.box_tests = st.box_tests;
+  stats_.node_visits = st.node_visits;
+  stats_.tri_tests = st.tri_tests;
+  stats_.mt_tests = st.mt_tests;
+  stats_.shaded_hits = st.shaded_hits;
+  stats_.kernel_ms = st.kernel_ms;
+  stats_.total_ms = st.total_ms;
+  return true;
+}
+
 // The supersampling factor is checked before anything touches a device: a caller without one sees this message too.
 bool MythTracer::CheckSupersampling(int image_width, int image_height, bool on_all_devices) {
   // (SetAdaptiveSupersampling wins over SetSupersampling)
