@@ -633,7 +633,8 @@ int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, 
  *   diffuse, specular, specular_exp, refraction_index, and transmission_filter of a material whose transparency is 0
  *     before and after: nothing to do, the shade reads them from the scene.  No kernel is launched.
  *   ambient or tex: where the material has a texture before or after the edit, MT_ERR_UNSUPPORTED before any device
- *     call (the tree keeps neither the texel nor the primitive).  Otherwise every ray whose material it is gets
+ *     call (the tree keeps neither the texel nor the primitive) -- unless the tree keeps uvw, see
+ *     mt_scene_set_raytree_uvw below, which lifts this refusal.  Otherwise every ray whose material it is gets
  *     albedo = ambient, which is what the tracing kernel stores for an untextured material.
  *   reflectance or transparency, of any material: the tree's shape may or may not survive.  A CHECK pass
  *     (mt::raytree_recoef_kernel, one launch per layer, top-down) carries every ray's coefficient under the new
@@ -679,7 +680,8 @@ int mt_raytree_update_materials(mt_raytree *tree, mt_stats *stats);
  *   (1) tree NULL: MT_ERR_ARG.
  *   (2) equal generations: MT_OK, no device call; info and stats all zero except n_layers_before = n_layers_after.
  *   (3) ambient or tex of a material that has a texture before or after the edit: MT_ERR_UNSUPPORTED with
- *       mt_raytree_update_materials's message (kept rays hold neither the texel nor the primitive).
+ *       mt_raytree_update_materials's message (kept rays hold neither the texel nor the primitive); not for a tree that
+ *       keeps uvw (mt_scene_set_raytree_uvw below).
  *   (4) a reflectance or transparency changed, or the edit is one a shadow ray may see (mt_raytree_update_materials's
  *       rule), the tree has lights, and the scene's light count is not the tree's: MT_ERR_ARG with
  *       mt_raytree_update_materials's message.  Stricter than that call: traced rays get their light planes from the
@@ -723,6 +725,74 @@ typedef struct mt_raytree_regrow_info {
   int64_t dropped[MT_MAX_RECURSION + 1]; /* per layer of the OLD tree: rays with no place in the new one */
 } mt_raytree_regrow_info;
 int mt_raytree_regrow_materials(mt_raytree *tree, mt_raytree_regrow_info *info, mt_stats *stats);
+
+/* Edited TEXTURES: texture `index` of the uploaded scene replaced in place -- size and format may change, the count may
+ * not -- for a look-dev session that swaps a floor's planks for tiles without flattening and uploading the triangles
+ * again.  (No reference counterpart.)  A texture touches exactly one quantity anywhere in this library, albedo =
+ * ambient * Texture::GetColorAt(u, v) (mythtracer.cc:58-64): no ray, hit, child condition or shadow loop reads one.
+ * mt_scene_set_texture is synchronous, like mt_scene_set_materials: it allocates room for the new texels, waits until
+ * the scene's device is idle, uploads them, patches the scene's one table entry and only then frees the old texels.  An
+ * allocation that does not fit is MT_ERR_NOMEM and the scene stays exactly as it was.  The kernels read size, format
+ * and texels through that table at run time; nothing derived from a texture is baked into the uploaded scene or cached
+ * on the host, so there is nothing else to refresh.
+ * Generations: the scene keeps one per texture, 0 at creation, bumped by EVERY successful set -- the scene keeps no host
+ * copy of the texels, so no comparison is made and setting the same bytes again counts as an edit.  Each successful set
+ * also bumps the scene's material generation: every ray tree of the scene becomes stale exactly as after a material
+ * edit (mt_raytree_update_materials).
+ * mt_scene_get_texture_info fills width, height and format of the texture as it now is; texels is set to NULL.
+ * CONTRACT: after the set, every call that renders or shades -- mt_scene_set_materials's list -- gives, byte for byte
+ * and plane for plane, what it gives on a scene newly created from the same description with that texture.  Cost
+ * history, forecasts and engine choice are left alone; G-buffer planes are the caller's (mt_retexture_gbuffer below).
+ * Argument checks come before any device call, in this order: the scene (NULL); index outside 0 .. n_textures - 1; a
+ * NULL mt_texture; set only: mt_scene_create's size and format check with its message ("texture %d: bad
+ * size/format").  All MT_ERR_ARG. */
+int mt_scene_set_texture(mt_scene *scene, int index, const mt_texture *tex);
+int mt_scene_get_texture_info(const mt_scene *scene, int index, mt_texture *out);
+
+/* Ray trees that keep uvw.  mt_scene_set_raytree_uvw(scene, 1): every tree made from now on -- mt_raytree_create,
+ * _create_rays, _create_rays_device, and the one inside mt_trace_rays -- stores one more plane per layer on the scene's
+ * GPU, uvw[n][3] doubles: Triangle::GetUVW(point), bit for bit mt_render_gbuffer's uvw for that ray, NaN for a miss.
+ * The tracing kernel computes it exactly as it does for a textured albedo, so no bit of any other plane moves.  0 is
+ * the default: bytes, planes and launches of a tree are then what they always were.  (MT_ERR_ARG: scene NULL, keep
+ * other than 0 or 1.)  A tree remembers how it was made (mt_raytree_keeps_uvw: 0 / 1, MT_ERR_ARG < 0 for NULL), and
+ * mt_raytree_info's bytes counts the plane: exactly 24 bytes per ray of the tree more than without it.  mt_raytree_layer stays as it is; mt_raytree_read_uvw copies one layer's plane to out_uvw[n_rays][3].  Its
+ * checks, in this order, all MT_ERR_ARG, before any device call: tree NULL; layer outside the tree's; out_uvw NULL; a
+ * tree that keeps no uvw.
+ * What uvw buys: mt_raytree_update_materials and mt_raytree_regrow_materials also compare the per-texture generations
+ * with the tree's snapshot of them (taken at creation and after each successful update or regrow).  A material is
+ * RETEXTURED when (a) its ambient or tex changed and it has a texture before or after the edit -- those calls' refusal
+ * (3) --, or (b) its current tex >= 0 and that texture was set since the snapshot.  A texture no material uses is
+ * nothing to do.
+ *   A tree WITHOUT uvw: (a) is refused as ever, with the same message; (b) is MT_ERR_UNSUPPORTED too, checked right
+ *     after (a) and before any device call, the message naming the texture and the first material that uses it; the
+ *     tree is untouched and still stale.  (Without this refusal a texture-only edit would compare equal materials and
+ *     declare a wrong tree fresh.)
+ *   A tree WITH uvw: the rays of a retextured material get albedo = ambient, times GetColorAt(texture, uvw.x, uvw.y)
+ *     where tex >= 0 -- the tracing kernel's expressions in its order, from the stored plane -- in the commit
+ *     (mt::raytree_recommit_kernel; in a regrow mt::raytree_regrow_copy_kernel for kept rays, reading the old layer's
+ *     uvw, which kept rays carry over and traced rays get from their trace).  No light plane is traced again for a
+ *     retexture alone: stats->rays_shadow stays 0.
+ * Everything else in the two calls is as documented above.  CONTRACT, unchanged in form: after MT_OK the tree is
+ * bit-identical, in every plane of every layer, uvw included, to mt_raytree_create[_rays] on a scene with the new
+ * materials and textures and the same switch; after a refusal it is bit-identical to what it was. */
+int mt_scene_set_raytree_uvw(mt_scene *scene, int keep);
+int mt_raytree_read_uvw(mt_raytree *tree, int layer, double *out_uvw);
+int mt_raytree_keeps_uvw(const mt_raytree *tree);
+
+/* The deferred path's counterpart: the albedo plane of a stored G-buffer again under the scene's CURRENT materials and
+ * textures.  Stateless, like mt_update_lightbuffer: reads gb->material and gb->uvw (chunk_w x chunk_h pixels, row-major)
+ * and writes gb->albedo for EVERY pixel: NaN where material is outside 0 .. n_materials - 1 (what mt_render_gbuffer
+ * stores for a miss or "no material"), else ambient, times GetColorAt(texture, uvw.x, uvw.y) where tex >= 0.  uvw may
+ * be NULL only while no current material has a texture.  No sensor, no traversal (mt::gbuffer_retexture_kernel, one
+ * thread per pixel): stats (nullable) has zero work counters, kernel_ms by events, total_ms = wall time.  No other
+ * plane is read or written.  Infinite u or v is left undefined, as in the tracing kernels.
+ * Checks, before any device call, in this order, all MT_ERR_ARG: gb NULL; material or albedo missing; uvw missing while
+ * a current material has a texture; chunk_w, chunk_h outside 1 .. 100000; the scene (NULL).  _device: the planes are
+ * device pointers on the scene's GPU, the launch is asynchronous on `stream`.
+ * CONTRACT: the albedo plane is bit-identical to mt_render_gbuffer's under the new materials and textures, so
+ * mt_shade_direct over it is mt_render_chunk(..., max_depth = 0) byte for byte. */
+int mt_retexture_gbuffer(mt_scene *scene, int chunk_w, int chunk_h, const mt_gbuffer *gb, mt_stats *stats);
+int mt_retexture_gbuffer_device(mt_scene *scene, int chunk_w, int chunk_h, const mt_gbuffer *d_gb, void *stream);
 
 /* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
  * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour

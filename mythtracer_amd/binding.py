@@ -38,6 +38,8 @@ HIP_SYMBOLS = [
     "mt_raytree_shade_colors_device", "mt_trace_rays",
     "mt_scene_set_materials", "mt_scene_get_materials", "mt_raytree_update_materials",
     "mt_raytree_regrow_materials",
+    "mt_scene_set_texture", "mt_scene_get_texture_info", "mt_scene_set_raytree_uvw", "mt_raytree_read_uvw",
+    "mt_raytree_keeps_uvw", "mt_retexture_gbuffer", "mt_retexture_gbuffer_device",
 ]
 MT_MAX_RECURSION = 16
 
@@ -308,6 +310,13 @@ class HipAbi:
         L.mt_scene_get_materials.argtypes = [vp, vp, ci]
         L.mt_raytree_update_materials.argtypes = [vp, vp]
         L.mt_raytree_regrow_materials.argtypes = [vp, vp, vp]
+        L.mt_scene_set_texture.argtypes = [vp, ci, C.POINTER(mt_texture)]
+        L.mt_scene_get_texture_info.argtypes = [vp, ci, C.POINTER(mt_texture)]
+        L.mt_scene_set_raytree_uvw.argtypes = [vp, ci]
+        L.mt_raytree_read_uvw.argtypes = [vp, ci, vp]
+        L.mt_raytree_keeps_uvw.argtypes = [vp]
+        L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
+        L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_chunk_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
         L.mt_render_tiles_device.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 8 + [vp, vp]
@@ -475,6 +484,60 @@ class HipAbi:
                          [m.refraction_index], dtype=np.float64)
             out.append(dict(values=v, tex=int(m.tex)))
         return out
+
+    def set_texture(self, h, index, texels):
+        """mt_scene_set_texture: texture `index` of the uploaded scene replaced by `texels`, an array (height, width, 3)
+        of uint8 (MT_TEX_RGB8) or float64 (MT_TEX_F64) as in flat["textures"] of MythTracer.flatten().  Size and
+        format may change.  Every ray tree of the scene is stale afterwards."""
+        texels = np.ascontiguousarray(texels)
+        if texels.ndim != 3 or texels.shape[2] != 3 or texels.dtype not in (np.uint8, np.float64):
+            raise ValueError("texels must be (height, width, 3) of uint8 or float64")
+        t = mt_texture()
+        t.height, t.width = texels.shape[0], texels.shape[1]
+        t.format = MT_TEX_RGB8 if texels.dtype == np.uint8 else MT_TEX_F64
+        t.texels = texels.ctypes.data
+        self.check(self.lib.mt_scene_set_texture(h, index, C.byref(t)))
+
+    def get_texture_info(self, h, index) -> dict:
+        """mt_scene_get_texture_info: dict(width, height, format) of the scene's texture `index` as it now is."""
+        t = mt_texture()
+        self.check(self.lib.mt_scene_get_texture_info(h, index, C.byref(t)))
+        return dict(width=int(t.width), height=int(t.height), format=int(t.format))
+
+    def set_raytree_uvw(self, h, keep: bool):
+        """mt_scene_set_raytree_uvw: ray trees made from now on keep (True) or do not keep (False, the default) a uvw
+        plane per layer, which update_materials / regrow need to take texture edits."""
+        self.check(self.lib.mt_scene_set_raytree_uvw(h, 1 if keep else 0))
+
+    def retexture_gbuffer(self, h, gbuffer) -> dict:
+        """mt_retexture_gbuffer: the albedo plane of `gbuffer` (dict with `material` (ch, cw) int32 and, unless no
+        current material has a texture, `uvw` (ch, cw, 3) float64) under the scene's CURRENT materials and textures.
+        Returns dict(albedo (ch, cw, 3), stats); the caller's planes are not written."""
+        if "material" not in gbuffer:
+            raise ValueError("the retexture needs the G-buffer plane 'material'")
+        m = np.ascontiguousarray(gbuffer["material"], dtype=np.int32)
+        if m.ndim != 2:
+            raise ValueError("G-buffer plane 'material' has shape %s, not (rows, columns)" % (m.shape,))
+        ch, cw = m.shape
+        uvw = None
+        if gbuffer.get("uvw") is not None:
+            uvw = np.ascontiguousarray(gbuffer["uvw"], dtype=np.float64)
+            if uvw.shape != (ch, cw, 3):
+                raise ValueError("G-buffer plane 'uvw' has shape %s, not that of the %dx%d chunk" % (uvw.shape, cw, ch))
+        albedo = np.zeros((ch, cw, 3), dtype=np.float64)
+        g = mt_gbuffer(material=m.ctypes.data, uvw=_ptr(uvw), albedo=albedo.ctypes.data)
+        st = mt_stats()
+        self.check(self.lib.mt_retexture_gbuffer(h, cw, ch, C.byref(g), C.addressof(st)))
+        return dict(albedo=albedo, stats=st.as_dict())
+
+    def retexture_gbuffer_device(self, h, chunk_w, chunk_h, d_gb_planes, stream=None):
+        """mt_retexture_gbuffer_device: dict plane name -> device pointer (material, albedo, uvw); asynchronous."""
+        for n in d_gb_planes:
+            if n not in GBUFFER_PLANES:
+                raise ValueError("unknown G-buffer plane %r" % (n,))
+        val = lambda p: p.value if isinstance(p, C.c_void_p) else p  # noqa: E731
+        g = mt_gbuffer(**{n: val(p) for n, p in d_gb_planes.items()})
+        self.check(self.lib.mt_retexture_gbuffer_device(h, chunk_w, chunk_h, C.byref(g), stream))
 
     def set_traversal_mode(self, h, mode: int):
         self.check(self.lib.mt_scene_set_traversal_mode(h, mode))
@@ -749,6 +812,23 @@ class HipAbi:
         self.check(self.lib.mt_raytree_read_layer(tree, layer, C.byref(ls)))
         return out
 
+    def raytree_keeps_uvw(self, tree) -> bool:
+        """mt_raytree_keeps_uvw: was the tree made while the scene's set_raytree_uvw switch was on?"""
+        rc = self.lib.mt_raytree_keeps_uvw(tree)
+        if rc < 0:
+            self.check(rc)
+        return bool(rc)
+
+    def raytree_read_uvw(self, tree, layer) -> np.ndarray:
+        """mt_raytree_read_uvw: the layer's uvw plane, (n, 3) float64, NaN for a miss; a RuntimeError for a tree that
+        keeps none."""
+        info = self.raytree_info(tree)
+        if not 0 <= layer < info["n_layers"]:
+            raise ValueError("layer %d outside the tree's %d layers" % (layer, info["n_layers"]))
+        out = np.zeros((info["n_rays"][layer], 3), dtype=np.float64)
+        self.check(self.lib.mt_raytree_read_uvw(tree, layer, out.ctypes.data))
+        return out
+
     def raytree_shade(self, tree, lights) -> dict:
         """mt_raytree_shade under `lights` (n x 12; count and positions as when the tree was made): dict(rgb, stats)."""
         info = self.raytree_info(tree)
@@ -774,8 +854,8 @@ class HipAbi:
 
     def raytree_update_materials(self, tree) -> dict:
         """mt_raytree_update_materials after set_materials: `tree` brought to the scene's current materials, or a
-        RuntimeError (code -3: the edit changes the tree's shape or a textured material's ambient) with the tree as it
-        was.  Returns the stats dict."""
+        RuntimeError (code -3: the edit changes the tree's shape or, for a tree without uvw, a textured material's
+        ambient or a texture in use) with the tree as it was.  Returns the stats dict."""
         st = mt_stats()
         self.check(self.lib.mt_raytree_update_materials(tree, C.addressof(st)))
         return st.as_dict()
@@ -1019,6 +1099,9 @@ def host_lib():
     L.mth_update_materials.argtypes = [vp, cs, vp]
     L.mth_raytree_update_materials.argtypes = [vp, vp, vp, vp]
     L.mth_raytree_regrow.argtypes = [vp, vp, vp, vp]
+    L.mth_update_texture.argtypes = [vp, cs, ci, ci, vp]
+    L.mth_set_raytree_keep_uvw.argtypes = [vp, ci]
+    L.mth_set_raytree_keep_uvw.restype = None
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1321,6 +1404,25 @@ class MythTracer:
         for name, v in staged or [(None, None)]:
             if not self.L.mth_update_materials(self.h, name.encode() if name is not None else None, _ptr(v)):
                 raise RuntimeError("UpdateMaterials failed: " + self.last_error())
+
+    def update_texture(self, name, rgb=None):
+        """MythTracer::UpdateTexture: the texture with the scene's key `name` (add_texture's name, or the file name an
+        .mtl gave) replaced on every device replica by `rgb`, (height, width, 3) doubles -- size free to change --, or
+        by the scene's entry as it is when `rgb` is None.  RayTrees made before are stale until their
+        update_materials(), which takes the edit only for a tree built after set_raytree_keep_uvw(True)."""
+        a = None
+        w = hgt = 0
+        if rgb is not None:
+            a = _f64(rgb)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("rgb must be (height, width, 3)")
+            hgt, w = a.shape[0], a.shape[1]
+        if not self.L.mth_update_texture(self.h, name.encode(), w, hgt, _ptr(a)):
+            raise RuntimeError("UpdateTexture failed: " + self.last_error())
+
+    def set_raytree_keep_uvw(self, keep: bool):
+        """MythTracer::SetRayTreeKeepUVW: RayTrees built from now on keep each ray's texture coordinates."""
+        self.L.mth_set_raytree_keep_uvw(self.h, 1 if keep else 0)
 
     @property
     def num_materials(self):

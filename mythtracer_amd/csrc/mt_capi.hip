@@ -291,6 +291,11 @@ struct mt_scene {
   std::vector<mt_material> mtls_host;
   unsigned long long mtl_generation = 0;
   int n_textures = 0;
+  // mt_scene_set_texture: what dev.texs holds (the texels are device pointers: the scene keeps no host copy of them) and
+  // how often each texture has been set since mt_scene_create; mt_scene_set_raytree_uvw's switch
+  std::vector<DevTexture> texs_host;
+  std::vector<unsigned long long> tex_generation;
+  int raytree_uvw = 0;
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -1132,6 +1137,15 @@ void mt_scene_destroy(mt_scene *s) {
   delete s;
 }
 
+// a texture's size and format (mt_scene_create, mt_scene_set_texture)
+static int check_texture(const mt_texture &t, int i) {
+  if (t.width <= 0 || t.height <= 0 || t.width > 30000 || t.height > 30000 || !t.texels ||
+      (t.format != MT_TEX_RGB8 && t.format != MT_TEX_F64)) {
+    return fail(MT_ERR_ARG, "texture %d: bad size/format", i);
+  }
+  return MT_OK;
+}
+
 static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   if (d->struct_size != sizeof(mt_scene_desc) || d->abi_version != MT_ABI_VERSION) {
     return fail(MT_ERR_ARG, "mt_scene_desc size/version mismatch (%u/%u, want %zu/%d)",
@@ -1195,13 +1209,7 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
       return fail(MT_ERR_ARG, "material %d: texture index %d outside -1..%d", i, t, d->n_textures - 1);
     }
   }
-  for (int i = 0; i < d->n_textures; i++) {
-    const mt_texture &t = d->textures[i];
-    if (t.width <= 0 || t.height <= 0 || t.width > 30000 || t.height > 30000 || !t.texels ||
-        (t.format != MT_TEX_RGB8 && t.format != MT_TEX_F64)) {
-      return fail(MT_ERR_ARG, "texture %d: bad size/format", i);
-    }
-  }
+  for (int i = 0; i < d->n_textures; i++) MT_TRY(check_texture(d->textures[i], i));
   // --- is the min/max-instruction path admissible for this scene?
   bool regular = finite3(d->node_aabb, (size_t)nn * 6) && finite3(d->node_center, (size_t)nn * 3) &&
                  finite3(d->tri_aabb, (size_t)d->n_tris * 6);
@@ -1532,6 +1540,8 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
     texs[i] = DevTexture{dev_texels, t.width, t.height, t.format, 0};
   }
   if ((rc = upload(s, texs.data(), texs.size(), &s->dev.texs)) != MT_OK) return rc;
+  s->texs_host = texs;
+  s->tex_generation.assign(texs.size(), 0ull);
   s->dev.n_tris = d->n_tris;
   s->dev.n_nodes = nn;
   s->dev.tree_depth = max_depth;
@@ -1640,6 +1650,67 @@ int mt_scene_set_materials(mt_scene *s, const mt_material *materials, int n) {
 int mt_scene_get_materials(const mt_scene *s, mt_material *out, int n) {
   MT_TRY(check_materials_args(s, out, n));
   if (n > 0) memcpy(out, s->mtls_host.data(), (size_t)n * sizeof(mt_material));
+  return MT_OK;
+}
+
+// checked before any device call, in the order of the header
+static int check_texture_index(const mt_scene *s, int index) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (index < 0 || index >= s->n_textures) {
+    return fail(MT_ERR_ARG, "texture index %d outside 0..%d", index, s->n_textures - 1);
+  }
+  return MT_OK;
+}
+
+int mt_scene_set_texture(mt_scene *s, int index, const mt_texture *tex) {
+  MT_TRY(check_texture_index(s, index));
+  if (!tex) return fail(MT_ERR_ARG, "the mt_texture is NULL");
+  MT_TRY(check_texture(*tex, index));
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t bytes = (size_t)tex->width * (size_t)tex->height * (tex->format == MT_TEX_RGB8 ? 3 : 24);
+  // the new texels next to the old ones: until the entry is patched the scene is what it was
+  void *fresh = nullptr;
+  const hipError_t e = hipMalloc(&fresh, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of texture %d", bytes, index);
+    return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for texture %d failed: %s", bytes, index, hipGetErrorString(e));
+  }
+  const DevTexture entry{fresh, tex->width, tex->height, tex->format, 0};
+  DevTexture *slot = const_cast<DevTexture *>(s->dev.texs) + index;
+  // (hipDeviceSynchronize: no kernel of an earlier call reads the entry or the old texels while they change)
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(fresh, tex->texels, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(slot, &entry, sizeof entry, hipMemcpyHostToDevice) != hipSuccess) {
+    const hipError_t why = hipGetLastError();
+    (void)hipFree(fresh);
+    return fail(MT_ERR_HIP, "uploading texture %d failed: %s", index, hipGetErrorString(why));
+  }
+  void *old = const_cast<void *>(s->texs_host[(size_t)index].texels);
+  for (void *&a : s->allocs) {
+    if (a == old) a = fresh;  // (the scene's uploads are freed with it)
+  }
+  (void)hipFree(old);
+  s->texs_host[(size_t)index] = entry;
+  s->tex_generation[(size_t)index]++;
+  s->mtl_generation++;  // every ray tree of the scene is stale, as after a material edit
+  return MT_OK;
+}
+
+int mt_scene_get_texture_info(const mt_scene *s, int index, mt_texture *out) {
+  MT_TRY(check_texture_index(s, index));
+  if (!out) return fail(MT_ERR_ARG, "the mt_texture is NULL");
+  const DevTexture &t = s->texs_host[(size_t)index];
+  out->width = t.width;
+  out->height = t.height;
+  out->format = t.format;
+  out->texels = nullptr;  // (no host copy is kept)
+  return MT_OK;
+}
+
+int mt_scene_set_raytree_uvw(mt_scene *s, int keep) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (keep != 0 && keep != 1) return fail(MT_ERR_ARG, "keep must be 0 or 1");
+  s->raytree_uvw = keep;
   return MT_OK;
 }
 
@@ -2734,6 +2805,83 @@ int mt_update_lightbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffe
   return MT_OK;
 }
 
+// ---- edited textures and the deferred path (mt_gbuffer.h, gbuffer_retexture_kernel): stateless, like
+// mt_update_lightbuffer ----
+namespace {
+
+// mt_retexture_gbuffer[_device]: checked before any device call, in the order of the header.
+int check_retexture_args(const mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb) {
+  if (!gb) return fail(MT_ERR_ARG, "the mt_gbuffer is NULL");
+  if (!gb->material || !gb->albedo) {
+    return fail(MT_ERR_ARG, "the retexture needs the material and albedo planes of the mt_gbuffer");
+  }
+  if (!gb->uvw && s) {
+    for (size_t i = 0; i < s->mtls_host.size(); i++) {
+      if (s->mtls_host[i].tex >= 0) {
+        return fail(MT_ERR_ARG, "material %d has a texture: the retexture needs the uvw plane of the mt_gbuffer", (int)i);
+      }
+    }
+  }
+  if (chunk_w <= 0 || chunk_h <= 0 || chunk_w > 100000 || chunk_h > 100000) {
+    return fail(MT_ERR_ARG, "chunk size %dx%d out of range", chunk_w, chunk_h);
+  }
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  return MT_OK;
+}
+
+// gbuffer_retexture_kernel over the chunk's pixels; planes = device pointers
+int launch_gbuffer_retexture(mt_scene *s, size_t npx, const mt_gbuffer &d_gb, hipStream_t stream) {
+  GBufferRetextureArgs A{};
+  A.material = d_gb.material; A.uvw = d_gb.uvw; A.albedo = d_gb.albedo;
+  A.mtls = s->dev.mtls;
+  A.texs = s->dev.texs;
+  A.n = npx;
+  A.n_materials = s->n_materials;
+  hipLaunchKernelGGL(gbuffer_retexture_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, A);
+  HIP_TRY(hipGetLastError());
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_retexture_gbuffer_device(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *d_gb, void *stream) {
+  MT_TRY(check_retexture_args(s, chunk_w, chunk_h, d_gb));
+  HIP_TRY(hipSetDevice(s->device));
+  return launch_gbuffer_retexture(s, (size_t)chunk_w * (size_t)chunk_h, *d_gb, (hipStream_t)stream);
+}
+
+// The host form: material and uvw go up into the scene's G-buffer buffers, only the albedo comes back.
+int mt_retexture_gbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb, mt_stats *stats) {
+  MT_TRY(check_retexture_args(s, chunk_w, chunk_h, gb));
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
+  hipStream_t stream = nullptr;
+  MT_TRY(s->d_gb_i32[2].ensure(npx * 4));
+  MT_TRY(s->d_gb_f64[4].ensure(npx * 24));
+  mt_gbuffer d{};
+  d.material = s->d_gb_i32[2]; d.albedo = s->d_gb_f64[4];
+  HIP_TRY(hipMemcpyAsync(d.material, gb->material, npx * 4, hipMemcpyHostToDevice, stream));
+  if (gb->uvw) {
+    MT_TRY(s->d_gb_f64[3].ensure(npx * 24));
+    d.uvw = s->d_gb_f64[3];
+    HIP_TRY(hipMemcpyAsync(d.uvw, gb->uvw, npx * 24, hipMemcpyHostToDevice, stream));
+  }
+  HIP_TRY(hipEventRecord(s->ev0, stream));
+  MT_TRY(launch_gbuffer_retexture(s, npx, d, stream));
+  HIP_TRY(hipEventRecord(s->ev1, stream));
+  HIP_TRY(hipMemcpyAsync(gb->albedo, d.albedo, npx * 24, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (stats) {  // (no ray, no traversal: every work counter is zero)
+    memset(stats, 0, sizeof *stats);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  }
+  return MT_OK;
+}
+
 // ---- the ray-tree buffer (mt_raytree.h).  Like the G-buffer and light-buffer calls, nothing here reads or writes what
 // decide_launch looks at. ----
 struct mt_raytree {
@@ -2751,6 +2899,10 @@ struct mt_raytree {
   // byte per material (first use)
   std::vector<mt_material> mtls;
   unsigned long long mtl_generation = 0;
+  // the scene's generation of every texture then (mt_scene_set_texture), and whether the layers have a uvw plane: the
+  // scene's mt_scene_set_raytree_uvw switch when the tree was made
+  std::vector<unsigned long long> tex_generation;
+  bool keep_uvw = false;
   unsigned long long *d_mismatch = nullptr;
   uint8_t *d_albedo_changed = nullptr;
   // mt_raytree_regrow_materials (first use, grown when a call needs more): `src` of the new layers k and k + 1 in turn,
@@ -2775,8 +2927,9 @@ int raytree_malloc(void **p, size_t bytes, const char *what) {
 }
 
 // One allocation holds a layer's planes, each at a multiple of 256 bytes: the planes of layer k with n rays and n_l
-// lights laid out from `base` (nullptr: only the size is wanted).  Returns the bytes.
-size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, RayTreeLayer *out) {
+// lights laid out from `base` (nullptr: only the size is wanted).  Returns the bytes.  The uvw plane of a tree that
+// keeps one comes last, [n][3] doubles at a multiple of 256 bytes: without it a layer is laid out as it always was.
+size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, bool keep_uvw, RayTreeLayer *out) {
   struct Part { void **at; size_t bytes; };
   RayTreeLayer &L = *out;
   const Part parts[] = {
@@ -2791,17 +2944,20 @@ size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, RayTreeLayer
     at += (p.bytes + 255) & ~(size_t)255;
   }
   if (k != 0) L.pixel = nullptr;
+  // (behind the last padded plane, itself unpadded: the layer grows by exactly 24 bytes per ray)
+  L.uvw = keep_uvw && base != nullptr ? (double *)((char *)base + at) : nullptr;
+  if (keep_uvw) at += n * 24;
   return at;
 }
 
 int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
   const size_t n_l = (size_t)t->info.n_lights;
   RayTreeLayer &L = t->layer[k];
-  const size_t total = raytree_carve_layer(nullptr, n_l, k, n, &L);
+  const size_t total = raytree_carve_layer(nullptr, n_l, k, n, t->keep_uvw, &L);
   char what[64];
   snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
   MT_TRY(raytree_malloc(&t->alloc[k], total, what));
-  (void)raytree_carve_layer(t->alloc[k], n_l, k, n, &L);
+  (void)raytree_carve_layer(t->alloc[k], n_l, k, n, t->keep_uvw, &L);
   t->info.bytes += total;
   t->info.n_rays[k] = (int64_t)n;
   t->info.n_layers = k + 1;
@@ -3066,6 +3222,7 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
   }
   t->mtls = s->mtls_host;
   t->mtl_generation = s->mtl_generation;
+  t->tex_generation = s->tex_generation;
   if (stats) {
     memset(stats, 0, sizeof *stats);
     fill_stats(s->h_counters, stats);
@@ -3159,6 +3316,7 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
   }
   mt_raytree *t = new mt_raytree();
   t->scene = s;
+  t->keep_uvw = s->raytree_uvw != 0;
   t->sensor = *sensor;
   t->info.n_lights = s->dev.n_lights;
   t->info.image_w = image_w; t->info.image_h = image_h;
@@ -3187,6 +3345,7 @@ int raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_
   if (hipSetDevice(s->device) != hipSuccess) return fail(MT_ERR_HIP, "hipSetDevice(%d) failed", s->device);
   mt_raytree *t = new mt_raytree();
   t->scene = s;
+  t->keep_uvw = s->raytree_uvw != 0;
   t->info.n_lights = s->dev.n_lights;
   t->info.image_w = t->info.chunk_w = rays->list_w;
   t->info.image_h = t->info.chunk_h = rays->list_h;
@@ -3244,6 +3403,26 @@ int mt_raytree_read_layer(mt_raytree *t, int layer, const mt_raytree_layer *out)
   for (const PlaneCopy &c : copies) {
     if (c.host != nullptr && c.bytes > 0) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
   }
+  return MT_OK;
+}
+
+int mt_raytree_keeps_uvw(const mt_raytree *t) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  return t->keep_uvw ? 1 : 0;
+}
+
+int mt_raytree_read_uvw(mt_raytree *t, int layer, double *out_uvw) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (layer < 0 || layer >= t->info.n_layers) {
+    return fail(MT_ERR_ARG, "layer %d outside the ray tree's %d layers", layer, t->info.n_layers);
+  }
+  if (!out_uvw) return fail(MT_ERR_ARG, "the uvw output is NULL");
+  if (!t->keep_uvw) {
+    return fail(MT_ERR_ARG, "the ray tree keeps no uvw: it was made with mt_scene_set_raytree_uvw at 0");
+  }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  const size_t n = (size_t)t->info.n_rays[layer];
+  if (n > 0) HIP_TRY(hipMemcpy(out_uvw, t->layer[layer].uvw, n * 24, hipMemcpyDeviceToHost));
   return MT_OK;
 }
 
@@ -3474,11 +3653,11 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     }
     const size_t n1 = (size_t)children;
     n_new[k + 1] = n1;
-    const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, &NL[k + 1]);
+    const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, t->keep_uvw, &NL[k + 1]);
     char what[64];
     snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k + 1, n1);
     if (const int rc = raytree_malloc(&alloc[k + 1], total, what)) return release(rc);
-    (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, &NL[k + 1]);
+    (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, t->keep_uvw, &NL[k + 1]);
     const int to = (k + 1) & 1;
     if (const int rc = raytree_scratch((void **)&t->d_src[to], &t->src_cap[to], n1 * 4, "the ray tree's regrow indices")) {
       return release(rc);
@@ -3507,6 +3686,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.n_lights = I.n_lights;
       A.n_materials = n_mtl;
       A.mtls = s->dev.mtls;
+      A.texs = s->dev.texs;
       A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
       hipLaunchKernelGGL(raytree_regrow_copy_kernel, grid_of(n1), dim3(256), 0, stream, A);
       if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
@@ -3525,11 +3705,11 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     n_traced[k + 1] = m;
     if (m == 0) continue;
     RayTreeRegrowListArgs A{};
-    const size_t tmp_bytes = raytree_carve_layer(nullptr, n_l, k + 1, m, &A.tmp);
+    const size_t tmp_bytes = raytree_carve_layer(nullptr, n_l, k + 1, m, t->keep_uvw, &A.tmp);
     if (const int rc = raytree_scratch(&t->d_tmp, &t->tmp_cap, tmp_bytes, "the ray tree's list of traced rays")) {
       return release(rc);
     }
-    (void)raytree_carve_layer(t->d_tmp, n_l, k + 1, m, &A.tmp);
+    (void)raytree_carve_layer(t->d_tmp, n_l, k + 1, m, t->keep_uvw, &A.tmp);
     A.L = NL[k + 1];
     A.n_rays = (uint32_t)n1;
     A.n_list = (uint32_t)m;
@@ -3551,6 +3731,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     RayTreeRecommitArgs A{};
     A.L = t->layer[0];
     A.mtls = s->dev.mtls;
+    A.texs = s->dev.texs;
     A.albedo_changed = t->d_albedo_changed;
     A.n_rays = (uint32_t)n0;
     A.n_materials = n_mtl;
@@ -3572,13 +3753,13 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   RayTreeLayer none{};
   for (int k = 1; k <= MT_MAX_RECURSION; k++) {
     if (t->alloc[k]) {
-      I.bytes -= raytree_carve_layer(nullptr, n_l, k, (size_t)I.n_rays[k], &none);
+      I.bytes -= raytree_carve_layer(nullptr, n_l, k, (size_t)I.n_rays[k], t->keep_uvw, &none);
       (void)hipFree(t->alloc[k]);
     }
     t->alloc[k] = alloc[k];
     t->layer[k] = NL[k];
     I.n_rays[k] = (int64_t)n_new[k];
-    if (alloc[k]) I.bytes += raytree_carve_layer(nullptr, n_l, k, n_new[k], &none);
+    if (alloc[k]) I.bytes += raytree_carve_layer(nullptr, n_l, k, n_new[k], t->keep_uvw, &none);
   }
   I.n_layers = new_layers;
   for (int k = 0; k <= MT_MAX_RECURSION; k++) {
@@ -3604,9 +3785,21 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
   if (t->mtl_generation == s->mtl_generation) return MT_OK;
   MaterialDiff D;
   diff_materials(t->mtls, s->mtls_host, &D);
-  if (D.textured >= 0) {
+  if (D.textured >= 0 && !t->keep_uvw) {
     return fail(MT_ERR_UNSUPPORTED, "material %d has a texture and its ambient or tex changed: the ray tree keeps neither "
                                     "the texel nor the primitive, a new tree is needed", D.textured);
+  }
+  // a texture set since the snapshot: the materials that use it NOW are retextured (one that used it and left it has a
+  // changed `tex`: diff_materials has it; one that no material uses is nothing to do)
+  for (size_t i = 0; i < s->mtls_host.size(); i++) {
+    const int tex = s->mtls_host[i].tex;
+    if (tex < 0 || t->tex_generation[(size_t)tex] == s->tex_generation[(size_t)tex]) continue;
+    if (!t->keep_uvw) {
+      return fail(MT_ERR_UNSUPPORTED, "texture %d was set after the ray tree was made and material %d uses it: the ray "
+                                      "tree keeps no uvw (mt_scene_set_raytree_uvw), a new tree is needed", tex, (int)i);
+    }
+    D.albedo = true;
+    D.albedo_changed[i] = 1;
   }
   const bool retrace = D.shadow && I.n_lights > 0;
   // (a regrow may trace new rays, whose light planes come from the scene's current lights)
@@ -3675,6 +3868,7 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
         RayTreeRecommitArgs A{};
         A.L = t->layer[k];
         A.mtls = s->dev.mtls;
+        A.texs = s->dev.texs;
         A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
         A.n_rays = (uint32_t)n;
         A.n_materials = n_mtl;
@@ -3720,6 +3914,7 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
   }
   t->mtls = s->mtls_host;
   t->mtl_generation = s->mtl_generation;
+  t->tex_generation = s->tex_generation;
   if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   return MT_OK;
 }

@@ -145,6 +145,44 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void gbuffer_kernel(DevScen
   }
 }
 
+// ---- edited textures (include/mythtracer_hip.h, mt_scene_set_texture ff.) ----
+// A texture touches exactly one stored quantity, the albedo, and that is arithmetic over a stored uvw: the rule of
+// write_gbuffer_planes above (mythtracer.cc:58-64), the same expressions in the same order, from memory instead of from
+// the trace.  Shared by gbuffer_retexture_kernel, raytree_recommit_kernel and raytree_regrow_copy_kernel
+// (mt_raytree.h).  `uvw` may be nullptr where no material the caller lets through has a texture.
+__device__ __forceinline__ V3 retextured_albedo(const mt_material *m, const DevTexture *texs, const double *uvw, size_t i) {
+  V3 surf = v3(m->ambient[0], m->ambient[1], m->ambient[2]);
+  if (m->tex >= 0 && uvw != nullptr) {
+    const V3 c = v3_load(uvw + i * 3);
+    surf = surf * texture_color_at(texs[m->tex], c.x, c.y);
+  }
+  return surf;
+}
+
+// gbuffer_retexture_kernel: the albedo plane of a stored G-buffer again under the scene's CURRENT materials and
+// textures, from its material and uvw planes -- no sensor, no traversal, a plain grid, one thread per pixel.  A material
+// outside 0 .. n_materials - 1 (a miss, "no material", or anything else a caller's plane may hold) gets NaN, what
+// write_gbuffer_planes stores for a miss.
+struct GBufferRetextureArgs {
+  const int32_t *material;  // [n]
+  const double *uvw;        // [n][3]; nullptr: no current material has a texture
+  double *albedo;           // [n][3]
+  const mt_material *mtls;
+  const DevTexture *texs;
+  unsigned long long n;
+  int32_t n_materials;
+};
+
+__global__ __launch_bounds__(256) void gbuffer_retexture_kernel(GBufferRetextureArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n) return;
+  const int mtl = A.material[i];
+  const double nan = __builtin_nan("");
+  V3 surf = v3(nan, nan, nan);
+  if (mtl >= 0 && mtl < A.n_materials) surf = retextured_albedo(A.mtls + mtl, A.texs, A.uvw, i);
+  store3(A.albedo, i, surf);
+}
+
 #define MT_INSTANTIATE_GB(DEEP_)                                                    \
   template __global__ void gbuffer_kernel<true, DEEP_>(DevScene, GBufferArgs);      \
   template __global__ void gbuffer_kernel<false, DEEP_>(DevScene, GBufferArgs);

@@ -8,7 +8,8 @@
 // parent's reflected ray before its refracted one.  Per ray: origin and direction as handed to IntersectRay, in_object,
 // coef, the G-buffer planes point / normal (unflipped) / albedo / material, per light power and in_shadow
 // (mt_lightbuffer.h's meaning, planes [n_lights][n_rays]), the two child indices into the next layer (-1 = none), and
-// in layer 0 the chunk-local pixel index.
+// in layer 0 the chunk-local pixel index.  A tree made while mt_scene_set_raytree_uvw is on also keeps the G-buffer
+// plane uvw: the one thing a texture edit needs to restate the albedo without tracing a ray.
 //
 //   raytree_primary_kernel  layer 0's ray list from the sensor, in raytree_layer0_index's order (8x8 blocks of the
 //                           chunk, row-major; a block clipped by the chunk's edge holds only its pixels, row-major:
@@ -47,6 +48,7 @@ struct RayTreeLayer {
   uint8_t *in_object;  // [n]
   uint8_t *in_shadow;  // [n_lights][n]
   uint8_t *spawn;      // [n] bit 0: a reflected child, bit 1: a refracted child
+  double *uvw;         // [n][3] Triangle::GetUVW(point), NaN on a miss; nullptr: the tree keeps none (mt_scene_set_raytree_uvw)
 };
 
 // index of chunk pixel (x, y) in layer 0's list
@@ -104,6 +106,7 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void raytree_trace_kernel(D
   st.clear();
   GBufferPlanes planes{};
   planes.point = A.L.point; planes.normal = A.L.normal; planes.albedo = A.L.albedo; planes.material = A.L.material;
+  planes.uvw = A.L.uvw;  // (nullable, wave-uniform: write_gbuffer_planes computes it exactly as for the textured albedo)
   const size_t n = (size_t)A.n_rays;
   // every iteration of a shadow loop crosses another surface
   const int iteration_bound = S.n_tris + 2;
@@ -603,7 +606,9 @@ __global__ __launch_bounds__(256) void raytree_color_kernel(const double *color,
 // raytree_recommit_kernel  the COMMIT, one launch per layer that has something to take: coef[i] = the scratch's
 //                          coefficient (copy_coef: layers >= 1 after a clean check), and albedo[i] = the new ambient for
 //                          the rays whose material's byte in `albedo_changed` is set -- what write_gbuffer_planes
-//                          stores for an untextured material, no arithmetic.
+//                          stores for an untextured material, no arithmetic; times the texel at the ray's stored uvw
+//                          where the material has a texture (retextured_albedo, mt_gbuffer.h: a tree that keeps uvw;
+//                          the host lets no textured material's byte through for a tree that does not).
 struct RayTreeRecoefArgs {
   RayTreeLayer L;
   double *child_scratch;         // the next layer's color plane, nullptr: there is no next layer
@@ -648,6 +653,7 @@ __global__ __launch_bounds__(256) void raytree_recoef_kernel(RayTreeRecoefArgs A
 struct RayTreeRecommitArgs {
   RayTreeLayer L;
   const mt_material *mtls;        // the scene's CURRENT materials
+  const DevTexture *texs;         // and its CURRENT textures
   const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
   uint32_t n_rays;
   int32_t n_materials;
@@ -661,8 +667,7 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
   if (A.albedo_changed != nullptr) {
     const int mtl = A.L.material[i];
     if (mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
-      const mt_material *m = A.mtls + mtl;
-      store3(A.L.albedo, i, v3(m->ambient[0], m->ambient[1], m->ambient[2]));
+      store3(A.L.albedo, i, retextured_albedo(A.mtls + mtl, A.texs, A.L.uvw, i));
     }
   }
 }
@@ -689,11 +694,13 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
 //                                  places live in child_refl until layer k + 1's own compaction overwrites them.
 //   raytree_regrow_copy_kernel     one thread per kept ray of layer k + 1, by the destination index: ray, in_object,
 //                                  point, normal, material, every light's power and in_shadow from the old layer at
-//                                  src; albedo too, or the new ambient where the material's byte in albedo_changed is
-//                                  set (raytree_recommit_kernel's rule).
+//                                  src; uvw too where the tree keeps it; albedo too, or the new ambient (times the texel
+//                                  at the OLD layer's uvw at src) where the material's byte in albedo_changed is set
+//                                  (raytree_recommit_kernel's rule).
 //   raytree_regrow_gather_kernel   ray, coef and in_object of the traced rays to their places in the temporary layer;
 //   (raytree_trace_kernel)         over the temporary layer, secondary = 1, may_spawn = (k + 1 < max_depth);
-//   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow and spawn back to the new layer.
+//   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow, spawn and (where kept) uvw back to
+//                                  the new layer.
 // That regrouping the traced rays changes no bit is the ray-list contract: layer k handed in as an n x 1 list gives the
 // tree's layers k onwards.  None of these kernels writes a plane of the OLD tree.
 struct RayTreeRegrowFlagsArgs {
@@ -778,6 +785,7 @@ struct RayTreeRegrowCopyArgs {
   int32_t n_lights;
   int32_t n_materials;
   const mt_material *mtls;        // the scene's CURRENT materials
+  const DevTexture *texs;         // and its CURRENT textures
   const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
 };
 
@@ -794,9 +802,9 @@ __global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowC
   store3(A.to.normal, j, v3_load(A.from.normal + s * 3));
   const int mtl = A.from.material[s];
   A.to.material[j] = mtl;
+  if (A.to.uvw != nullptr) store3(A.to.uvw, j, v3_load(A.from.uvw + s * 3));
   if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
-    const mt_material *m = A.mtls + mtl;
-    store3(A.to.albedo, j, v3(m->ambient[0], m->ambient[1], m->ambient[2]));
+    store3(A.to.albedo, j, retextured_albedo(A.mtls + mtl, A.texs, A.from.uvw, s));
   } else {
     store3(A.to.albedo, j, v3_load(A.from.albedo + s * 3));
   }
@@ -835,6 +843,7 @@ __global__ __launch_bounds__(256) void raytree_regrow_scatter_kernel(RayTreeRegr
   store3(A.L.normal, j, v3_load(A.tmp.normal + p * 3));
   store3(A.L.albedo, j, v3_load(A.tmp.albedo + p * 3));
   A.L.material[j] = A.tmp.material[p];
+  if (A.L.uvw != nullptr) store3(A.L.uvw, j, v3_load(A.tmp.uvw + p * 3));
   for (int li = 0; li < A.n_lights; li++) {
     store3(A.L.power, (size_t)li * n + j, v3_load(A.tmp.power + ((size_t)li * m + p) * 3));
     A.L.in_shadow[(size_t)li * n + j] = A.tmp.in_shadow[(size_t)li * m + p];

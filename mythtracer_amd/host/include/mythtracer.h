@@ -212,17 +212,31 @@ class MythTracer {
   // call edits, it neither adds nor removes) or a material points at a texture that was not uploaded.  Before the
   // first upload it is Prepare.  RayTrees built before the edit are stale until UpdateRayTreeMaterials.
   bool UpdateMaterials();
+  // After a texture was EDITED in place in GetScene()->textures[key] (its colors, width and height; the Texture object
+  // itself stays, materials point at it): replaces the uploaded texture on every device replica by the entry as it now
+  // is (mt_scene_set_texture), size and format free to change, without uploading a triangle again.  `key` is the
+  // texture table's key.  Refused with a message when the table has no such key, when that texture was not uploaded (no
+  // material of a triangle used it at the upload: the call edits, it neither adds nor removes) or when its size and
+  // colours disagree.  Before the first upload it is Prepare.  RayTrees built before the edit are stale until
+  // UpdateRayTreeMaterials, which needs a tree that keeps uvw for it (SetRayTreeKeepUVW).
+  bool UpdateTexture(const std::string& key);
+  // RayTrees built from now on also keep each ray's texture coordinates (mt_scene_set_raytree_uvw): 24 bytes more per
+  // ray, and UpdateRayTreeMaterials / RegrowRayTree then take texture edits and ambient or texture changes of textured
+  // materials, which they refuse for a tree without.  Off by default.
+  void SetRayTreeKeepUVW(bool keep);
   // Brings `tree` to the materials of the last UpdateMaterials without tracing a primary or secondary ray
   // (mt_raytree_update_materials): new albedo and coefficients, and the light planes again where a shadow ray can see
   // the edit (under GetScene()->lights).  Fails, with the tree exactly as it was, when the edit changes which rays
-  // spawn children or touches the ambient of a textured material: a new BuildRayTree is needed then.  Refused with
+  // spawn children, or -- for a tree built without SetRayTreeKeepUVW -- touches the ambient of a textured material or a
+  // texture in use: a new BuildRayTree is needed then.  Refused with
   // several devices, like BuildRayTree, and for a NULL or empty RayTree.  LastStats() describes the call.
   bool UpdateRayTreeMaterials(RayTree* tree);
   // The same after an edit that changes which rays spawn children -- a matte surface made reflective, a mirror switched
   // off, a pane made opaque (mt_raytree_regrow_materials): the rays whose path survives are kept, the dead subtrees
   // dropped and only the new rays traced, under GetScene()->lights; Layers() and Rays() follow.  The tree is then what a
   // new BuildRayTree gives, and ShadeRayTree gives RayTrace's frame.  Where the shape survives the call is
-  // UpdateRayTreeMaterials.  Still fails for the ambient of a textured material.  Refused with several devices and for a
+  // UpdateRayTreeMaterials.  Still fails for the ambient of a textured material or an edited texture when the tree
+  // was built without SetRayTreeKeepUVW.  Refused with several devices and for a
   // NULL or empty RayTree.  LastStats() describes the call (rays_secondary = the rays traced).
   bool RegrowRayTree(RayTree* tree);
   // The caller's rays instead of a camera's (mt_raytree_create_rays): TraceRay for a ray list, to the recursion level of
@@ -264,6 +278,7 @@ class MythTracer {
   void DropDeviceScenes();
   std::vector<std::string> uploaded_names_, dense_names_;  // UpdateMaterials: all names at the upload; the dense table's
   std::vector<const Texture*> uploaded_textures_;          // ... and the texture table's sources
+  bool keep_uvw_ = false;                                  // SetRayTreeKeepUVW
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
   int adaptive_ss_ = 1, adaptive_threshold_ = 16;

@@ -565,6 +565,38 @@ int mth_update_materials(void* p, const char* name, const double* values16) {
   return h->mt.UpdateMaterials() ? 1 : 0;
 }
 
+// MythTracer::UpdateTexture after an edit of one texture by its key: w x hgt colours in rgb (NULL = no edit, only the
+// update).  The Texture object is edited in place, so the materials that point at it keep doing so.  0 with the facade's
+// message when it refuses; an unknown key is the shim's.
+int mth_update_texture(void* p, const char* name, int w, int hgt, const double* rgb) {
+  Handle* h = static_cast<Handle*>(p);
+  if (name == nullptr) {
+    h->shim_error = "the texture key is NULL";
+    return 0;
+  }
+  if (rgb != nullptr) {
+    auto& texs = h->mt.GetScene()->textures;
+    auto it = texs.find(name);
+    if (it == texs.end()) {
+      h->shim_error = std::string("no texture named ") + name;
+      return 0;
+    }
+    if (w < 1 || hgt < 1) {
+      h->shim_error = "texture size out of range";
+      return 0;
+    }
+    Texture& t = *it->second;
+    t.width = (size_t)w;
+    t.height = (size_t)hgt;
+    t.colors.resize((size_t)w * hgt);
+    for (size_t i = 0; i < t.colors.size(); i++) t.colors[i] = {rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]};
+  }
+  return h->mt.UpdateTexture(name) ? 1 : 0;
+}
+
+// MythTracer::SetRayTreeKeepUVW
+void mth_set_raytree_keep_uvw(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepUVW(keep != 0); }
+
 // MythTracer::UpdateRayTreeMaterials; stats8 / ms2 as mth_raytree_update fills them
 int mth_raytree_update_materials(void* p, void* t, uint64_t* stats8, double* ms2) {
   Handle* h = static_cast<Handle*>(p);

@@ -204,6 +204,7 @@ bool MythTracer::Prepare() {
       DropDeviceScenes();
       return false;
     }
+    (void)mt_scene_set_raytree_uvw(s, keep_uvw_ ? 1 : 0);
     if (r == 0) dev_ = s;
     else replicas_.push_back(s);
   }
@@ -255,6 +256,52 @@ bool MythTracer::UpdateMaterials() {
     }
   }
   return true;
+}
+
+bool MythTracer::UpdateTexture(const std::string& key) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes it as it is
+  const auto it = scene.textures.find(key);
+  if (it == scene.textures.end()) return refuse("the scene has no texture " + key);
+  const Texture& t = *it->second;
+  int index = -1;
+  for (size_t k = 0; k < uploaded_textures_.size(); k++) {
+    if (uploaded_textures_[k] == &t) index = (int)k;
+  }
+  if (index < 0) return refuse("texture " + key + " was not uploaded: UpdateTexture edits, it neither adds nor removes");
+  if (t.colors.size() != t.width * t.height || t.width == 0 || t.height == 0) {
+    return refuse("texture with inconsistent size");
+  }
+  // FlatScene::Build's choice of format
+  mt_texture o{};
+  o.width = (int32_t)t.width;
+  o.height = (int32_t)t.height;
+  std::vector<uint8_t> rgb8;
+  if (PackRgb8(t, &rgb8)) {
+    o.format = MT_TEX_RGB8;
+    o.texels = rgb8.data();
+  } else {
+    o.format = MT_TEX_F64;
+    o.texels = t.colors.data();  // V3D is three packed doubles
+  }
+  std::vector<mt_scene*> all(1, dev_);
+  all.insert(all.end(), replicas_.begin(), replicas_.end());
+  for (mt_scene* s : all) {
+    if (mt_scene_set_texture(s, index, &o) != MT_OK) {
+      return refuse(std::string("texture update failed: ") + mt_last_error());
+    }
+  }
+  return true;
+}
+
+void MythTracer::SetRayTreeKeepUVW(bool keep) {
+  keep_uvw_ = keep;
+  if (dev_ != nullptr) (void)mt_scene_set_raytree_uvw(dev_, keep ? 1 : 0);
+  for (mt_scene* s : replicas_) (void)mt_scene_set_raytree_uvw(s, keep ? 1 : 0);
 }
 
 bool MythTracer::UpdateRayTreeMaterials(RayTree* tree) {

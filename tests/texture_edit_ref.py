@@ -1,0 +1,220 @@
+"""The texture edits of the edit-in-place tests (mt_scene_set_texture, ray trees that keep uvw, mt_retexture_gbuffer):
+the numpy restatement of albedo = ambient * Texture::GetColorAt(u, v), the replacement textures, the tiny scene and the
+synthetic G-buffer planes -- shared by tests/test_texture_edit_cpu.py, which pins the restatement to the oracle, and
+tests/test_gpu_texture_edit.py.  Test infrastructure.
+
+`color_at` restates texture_color_at of mythtracer_amd/csrc/mt_shade.h expression by expression (Texture::GetColorAt,
+texture.cc:11-58): fmod(u, 1), + 1 where negative, v = 1 - v, x = u (w - 1), y = v (h - 1), the four texels around
+(x, y) with the neighbour clamped in the last column and row, the bilinear weights from fmod(x, 1) and fmod(y, 1), the
+sum in the order t0 a0 + t1 a1 + t2 a2 + t3 a3.  numpy's float64 arithmetic is IEEE and contracts nothing, so the
+restatement is held to the oracle's bits.  NaN coordinates give a NaN colour (the kernels' definition); infinite
+coordinates are left out everywhere (the conversion of NaN to an integer is undefined in C++).
+"""
+import numpy as np
+
+NAN = float("nan")
+
+
+def texel_values(texels):
+    """A texture as the kernels read it: (h, w, 3) float64; uint8 texels are byte / 255.0 (texture.cc:100-104)."""
+    t = np.asarray(texels)
+    if t.dtype == np.uint8:
+        return t.astype(np.float64) / 255.0
+    return np.ascontiguousarray(t, dtype=np.float64)
+
+
+def color_at(texels, u, v):
+    """texture_color_at for arrays u, v (n,): (n, 3) float64."""
+    t = texel_values(texels)
+    h, w = t.shape[0], t.shape[1]
+    flat = t.reshape(h * w, 3)
+    u = np.array(u, dtype=np.float64).reshape(-1)
+    v = np.array(v, dtype=np.float64).reshape(-1)
+    nan = np.isnan(u) | np.isnan(v)
+    assert not (np.isinf(u) | np.isinf(v)).any(), "infinite texture coordinates are undefined"
+    u = np.where(nan, 0.0, u)
+    v = np.where(nan, 0.0, v)
+    u = np.fmod(u, 1.0)
+    v = np.fmod(v, 1.0)
+    u = np.where(u < 0.0, u + 1.0, u)
+    v = np.where(v < 0.0, v + 1.0, v)
+    v = 1.0 - v
+    x = u * float(w - 1)
+    y = v * float(h - 1)
+    bx = x.astype(np.uint64)  # (size_t)x: x >= 0, truncation
+    by = y.astype(np.uint64)
+    x1 = np.where(bx + np.uint64(1) == np.uint64(w), bx, bx + np.uint64(1))
+    y1 = np.where(by + np.uint64(1) == np.uint64(h), by, by + np.uint64(1))
+    W = np.uint64(w)
+    idx = [bx + by * W, x1 + by * W, bx + y1 * W, x1 + y1 * W]
+    outside = np.zeros(len(u), dtype=bool)
+    for i in idx:
+        outside |= i >= np.uint64(w * h)
+    dx = np.fmod(x, 1.0)
+    dy = np.fmod(y, 1.0)
+    area = [(1.0 - dx) * (1.0 - dy), dx * (1.0 - dy), (1.0 - dx) * dy, dx * dy]
+    c = [flat[np.where(outside, 0, i).astype(np.int64)] for i in idx]
+    out = c[0] * area[0][:, None] + c[1] * area[1][:, None] + c[2] * area[2][:, None] + c[3] * area[3][:, None]
+    out[nan | outside] = NAN
+    return out
+
+
+def albedo(materials, textures, material, uvw):
+    """What mt_render_gbuffer stores in albedo, and mt_retexture_gbuffer restores: `materials` as flat["materials"]
+    (dict(values = ka kd ks ns refl tr tf ni, tex)), `textures` a list of texel arrays, `material` (n,) int32, `uvw`
+    (n, 3) or None.  NaN where material is outside 0 .. n_materials - 1; ambient, times the texel where tex >= 0."""
+    material = np.asarray(material, dtype=np.int32).reshape(-1)
+    out = np.full((len(material), 3), NAN)
+    for i, m in enumerate(materials):
+        sel = material == i
+        if not sel.any():
+            continue
+        surf = np.tile(np.asarray(m["values"], dtype=np.float64)[:3], (int(sel.sum()), 1))
+        if m["tex"] >= 0:
+            c = np.asarray(uvw, dtype=np.float64).reshape(-1, 3)[sel]
+            surf = surf * color_at(textures[m["tex"]], c[:, 0], c[:, 1])
+        out[sel] = surf
+    return out
+
+
+def splitmix(seed):
+    """A deterministic stream of doubles in [0, 1) (SplitMix64, as mythtracer_amd.scenegen's)."""
+    state = [seed & 0xFFFFFFFFFFFFFFFF]
+
+    def unit():
+        state[0] = (state[0] + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        z = state[0]
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+        z ^= z >> 31
+        return (z >> 11) / float(1 << 53)
+    return unit
+
+
+def replacements(original):
+    """The textures that replace `original` (a texel array): 1 x 1, 2 x 2, 3 x 5 float64 (width 3, height 5: not
+    square, another format, and with few texels the last-row and last-column clamp of x1 / y1 is hit), and the original
+    bytes again."""
+    r = splitmix(0x7e87)
+    f64 = np.array([[[0.05 + 0.9 * r() for _ in range(3)] for _ in range(3)] for _ in range(5)], dtype=np.float64)
+    f64[2, 1] = (1.25, 0.0, 0.3333333333333333)  # (not a byte / 255: the format cannot be RGB8)
+    return {
+        "1x1": np.array([[[200, 100, 50]]], dtype=np.uint8),
+        "2x2": np.array([[[255, 0, 0], [0, 255, 0]], [[0, 0, 255], [255, 255, 64]]], dtype=np.uint8),
+        "3x5_f64": f64,
+        "original": np.array(original, copy=True),
+    }
+
+
+def edge_uv(n_random=300, seed=0x51de):
+    """(u, v) pairs for the pin: the edges -- exactly 0 and 1, negative, outside [0, 1), tiny negatives that round to 1
+    after + 1, huge values, -0.0, NaN -- crossed with each other, then random ones in [-3, 3)."""
+    edges = [0.0, -0.0, 1.0, -1.0, 0.5, 0.25, 0.999999999, 1.0 - 2.0 ** -53, -2.0 ** -60, 2.0 ** -60, 1.5, -0.75, 7.0, -7.0,
+             123456.789, -98765.4321, 1e300, -1e300, NAN]
+    uv = [(a, b) for a in edges for b in edges]
+    r = splitmix(seed)
+    uv += [(6.0 * r() - 3.0, 6.0 * r() - 3.0) for _ in range(n_random)]
+    a = np.array(uv, dtype=np.float64)
+    return a[:, 0].copy(), a[:, 1].copy()
+
+
+# ---- the tiny scene: one textured quad (the floor), a second textured quad (the left wall), one untextured mirror, one
+# pane, an untextured matte wall, a triangle whose uvw is NaN and a zero-area triangle
+
+TINY_CAMERA = (5.0, 5.0, -4.0, 20.0, 0.0, 0.0, 100.0)
+TINY_IMAGE = (48, 32)
+TINY_DEPTH = 3
+TINY_LIGHTS = [(5.0, 9.0, 2.0, 0.1, 0.1, 0.1, 0.8, 0.8, 0.8, 0.5, 0.5, 0.5),
+               (1.0, 6.0, -3.0, 0.05, 0.1, 0.02, 0.5, 0.4, 0.6, 0.3, 0.5, 0.2)]
+# name: (ka, kd, ks, ns, refl, tr, tf)
+TINY_MATERIALS = [
+    ("floor", (0.9, 0.8, 0.7), (0.7, 0.7, 0.7), (0.2, 0.2, 0.2), 8.0, 0.25, 0.0, (0.0, 0.0, 0.0)),
+    ("wall", (0.6, 0.9, 0.5), (0.6, 0.6, 0.6), (0.1, 0.1, 0.1), 4.0, 0.0, 0.0, (0.0, 0.0, 0.0)),
+    ("mirror", (0.1, 0.1, 0.1), (0.2, 0.2, 0.2), (0.6, 0.6, 0.6), 32.0, 0.75, 0.0, (0.0, 0.0, 0.0)),
+    ("pane", (0.05, 0.05, 0.1), (0.1, 0.1, 0.2), (0.4, 0.4, 0.4), 16.0, 0.0, 0.5, (0.9, 0.8, 0.7)),
+    ("matte", (0.3, 0.4, 0.8), (0.5, 0.5, 0.5), (0.0, 0.0, 0.0), 1.0, 0.0, 0.0, (0.0, 0.0, 0.0)),
+]
+FLOOR, WALL, MIRROR, PANE, MATTE = range(5)
+
+
+def tiny_textures():
+    """The two textures of the tiny scene (floor: 4 x 4 bytes, wall: 3 x 2 bytes) and a third one no material uses."""
+    r = splitmix(0x7147)
+    byte = lambda: int(255 * r())  # noqa: E731
+    floor = np.array([[[byte(), byte(), byte()] for _ in range(4)] for _ in range(4)], dtype=np.uint8)
+    wall = np.array([[[byte(), byte(), byte()] for _ in range(3)] for _ in range(2)], dtype=np.uint8)
+    spare = np.array([[[byte(), byte(), byte()] for _ in range(2)] for _ in range(2)], dtype=np.uint8)
+    return [floor, wall, spare]
+
+
+def _quad(p, du, dv, uv0, uvu, uvv):
+    """Two triangles of the quad p, p + du, p + du + dv, p + dv with texture coordinates uv0 (+ uvu) (+ uvv)."""
+    p, du, dv = np.asarray(p, float), np.asarray(du, float), np.asarray(dv, float)
+    uv0, uvu, uvv = np.asarray(uv0, float), np.asarray(uvu, float), np.asarray(uvv, float)
+    n = np.cross(du, dv)
+    n = n / np.sqrt((n * n).sum())
+    corner = [(p, uv0), (p + du, uv0 + uvu), (p + du + dv, uv0 + uvu + uvv), (p + dv, uv0 + uvv)]
+    tris = []
+    for ids in ((0, 1, 2), (0, 2, 3)):
+        v = [corner[i][0].tolist() for i in ids]
+        t = [corner[i][1].tolist() + [0.0] for i in ids]
+        tris.append((v, [n.tolist()] * 3, t))
+    return tris
+
+
+def tiny_triangles():
+    """[(vertices, normals, uvw, material)] in AddPrimitive order."""
+    out = []
+    # the floor: texture coordinates from -0.5 to 2 (negative, and beyond 1)
+    out += [t + (FLOOR,) for t in _quad((0, 0, 0), (0, 0, 10), (10, 0, 0), (-0.5, -0.5), (0.0, 2.5), (2.5, 0.0))]
+    # the left wall, textured with the second texture; coordinates exactly 0 .. 1
+    out += [t + (WALL,) for t in _quad((0, 0, 0), (0, 8, 0), (0, 0, 10), (0.0, 0.0), (0.0, 1.0), (1.0, 0.0))]
+    # the back wall: a mirror
+    out += [t + (MIRROR,) for t in _quad((0, 0, 10), (0, 8, 0), (10, 0, 0), (0.0, 0.0), (0.0, 1.0), (1.0, 0.0))]
+    # the right wall: matte, untextured -- with texture coordinates, so that it can be given a texture
+    out += [t + (MATTE,) for t in _quad((10, 0, 0), (0, 0, 10), (0, 8, 0), (0.25, 0.25), (1.5, 0.0), (0.0, 1.5))]
+    # a pane in the middle of the room
+    out += [t + (PANE,) for t in _quad((3, 0, 5), (4, 0, 0), (0, 5, 0), (0.0, 0.0), (1.0, 0.0), (0.0, 1.0))]
+    # a floor-material triangle whose texture coordinates are NaN: uvw is NaN, and so is its albedo under any texture
+    nan3 = [[NAN, NAN, NAN]] * 3
+    out.append(([[6.5, 0.5, 3.0], [9.0, 0.5, 3.0], [7.5, 3.0, 3.0]], [[0.0, 0.0, -1.0]] * 3, nan3, FLOOR))
+    # and a zero-area one (a segment)
+    out.append(([[1.0, 1.0, 2.0], [3.0, 3.0, 2.0], [2.0, 2.0, 2.0]], [[0.0, 0.0, -1.0]] * 3, [[0.5, 0.5, 0.0]] * 3, WALL))
+    return out
+
+
+def build_tiny(scene, textures=None, tex_of=None):
+    """The tiny scene through add_texture / add_material / add_triangle of `scene` (a MythTracer or an OracleScene).
+    textures: the texel arrays of the two textures in use (default tiny_textures()[:2]); tex_of: material index ->
+    texture index or -1 (default: floor 0, wall 1)."""
+    textures = tiny_textures()[:2] if textures is None else textures
+    tex_of = {FLOOR: 0, WALL: 1} if tex_of is None else tex_of
+    for i, t in enumerate(textures):
+        scene.add_texture("tex%d" % i, texel_values(t))
+    for name, ka, kd, ks, ns, refl, tr, tf in TINY_MATERIALS:
+        scene.add_material(name, ka, kd, ks, ns=ns, refl=refl, tr=tr, tf=tf, ni=1.0)
+    for m, t in tex_of.items():
+        if t >= 0:
+            scene.set_material_texture(m, t)
+    for k, (v, n, uvw, mtl) in enumerate(tiny_triangles()):
+        scene.add_triangle(v, n, uvw, mtl=mtl, line_no=k)
+    return scene
+
+
+# ---- planes no scene produces, for the data-only run of mt_retexture_gbuffer
+
+def synthetic_planes(n_materials, w=67, h=5, seed=0xda7a):
+    """(material (h, w) int32, uvw (h, w, 3)): every material index of the scene and -1, -7, n_materials; texture
+    coordinates NaN, +-1e300, -0.0, exactly integral, on texel boundaries, and random ones.  u and v are finite or NaN."""
+    r = splitmix(seed)
+    n = w * h
+    special_m = [-1, -7, n_materials, 2 ** 31 - 1, -2 ** 31]
+    special_c = [NAN, 1e300, -1e300, -0.0, 0.0, 1.0, -1.0, 2.0, -3.0, 17.0, 0.5, 1.0 / 3.0, 2.0 / 3.0, 0.25, 0.75, -2.0 ** -60]
+    material = np.zeros(n, dtype=np.int32)
+    uvw = np.zeros((n, 3), dtype=np.float64)
+    for i in range(n):
+        material[i] = special_m[i % 11] if i % 11 < len(special_m) else int(r() * n_materials)
+        for k in range(3):
+            j = int(r() * (len(special_c) + 8))
+            uvw[i, k] = special_c[j] if j < len(special_c) else 8.0 * r() - 4.0
+    return material.reshape(h, w), uvw.reshape(h, w, 3)
