@@ -648,7 +648,11 @@ int mt_raytree_update_lights_device(mt_raytree *tree, const int32_t *light_idx, 
  *     ray may cross it whether or not a ray of the tree hits it, so after the commit the planes of ALL lights are
  *     traced again in all layers under the scene's current lights, by mt_raytree_update_lights's kernel over the
  *     indices 0 .. n_lights - 1 (the scene's light count must be the tree's: MT_ERR_ARG before any device call).  A
- *     tree of zero lights skips this.
+ *     tree of zero lights skips this.  Composed with a moved light: if a light moved since the tree's planes were
+ *     made (mt_scene_set_lights without mt_raytree_update_lights), this re-trace brings the planes of EVERY light to
+ *     the scene's current positions, so a following mt_raytree_update_lights over the moved index changes no bit;
+ *     an update that runs no re-trace leaves the old positions' planes, and the tree is then the fresh tree under the
+ *     new materials and the OLD positions until mt_raytree_update_lights is called.
  * CONTRACT: the update succeeds exactly when mt_raytree_create[_rays] under the new materials has the same rays per
  * layer and the same child indices, and no textured material changed ambient or tex.  After a successful update the
  * tree is bit-identical in every plane of every layer to that fresh tree (doubles with NaN = NaN, bytes and indices

@@ -183,16 +183,17 @@ def tiny_triangles():
     return out
 
 
-def build_tiny(scene, textures=None, tex_of=None):
+def build_tiny(scene, textures=None, tex_of=None, materials=None):
     """The tiny scene through add_texture / add_material / add_triangle of `scene` (a MythTracer or an OracleScene).
-    textures: the texel arrays of the two textures in use (default tiny_textures()[:2]); tex_of: material index ->
-    texture index or -1 (default: floor 0, wall 1)."""
+    textures: the texel arrays of the textures (default tiny_textures()[:2]); tex_of: material index -> texture index
+    or -1 (default: floor 0, wall 1); materials: the table in TINY_MATERIALS' form (default TINY_MATERIALS), its rows
+    optionally with a ninth entry, the refraction index (default 1.0)."""
     textures = tiny_textures()[:2] if textures is None else textures
     tex_of = {FLOOR: 0, WALL: 1} if tex_of is None else tex_of
     for i, t in enumerate(textures):
         scene.add_texture("tex%d" % i, texel_values(t))
-    for name, ka, kd, ks, ns, refl, tr, tf in TINY_MATERIALS:
-        scene.add_material(name, ka, kd, ks, ns=ns, refl=refl, tr=tr, tf=tf, ni=1.0)
+    for name, ka, kd, ks, ns, refl, tr, tf, *ni in (TINY_MATERIALS if materials is None else materials):
+        scene.add_material(name, ka, kd, ks, ns=ns, refl=refl, tr=tr, tf=tf, ni=ni[0] if ni else 1.0)
     for m, t in tex_of.items():
         if t >= 0:
             scene.set_material_texture(m, t)
