@@ -900,7 +900,10 @@ int mt_render_frame_multi(mt_scene *const *scenes, int n_scenes,
  * element-wise MAX (torch.distributed.all_reduce / RCCL); import hands the
  * result to the scene, whose NEXT launch reads it wherever a re-projected
  * forecast needs a cost (later launches fall back to the scene's own costs
- * unless a new map is imported).  Nothing computed for a pixel depends on it.
+ * unless a new map is imported).  Any uint32 value is acceptable input: 0 =
+ * nobody reported that block, and whatever else a word holds (export never
+ * sets bit 31) only orders the work.  Nothing computed for a pixel depends on
+ * it.
  * mt_render_frame_multi does the same between its replicas by itself. */
 int mt_scene_export_costs_device(mt_scene *scene, void *d_map, int map_w,
                                  int map_h, void *stream);
