@@ -798,6 +798,71 @@ int mt_raytree_keeps_uvw(const mt_raytree *tree);
 int mt_retexture_gbuffer(mt_scene *scene, int chunk_w, int chunk_h, const mt_gbuffer *gb, mt_stats *stats);
 int mt_retexture_gbuffer_device(mt_scene *scene, int chunk_w, int chunk_h, const mt_gbuffer *d_gb, void *stream);
 
+/* Triangles given another MATERIAL in place: the whole tri_material array replaced, in node-stream order, exactly as
+ * mt_scene_desc::tri_material has it -- the same count, every entry one of the scene's materials or -1.  (No reference
+ * counterpart.)  For a look-dev session that paints the box with the mirror's material or makes the pane opaque by
+ * giving it the wall's: mt_scene_set_materials cannot express that, since a material's constants belong to every
+ * object that shares it.  Every kernel reads a triangle's material index at run time and nothing derived from the
+ * assignment is baked into the uploaded scene, so the call is one copy into the existing array, no kernel.
+ * mt_scene_set_triangle_materials is synchronous, like mt_scene_set_materials: it waits until the scene's device is
+ * idle, then copies.  The scene keeps a host copy of the assignment and an ASSIGNMENT generation, 0 at creation; a set
+ * that changes at least one entry bumps it and bumps the material generation too, so every ray tree of the scene
+ * becomes stale exactly as after a material edit (mt_raytree_update_materials).  A set that changes nothing changes no
+ * state and makes no device call.  mt_scene_get_triangle_materials returns the host copy.  Zero triangles and
+ * n_tris = 0 is MT_OK and does nothing, in both.
+ * CONTRACT: after the set, every call that renders or shades -- mt_scene_set_materials's list, both frame engines, the
+ * hybrid, the lean kernel and its redo launch, supersampled and adaptive frames, tile lists and mt_render_frame_multi
+ * replicas that share a device -- gives, byte for byte and plane for plane, what the same call gives on a scene newly
+ * created from the same description with that tri_material.  Cost history, forecasts and engine choice are left alone.
+ * G-buffer and light-buffer planes are the caller's and describe the old assignment; there is no G-buffer counterpart
+ * of this edit: render the G-buffer again, one primary pass.  There is no _device form.
+ * Argument checks come before any device call, in this order: the scene (NULL); n_tris unequal to the scene's; a NULL
+ * array with n_tris > 0; set only: an entry outside -1 .. n_materials - 1 (mt_scene_create's message, "triangle %d:
+ * material index %d outside -1..%d").  All MT_ERR_ARG. */
+int mt_scene_set_triangle_materials(mt_scene *scene, const int32_t *tri_material, int n_tris);
+int mt_scene_get_triangle_materials(const mt_scene *scene, int32_t *out, int n_tris);
+
+/* Ray trees that keep the triangle.  mt_scene_set_raytree_tri(scene, 1): every tree made from now on --
+ * mt_raytree_create, _create_rays, _create_rays_device, and the one inside mt_trace_rays -- stores one more plane per
+ * layer on the scene's GPU, tri[n] int32: the node-stream index of the triangle the ray hit (the index of
+ * mt_scene_desc::tri_material and of mt_intersect_rays's `tri`), -1 for a miss.  The tracing kernel has it in hand, so
+ * no bit of any other plane moves.  0 is the default: bytes, planes and launches of a tree are then what they always
+ * were.  (MT_ERR_ARG: scene NULL, keep other than 0 or 1.)  The switch is independent of mt_scene_set_raytree_uvw.  A
+ * tree remembers how it was made (mt_raytree_keeps_tri: 0 / 1, MT_ERR_ARG < 0 for NULL), and mt_raytree_info's bytes
+ * counts the plane: exactly 4 bytes per ray of the tree more than without it.  mt_raytree_layer stays as it is;
+ * mt_raytree_read_tri copies one layer's plane to out_tri[n_rays].  Its checks, in this order, all MT_ERR_ARG, before any
+ * device call: tree NULL; layer outside the tree's; out_tri NULL; a tree that keeps no tri.
+ * What tri buys: mt_raytree_update_materials and mt_raytree_regrow_materials take a REASSIGNMENT.  A tree's snapshot
+ * holds the scene's assignment generation and the assignment itself, taken at creation and after each successful update
+ * or regrow.  When the generations differ, CHANGED = the stream indices where the snapshot and the scene's current
+ * assignment differ.  An empty CHANGED (A -> B -> A) is nothing to do for the assignment; if no constant or texture
+ * changed either, the call is MT_OK without a device call and the tree is fresh.  Otherwise, before any device call and
+ * after the two texture refusals, MT_ERR_UNSUPPORTED with the tree untouched and still stale:
+ *   a tree WITHOUT tri: the message gives the count of changed triangles and the first.  (Without this refusal a
+ *     reassignment would compare equal material tables and declare a wrong tree fresh.)
+ *   a tree with tri but WITHOUT uvw, and a changed triangle whose NEW material has tex >= 0: the message names the
+ *     triangle and the material.
+ * mt_raytree_regrow_materials's light count check (4) also fires for a non-empty CHANGED.
+ * While a reassignment is pending, every kernel of the two calls that reads a stored or kept ray's material reads the
+ * EFFECTIVE material m'(i) = tri[i] < 0 ? -1 : tri_material_now[tri[i]] instead: for the child conditions, the
+ * coefficient product and the albedo (mt::raytree_recoef_kernel, _recommit_kernel, _regrow_flags_kernel,
+ * _regrow_copy_kernel, and _regrow_link_kernel).  The check pass always runs.  Commit and copy write m'(i) into the
+ * material plane and restate the albedo where m'(i) differs from the stored material or m'(i)'s ambient, tex or
+ * texture changed: ambient, times the texel at the stored uvw where textured; NaN for m' = -1, what the tracing kernel
+ * stores.  The check pass still writes nothing but scratch.
+ * Light planes: ALL are traced again in all layers (mt_raytree_update_lights's kernel over 0 .. n_lights - 1) when
+ * mt_raytree_update_materials's rule says so OR some changed triangle qualifies.  With a = its old material under the
+ * tree's snapshot of the constants and b = its new one under the scene's current table, it qualifies when a or b is -1
+ * (a ray on it enters or leaves the light loop), when the transparencies differ by their bits, or when either
+ * transparency is not 0 and the transmission filters differ.  The rule is conservative on purpose.
+ * CONTRACT, unchanged in form: after MT_OK the tree is bit-identical in every plane of every layer, tri and uvw
+ * included where kept, and in n_layers, n_rays and bytes, to mt_raytree_create[_rays] on a scene newly created with the
+ * current assignment, materials, textures and lights and the same switches; after a refusal it is bit-identical to
+ * what it was.  regrown, kept, traced, dropped and the stats keep their documented meaning. */
+int mt_scene_set_raytree_tri(mt_scene *scene, int keep);
+int mt_raytree_read_tri(mt_raytree *tree, int layer, int32_t *out_tri);
+int mt_raytree_keeps_tri(const mt_raytree *tree);
+
 /* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
  * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour
  * of.  Everything after layer 0 of a ray tree already runs over a ray list and never looks at a sensor or an image, so

@@ -40,6 +40,8 @@ HIP_SYMBOLS = [
     "mt_raytree_regrow_materials",
     "mt_scene_set_texture", "mt_scene_get_texture_info", "mt_scene_set_raytree_uvw", "mt_raytree_read_uvw",
     "mt_raytree_keeps_uvw", "mt_retexture_gbuffer", "mt_retexture_gbuffer_device",
+    "mt_scene_set_triangle_materials", "mt_scene_get_triangle_materials", "mt_scene_set_raytree_tri",
+    "mt_raytree_read_tri", "mt_raytree_keeps_tri",
 ]
 MT_MAX_RECURSION = 16
 
@@ -315,6 +317,11 @@ class HipAbi:
         L.mt_scene_set_raytree_uvw.argtypes = [vp, ci]
         L.mt_raytree_read_uvw.argtypes = [vp, ci, vp]
         L.mt_raytree_keeps_uvw.argtypes = [vp]
+        L.mt_scene_set_triangle_materials.argtypes = [vp, vp, ci]
+        L.mt_scene_get_triangle_materials.argtypes = [vp, vp, ci]
+        L.mt_scene_set_raytree_tri.argtypes = [vp, ci]
+        L.mt_raytree_read_tri.argtypes = [vp, ci, vp]
+        L.mt_raytree_keeps_tri.argtypes = [vp]
         L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
@@ -508,6 +515,24 @@ class HipAbi:
         """mt_scene_set_raytree_uvw: ray trees made from now on keep (True) or do not keep (False, the default) a uvw
         plane per layer, which update_materials / regrow need to take texture edits."""
         self.check(self.lib.mt_scene_set_raytree_uvw(h, 1 if keep else 0))
+
+    def set_triangle_materials(self, h, tri_material):
+        """mt_scene_set_triangle_materials: the whole per-triangle material index array replaced, in node-stream order
+        as flat["tri_material"] of MythTracer.flatten() has it (-1 = no material).  Every ray tree of the scene is
+        stale afterwards when an entry changed."""
+        a = np.ascontiguousarray(tri_material, dtype=np.int32).reshape(-1)
+        self.check(self.lib.mt_scene_set_triangle_materials(h, a.ctypes.data if a.size else None, int(a.size)))
+
+    def get_triangle_materials(self, h, n_tris) -> np.ndarray:
+        """mt_scene_get_triangle_materials: the scene's current assignment, (n_tris,) int32."""
+        out = np.zeros(max(n_tris, 0), dtype=np.int32)
+        self.check(self.lib.mt_scene_get_triangle_materials(h, out.ctypes.data if out.size else None, n_tris))
+        return out
+
+    def set_raytree_tri(self, h, keep: bool):
+        """mt_scene_set_raytree_tri: ray trees made from now on keep (True) or do not keep (False, the default) a tri
+        plane per layer, which update_materials / regrow need to take a set_triangle_materials."""
+        self.check(self.lib.mt_scene_set_raytree_tri(h, 1 if keep else 0))
 
     def retexture_gbuffer(self, h, gbuffer) -> dict:
         """mt_retexture_gbuffer: the albedo plane of `gbuffer` (dict with `material` (ch, cw) int32 and, unless no
@@ -829,6 +854,23 @@ class HipAbi:
         self.check(self.lib.mt_raytree_read_uvw(tree, layer, out.ctypes.data))
         return out
 
+    def raytree_keeps_tri(self, tree) -> bool:
+        """mt_raytree_keeps_tri: was the tree made while the scene's set_raytree_tri switch was on?"""
+        rc = self.lib.mt_raytree_keeps_tri(tree)
+        if rc < 0:
+            self.check(rc)
+        return bool(rc)
+
+    def raytree_read_tri(self, tree, layer) -> np.ndarray:
+        """mt_raytree_read_tri: the layer's tri plane, (n,) int32 stream indices, -1 for a miss; a RuntimeError for a
+        tree that keeps none."""
+        info = self.raytree_info(tree)
+        if not 0 <= layer < info["n_layers"]:
+            raise ValueError("layer %d outside the tree's %d layers" % (layer, info["n_layers"]))
+        out = np.zeros(info["n_rays"][layer], dtype=np.int32)
+        self.check(self.lib.mt_raytree_read_tri(tree, layer, out.ctypes.data if out.size else None))
+        return out
+
     def raytree_shade(self, tree, lights) -> dict:
         """mt_raytree_shade under `lights` (n x 12; count and positions as when the tree was made): dict(rgb, stats)."""
         info = self.raytree_info(tree)
@@ -1102,6 +1144,10 @@ def host_lib():
     L.mth_update_texture.argtypes = [vp, cs, ci, ci, vp]
     L.mth_set_raytree_keep_uvw.argtypes = [vp, ci]
     L.mth_set_raytree_keep_uvw.restype = None
+    L.mth_assign_material.argtypes = [vp, vp, ci, C.c_char_p]
+    L.mth_update_triangle_materials.argtypes = [vp]
+    L.mth_set_raytree_keep_triangles.argtypes = [vp, ci]
+    L.mth_set_raytree_keep_triangles.restype = None
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1423,6 +1469,27 @@ class MythTracer:
     def set_raytree_keep_uvw(self, keep: bool):
         """MythTracer::SetRayTreeKeepUVW: RayTrees built from now on keep each ray's texture coordinates."""
         self.L.mth_set_raytree_keep_uvw(self.h, 1 if keep else 0)
+
+    def assign_material(self, add_indices, name):
+        """Triangle::mtl of the triangles `add_indices` (add_triangle / .obj order) pointed at the scene's material
+        `name`, or at none for None.  Only the host scene changes: update_triangle_materials() pushes it.  RuntimeError
+        for an unknown name or an index outside the scene's triangles; no triangle is changed then."""
+        a = np.ascontiguousarray(add_indices, dtype=np.int32).reshape(-1)
+        if not self.L.mth_assign_material(self.h, a.ctypes.data if a.size else None, int(a.size),
+                                          name.encode() if name is not None else None):
+            raise RuntimeError("assign_material failed: " + self.last_error())
+
+    def update_triangle_materials(self):
+        """MythTracer::UpdateTriangleMaterials: the triangles' current materials, as indices into the uploaded dense
+        table, replaced on every device replica without uploading the geometry again.  RuntimeError when a triangle
+        points at a material that was not uploaded.  RayTrees made before are stale until their update_materials() or
+        regrow(), which take the edit only for a tree built after set_raytree_keep_triangles(True)."""
+        if not self.L.mth_update_triangle_materials(self.h):
+            raise RuntimeError("UpdateTriangleMaterials failed: " + self.last_error())
+
+    def set_raytree_keep_triangles(self, keep: bool):
+        """MythTracer::SetRayTreeKeepTriangles: RayTrees built from now on keep the triangle each ray hit."""
+        self.L.mth_set_raytree_keep_triangles(self.h, 1 if keep else 0)
 
     @property
     def num_materials(self):

@@ -296,6 +296,11 @@ struct mt_scene {
   std::vector<DevTexture> texs_host;
   std::vector<unsigned long long> tex_generation;
   int raytree_uvw = 0;
+  // mt_scene_set_triangle_materials: what dev.tri_mtl holds (shared with the ray trees' snapshots: a set replaces the
+  // vector, it never writes into it) and how often it has changed since mt_scene_create; mt_scene_set_raytree_tri's switch
+  std::shared_ptr<const std::vector<int32_t>> tri_mtl_host;
+  unsigned long long asg_generation = 0;
+  int raytree_tri = 0;
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -1519,6 +1524,7 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   if ((rc = upload(s, d->tri_normal, nt * 9, &s->dev.tri_normal)) != MT_OK) return rc;
   if ((rc = upload(s, d->tri_uvw, nt * 9, &s->dev.tri_uvw)) != MT_OK) return rc;
   if ((rc = upload(s, d->tri_material, nt, &s->dev.tri_mtl)) != MT_OK) return rc;
+  s->tri_mtl_host = std::make_shared<const std::vector<int32_t>>(d->tri_material, d->tri_material + nt);
   if ((rc = upload(s, d->tri_line_no, nt, &s->dev.tri_line)) != MT_OK) return rc;
   if (d->tri_id != nullptr) {  // (mt_render_gbuffer's `prim` plane; not part of DevScene)
     s->tri_id_host.assign(d->tri_id, d->tri_id + nt);
@@ -1711,6 +1717,45 @@ int mt_scene_set_raytree_uvw(mt_scene *s, int keep) {
   if (!s) return fail(MT_ERR_ARG, "scene is NULL");
   if (keep != 0 && keep != 1) return fail(MT_ERR_ARG, "keep must be 0 or 1");
   s->raytree_uvw = keep;
+  return MT_OK;
+}
+
+// checked before any device call, in the order of the header
+static int check_triangle_materials_args(const mt_scene *s, const void *tri_material, int n) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (n != s->dev.n_tris) return fail(MT_ERR_ARG, "%d triangles for a scene made with %d", n, s->dev.n_tris);
+  if (n > 0 && !tri_material) return fail(MT_ERR_ARG, "the triangle material array is NULL");
+  return MT_OK;
+}
+
+int mt_scene_set_triangle_materials(mt_scene *s, const int32_t *tri_material, int n) {
+  MT_TRY(check_triangle_materials_args(s, tri_material, n));
+  for (int i = 0; i < n; i++) {
+    const int m = tri_material[i];
+    if (m < -1 || m >= s->n_materials) {
+      return fail(MT_ERR_ARG, "triangle %d: material index %d outside -1..%d", i, m, s->n_materials - 1);
+    }
+  }
+  if (n == 0 || memcmp(s->tri_mtl_host->data(), tri_material, (size_t)n * sizeof(int32_t)) == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the array while it changes
+  HIP_TRY(hipMemcpy(const_cast<int32_t *>(s->dev.tri_mtl), tri_material, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  s->tri_mtl_host = std::make_shared<const std::vector<int32_t>>(tri_material, tri_material + n);
+  s->asg_generation++;
+  s->mtl_generation++;  // every ray tree of the scene is stale, as after a material edit
+  return MT_OK;
+}
+
+int mt_scene_get_triangle_materials(const mt_scene *s, int32_t *out, int n) {
+  MT_TRY(check_triangle_materials_args(s, out, n));
+  if (n > 0) memcpy(out, s->tri_mtl_host->data(), (size_t)n * sizeof(int32_t));
+  return MT_OK;
+}
+
+int mt_scene_set_raytree_tri(mt_scene *s, int keep) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (keep != 0 && keep != 1) return fail(MT_ERR_ARG, "keep must be 0 or 1");
+  s->raytree_tri = keep;
   return MT_OK;
 }
 
@@ -2903,6 +2948,11 @@ struct mt_raytree {
   // scene's mt_scene_set_raytree_uvw switch when the tree was made
   std::vector<unsigned long long> tex_generation;
   bool keep_uvw = false;
+  // the scene's assignment then (mt_scene_set_triangle_materials: the scene's own vector of that time, shared) with its
+  // generation, and whether the layers have a tri plane: the scene's mt_scene_set_raytree_tri switch when the tree was made
+  std::shared_ptr<const std::vector<int32_t>> tri_mtl;
+  unsigned long long asg_generation = 0;
+  bool keep_tri = false;
   unsigned long long *d_mismatch = nullptr;
   uint8_t *d_albedo_changed = nullptr;
   // mt_raytree_regrow_materials (first use, grown when a call needs more): `src` of the new layers k and k + 1 in turn,
@@ -2929,7 +2979,8 @@ int raytree_malloc(void **p, size_t bytes, const char *what) {
 // One allocation holds a layer's planes, each at a multiple of 256 bytes: the planes of layer k with n rays and n_l
 // lights laid out from `base` (nullptr: only the size is wanted).  Returns the bytes.  The uvw plane of a tree that
 // keeps one comes last, [n][3] doubles at a multiple of 256 bytes: without it a layer is laid out as it always was.
-size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, bool keep_uvw, RayTreeLayer *out) {
+// The tri plane of a tree that keeps one comes behind that, [n] int32, unpadded too.
+size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, bool keep_uvw, bool keep_tri, RayTreeLayer *out) {
   struct Part { void **at; size_t bytes; };
   RayTreeLayer &L = *out;
   const Part parts[] = {
@@ -2947,17 +2998,20 @@ size_t raytree_carve_layer(void *base, size_t n_l, int k, size_t n, bool keep_uv
   // (behind the last padded plane, itself unpadded: the layer grows by exactly 24 bytes per ray)
   L.uvw = keep_uvw && base != nullptr ? (double *)((char *)base + at) : nullptr;
   if (keep_uvw) at += n * 24;
+  // (at a multiple of 8 bytes either way: the layer grows by exactly 4 bytes per ray)
+  L.tri = keep_tri && base != nullptr ? (int32_t *)((char *)base + at) : nullptr;
+  if (keep_tri) at += n * 4;
   return at;
 }
 
 int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
   const size_t n_l = (size_t)t->info.n_lights;
   RayTreeLayer &L = t->layer[k];
-  const size_t total = raytree_carve_layer(nullptr, n_l, k, n, t->keep_uvw, &L);
+  const size_t total = raytree_carve_layer(nullptr, n_l, k, n, t->keep_uvw, t->keep_tri, &L);
   char what[64];
   snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
   MT_TRY(raytree_malloc(&t->alloc[k], total, what));
-  (void)raytree_carve_layer(t->alloc[k], n_l, k, n, t->keep_uvw, &L);
+  (void)raytree_carve_layer(t->alloc[k], n_l, k, n, t->keep_uvw, t->keep_tri, &L);
   t->info.bytes += total;
   t->info.n_rays[k] = (int64_t)n;
   t->info.n_layers = k + 1;
@@ -3223,6 +3277,8 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
   t->mtls = s->mtls_host;
   t->mtl_generation = s->mtl_generation;
   t->tex_generation = s->tex_generation;
+  t->tri_mtl = s->tri_mtl_host;
+  t->asg_generation = s->asg_generation;
   if (stats) {
     memset(stats, 0, sizeof *stats);
     fill_stats(s->h_counters, stats);
@@ -3317,6 +3373,7 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
   mt_raytree *t = new mt_raytree();
   t->scene = s;
   t->keep_uvw = s->raytree_uvw != 0;
+  t->keep_tri = s->raytree_tri != 0;
   t->sensor = *sensor;
   t->info.n_lights = s->dev.n_lights;
   t->info.image_w = image_w; t->info.image_h = image_h;
@@ -3346,6 +3403,7 @@ int raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_
   mt_raytree *t = new mt_raytree();
   t->scene = s;
   t->keep_uvw = s->raytree_uvw != 0;
+  t->keep_tri = s->raytree_tri != 0;
   t->info.n_lights = s->dev.n_lights;
   t->info.image_w = t->info.chunk_w = rays->list_w;
   t->info.image_h = t->info.chunk_h = rays->list_h;
@@ -3423,6 +3481,26 @@ int mt_raytree_read_uvw(mt_raytree *t, int layer, double *out_uvw) {
   HIP_TRY(hipSetDevice(t->scene->device));
   const size_t n = (size_t)t->info.n_rays[layer];
   if (n > 0) HIP_TRY(hipMemcpy(out_uvw, t->layer[layer].uvw, n * 24, hipMemcpyDeviceToHost));
+  return MT_OK;
+}
+
+int mt_raytree_keeps_tri(const mt_raytree *t) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  return t->keep_tri ? 1 : 0;
+}
+
+int mt_raytree_read_tri(mt_raytree *t, int layer, int32_t *out_tri) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (layer < 0 || layer >= t->info.n_layers) {
+    return fail(MT_ERR_ARG, "layer %d outside the ray tree's %d layers", layer, t->info.n_layers);
+  }
+  if (!out_tri) return fail(MT_ERR_ARG, "the tri output is NULL");
+  if (!t->keep_tri) {
+    return fail(MT_ERR_ARG, "the ray tree keeps no tri: it was made with mt_scene_set_raytree_tri at 0");
+  }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  const size_t n = (size_t)t->info.n_rays[layer];
+  if (n > 0) HIP_TRY(hipMemcpy(out_tri, t->layer[layer].tri, n * 4, hipMemcpyDeviceToHost));
   return MT_OK;
 }
 
@@ -3546,7 +3624,38 @@ struct MaterialDiff {
   bool albedo = false;   // some ambient changed
   int textured = -1;     // the first textured material whose ambient or tex changed
   std::vector<uint8_t> albedo_changed;
+  // a pending reassignment (mt_scene_set_triangle_materials): the triangles whose material differs from the tree's
+  // snapshot, the first of them, and the first whose NEW material has a texture (with that material)
+  long long reassigned = 0;
+  int first_reassigned = -1, textured_tri = -1, textured_tri_mtl = -1;
 };
+
+// CHANGED of the assignment `was` -> `now`, and whether a shadow ray may see it: a = the old material under the tree's
+// constants `mtls_was`, b = the new one under the scene's `mtls_now`
+void diff_assignment(const std::vector<int32_t> &was, const std::vector<int32_t> &now, const std::vector<mt_material> &mtls_was,
+                     const std::vector<mt_material> &mtls_now, MaterialDiff *out) {
+  MaterialDiff &D = *out;
+  for (size_t i = 0; i < now.size(); i++) {
+    const int a = was[i], b = now[i];
+    if (a == b) continue;
+    if (D.reassigned++ == 0) D.first_reassigned = (int)i;
+    if (b >= 0 && mtls_now[(size_t)b].tex >= 0 && D.textured_tri < 0) {
+      D.textured_tri = (int)i;
+      D.textured_tri_mtl = b;
+    }
+    if (a < 0 || b < 0) {  // a ray on it enters or leaves the light loop
+      D.shadow = true;
+      continue;
+    }
+    const mt_material &ma = mtls_was[(size_t)a], &mb = mtls_now[(size_t)b];
+    const bool opaque = ma.transparency == 0.0 && mb.transparency == 0.0;  // (the shadow loop's own test)
+    if (!same_bits(&ma.transparency, &mb.transparency, 1) ||
+        (!opaque && !same_bits(ma.transmission_filter, mb.transmission_filter, 3))) {
+      D.shadow = true;
+    }
+  }
+  if (D.reassigned != 0) D.shape = true;  // the check pass decides
+}
 
 void diff_materials(const std::vector<mt_material> &was, const std::vector<mt_material> &now, MaterialDiff *out) {
   MaterialDiff &D = *out;
@@ -3589,6 +3698,8 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   const int n_mtl = s->n_materials;
   const size_t n_l = (size_t)I.n_lights;
   const int old_layers = I.n_layers;
+  // a pending reassignment: layer 0's material plane waits for the commit, the copy kernel restates the kept rays'
+  const int32_t *tri_mtl_now = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
   void *alloc[MT_MAX_RECURSION + 1] = {};  // the new layers >= 1, aside
   RayTreeLayer NL[MT_MAX_RECURSION + 1] = {};
   size_t n_new[MT_MAX_RECURSION + 1] = {}, n_traced[MT_MAX_RECURSION + 1] = {};
@@ -3624,6 +3735,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.L = NL[k];
       A.src = src;
       A.mtls = s->dev.mtls;
+      A.tri_mtl = k == 0 ? tri_mtl_now : nullptr;
       A.n_rays = (uint32_t)n;
       A.n_materials = n_mtl;
       A.may_spawn = k < I.max_depth ? 1 : 0;
@@ -3653,11 +3765,11 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     }
     const size_t n1 = (size_t)children;
     n_new[k + 1] = n1;
-    const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, t->keep_uvw, &NL[k + 1]);
+    const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, t->keep_uvw, t->keep_tri, &NL[k + 1]);
     char what[64];
     snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k + 1, n1);
     if (const int rc = raytree_malloc(&alloc[k + 1], total, what)) return release(rc);
-    (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, t->keep_uvw, &NL[k + 1]);
+    (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, t->keep_uvw, t->keep_tri, &NL[k + 1]);
     const int to = (k + 1) & 1;
     if (const int rc = raytree_scratch((void **)&t->d_src[to], &t->src_cap[to], n1 * 4, "the ray tree's regrow indices")) {
       return release(rc);
@@ -3672,6 +3784,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.old_child_refr = k < old_layers ? t->layer[k].child_refr : nullptr;
       A.child_src = t->d_src[to];
       A.mtls = s->dev.mtls;
+      A.tri_mtl = k == 0 ? tri_mtl_now : nullptr;
       A.n_parent = (uint32_t)n;
       hipLaunchKernelGGL(raytree_regrow_link_kernel, grid_of(n), dim3(256), 0, stream, A);
       if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's link kernel failed"));
@@ -3688,6 +3801,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.mtls = s->dev.mtls;
       A.texs = s->dev.texs;
       A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+      A.tri_mtl = tri_mtl_now;
       hipLaunchKernelGGL(raytree_regrow_copy_kernel, grid_of(n1), dim3(256), 0, stream, A);
       if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
     }
@@ -3705,11 +3819,11 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     n_traced[k + 1] = m;
     if (m == 0) continue;
     RayTreeRegrowListArgs A{};
-    const size_t tmp_bytes = raytree_carve_layer(nullptr, n_l, k + 1, m, t->keep_uvw, &A.tmp);
+    const size_t tmp_bytes = raytree_carve_layer(nullptr, n_l, k + 1, m, t->keep_uvw, t->keep_tri, &A.tmp);
     if (const int rc = raytree_scratch(&t->d_tmp, &t->tmp_cap, tmp_bytes, "the ray tree's list of traced rays")) {
       return release(rc);
     }
-    (void)raytree_carve_layer(t->d_tmp, n_l, k + 1, m, t->keep_uvw, &A.tmp);
+    (void)raytree_carve_layer(t->d_tmp, n_l, k + 1, m, t->keep_uvw, t->keep_tri, &A.tmp);
     A.L = NL[k + 1];
     A.n_rays = (uint32_t)n1;
     A.n_list = (uint32_t)m;
@@ -3727,12 +3841,13 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       hipMemcpyAsync(t->layer[0].child_refr, NL[0].child_refr, n0 * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
     return release(fail(MT_ERR_HIP, "writing layer 0's child indices failed"));
   }
-  if (D.albedo) {
+  if (D.albedo || tri_mtl_now != nullptr) {
     RayTreeRecommitArgs A{};
     A.L = t->layer[0];
     A.mtls = s->dev.mtls;
     A.texs = s->dev.texs;
-    A.albedo_changed = t->d_albedo_changed;
+    A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+    A.tri_mtl = tri_mtl_now;
     A.n_rays = (uint32_t)n0;
     A.n_materials = n_mtl;
     A.copy_coef = 0;
@@ -3753,13 +3868,13 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   RayTreeLayer none{};
   for (int k = 1; k <= MT_MAX_RECURSION; k++) {
     if (t->alloc[k]) {
-      I.bytes -= raytree_carve_layer(nullptr, n_l, k, (size_t)I.n_rays[k], t->keep_uvw, &none);
+      I.bytes -= raytree_carve_layer(nullptr, n_l, k, (size_t)I.n_rays[k], t->keep_uvw, t->keep_tri, &none);
       (void)hipFree(t->alloc[k]);
     }
     t->alloc[k] = alloc[k];
     t->layer[k] = NL[k];
     I.n_rays[k] = (int64_t)n_new[k];
-    if (alloc[k]) I.bytes += raytree_carve_layer(nullptr, n_l, k, n_new[k], t->keep_uvw, &none);
+    if (alloc[k]) I.bytes += raytree_carve_layer(nullptr, n_l, k, n_new[k], t->keep_uvw, t->keep_tri, &none);
   }
   I.n_layers = new_layers;
   for (int k = 0; k <= MT_MAX_RECURSION; k++) {
@@ -3801,6 +3916,20 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     D.albedo = true;
     D.albedo_changed[i] = 1;
   }
+  // a reassignment since the snapshot (A -> B -> A is none)
+  if (t->asg_generation != s->asg_generation && t->tri_mtl != s->tri_mtl_host) {
+    diff_assignment(*t->tri_mtl, *s->tri_mtl_host, t->mtls, s->mtls_host, &D);
+  }
+  if (D.reassigned != 0 && !t->keep_tri) {
+    return fail(MT_ERR_UNSUPPORTED, "%lld triangles were given another material after the ray tree was made, the first is "
+                                    "triangle %d: the ray tree keeps no tri (mt_scene_set_raytree_tri), a new tree is needed",
+                D.reassigned, D.first_reassigned);
+  }
+  if (D.textured_tri >= 0 && !t->keep_uvw) {
+    return fail(MT_ERR_UNSUPPORTED, "triangle %d was given material %d, which has a texture: the ray tree keeps no uvw "
+                                    "(mt_scene_set_raytree_uvw), a new tree is needed", D.textured_tri, D.textured_tri_mtl);
+  }
+  const int32_t *tri_mtl_now = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
   const bool retrace = D.shadow && I.n_lights > 0;
   // (a regrow may trace new rays, whose light planes come from the scene's current lights)
   const bool lights_read = regrow ? (D.shape || D.shadow) && I.n_lights > 0 : retrace;
@@ -3825,6 +3954,7 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
         A.L = t->layer[k];
         A.child_scratch = k + 1 < I.n_layers ? t->layer[k + 1].color : nullptr;
         A.mtls = s->dev.mtls;
+        A.tri_mtl = tri_mtl_now;
         A.n_rays = (uint32_t)n;
         A.n_materials = n_mtl;
         A.layer = k;
@@ -3870,10 +4000,11 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
         A.mtls = s->dev.mtls;
         A.texs = s->dev.texs;
         A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+        A.tri_mtl = tri_mtl_now;
         A.n_rays = (uint32_t)n;
         A.n_materials = n_mtl;
         A.copy_coef = D.shape && k > 0 ? 1 : 0;
-        if (!A.copy_coef && !A.albedo_changed) continue;
+        if (!A.copy_coef && !A.albedo_changed && !A.tri_mtl) continue;
         hipLaunchKernelGGL(raytree_recommit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
         HIP_TRY(hipGetLastError());
       }
@@ -3915,6 +4046,8 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
   t->mtls = s->mtls_host;
   t->mtl_generation = s->mtl_generation;
   t->tex_generation = s->tex_generation;
+  t->tri_mtl = s->tri_mtl_host;
+  t->asg_generation = s->asg_generation;
   if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   return MT_OK;
 }

@@ -9,7 +9,9 @@
 // coef, the G-buffer planes point / normal (unflipped) / albedo / material, per light power and in_shadow
 // (mt_lightbuffer.h's meaning, planes [n_lights][n_rays]), the two child indices into the next layer (-1 = none), and
 // in layer 0 the chunk-local pixel index.  A tree made while mt_scene_set_raytree_uvw is on also keeps the G-buffer
-// plane uvw: the one thing a texture edit needs to restate the albedo without tracing a ray.
+// plane uvw: the one thing a texture edit needs to restate the albedo without tracing a ray.  A tree made while
+// mt_scene_set_raytree_tri is on keeps tri, the stream index of the triangle each ray hit: the one thing a REASSIGNMENT
+// (mt_scene_set_triangle_materials) needs to restate the ray's material, raytree_effective_material below.
 //
 //   raytree_primary_kernel  layer 0's ray list from the sensor, in raytree_layer0_index's order (8x8 blocks of the
 //                           chunk, row-major; a block clipped by the chunk's edge holds only its pixels, row-major:
@@ -49,7 +51,16 @@ struct RayTreeLayer {
   uint8_t *in_shadow;  // [n_lights][n]
   uint8_t *spawn;      // [n] bit 0: a reflected child, bit 1: a refracted child
   double *uvw;         // [n][3] Triangle::GetUVW(point), NaN on a miss; nullptr: the tree keeps none (mt_scene_set_raytree_uvw)
+  int32_t *tri;        // [n] the stream index of the triangle hit, -1 on a miss; nullptr: the tree keeps none (mt_scene_set_raytree_tri)
 };
+
+// The material of stored ray i while a reassignment is pending (tri_mtl = the scene's CURRENT assignment, read through
+// the layer's tri plane), else -- tri_mtl == nullptr -- what the material plane holds.
+__device__ __forceinline__ int raytree_effective_material(const RayTreeLayer &L, const int32_t *tri_mtl, size_t i) {
+  if (tri_mtl == nullptr) return L.material[i];
+  const int tri = L.tri[i];
+  return tri < 0 ? -1 : tri_mtl[tri];
+}
 
 // index of chunk pixel (x, y) in layer 0's list
 __host__ __device__ inline size_t raytree_layer0_index(int x, int y, int chunk_w, int chunk_h) {
@@ -138,6 +149,7 @@ __global__ __launch_bounds__(256, MT_WAVES_PER_SIMD) void raytree_trace_kernel(D
       }
       lit = to.prim >= 0 && h.mtl >= 0;
       if (lit) Pt = h.point;
+      if (A.L.tri != nullptr) A.L.tri[i] = to.prim >= 0 ? to.prim : -1;  // (nullable, wave-uniform)
       // the child conditions, :181-184 and :192 (level < max_depth is the layer's: wave-uniform)
       unsigned spawn = 0;
       if (lit && A.may_spawn) {
@@ -609,10 +621,14 @@ __global__ __launch_bounds__(256) void raytree_color_kernel(const double *color,
 //                          stores for an untextured material, no arithmetic; times the texel at the ray's stored uvw
 //                          where the material has a texture (retextured_albedo, mt_gbuffer.h: a tree that keeps uvw;
 //                          the host lets no textured material's byte through for a tree that does not).
+// A pending REASSIGNMENT (tri_mtl != nullptr, a tree that keeps tri): both kernels read raytree_effective_material in the
+// material plane's place; the commit also writes it into the material plane, and restates the albedo of every ray whose
+// material moved as well -- NaN for "no material", what write_gbuffer_planes stores.
 struct RayTreeRecoefArgs {
   RayTreeLayer L;
   double *child_scratch;         // the next layer's color plane, nullptr: there is no next layer
   const mt_material *mtls;       // the scene's CURRENT materials
+  const int32_t *tri_mtl;        // the scene's CURRENT assignment while a reassignment is pending, else nullptr
   uint32_t n_rays;
   int32_t n_materials;
   int32_t layer;
@@ -625,7 +641,7 @@ __global__ __launch_bounds__(256) void raytree_recoef_kernel(RayTreeRecoefArgs A
   if (i >= (size_t)A.n_rays) return;
   const double c = A.layer == 0 ? A.L.coef[i] : A.L.color[i * 3];
   const double p0 = A.L.point[i * 3];
-  const int mtl = A.L.material[i];
+  const int mtl = raytree_effective_material(A.L, A.tri_mtl, i);
   const bool lit = p0 == p0 && mtl >= 0 && mtl < A.n_materials;
   const int cr = A.L.child_refl[i], ct = A.L.child_refr[i];
   // the child conditions, :181-184 and :192, as raytree_trace_kernel states them
@@ -654,21 +670,31 @@ struct RayTreeRecommitArgs {
   RayTreeLayer L;
   const mt_material *mtls;        // the scene's CURRENT materials
   const DevTexture *texs;         // and its CURRENT textures
-  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
+  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite for a material's own sake
+  const int32_t *tri_mtl;         // the scene's CURRENT assignment while a reassignment is pending, else nullptr
   uint32_t n_rays;
   int32_t n_materials;
   int32_t copy_coef;
 };
 
+// the albedo of a stored ray whose material is now `mtl`: retextured_albedo, NaN for "no material"
+__device__ __forceinline__ V3 raytree_restated_albedo(const mt_material *mtls, const DevTexture *texs, int mtl,
+                                                      const double *uvw, size_t i) {
+  const double nan = __builtin_nan("");
+  return mtl >= 0 ? retextured_albedo(mtls + mtl, texs, uvw, i) : v3(nan, nan, nan);
+}
+
 __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitArgs A) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)A.n_rays) return;
   if (A.copy_coef) A.L.coef[i] = A.L.color[i * 3];
-  if (A.albedo_changed != nullptr) {
-    const int mtl = A.L.material[i];
-    if (mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
-      store3(A.L.albedo, i, retextured_albedo(A.mtls + mtl, A.texs, A.L.uvw, i));
-    }
+  const int was = A.L.material[i];
+  const int mtl = raytree_effective_material(A.L, A.tri_mtl, i);
+  if (mtl != was) {
+    A.L.material[i] = mtl;
+    store3(A.L.albedo, i, raytree_restated_albedo(A.mtls, A.texs, mtl, A.L.uvw, i));
+  } else if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
+    store3(A.L.albedo, i, retextured_albedo(A.mtls + mtl, A.texs, A.L.uvw, i));
   }
 }
 
@@ -694,19 +720,21 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
 //                                  places live in child_refl until layer k + 1's own compaction overwrites them.
 //   raytree_regrow_copy_kernel     one thread per kept ray of layer k + 1, by the destination index: ray, in_object,
 //                                  point, normal, material, every light's power and in_shadow from the old layer at
-//                                  src; uvw too where the tree keeps it; albedo too, or the new ambient (times the texel
-//                                  at the OLD layer's uvw at src) where the material's byte in albedo_changed is set
-//                                  (raytree_recommit_kernel's rule).
+//                                  src; uvw and tri too where the tree keeps them; albedo too, or the new ambient (times
+//                                  the texel at the OLD layer's uvw at src) where the material's byte in albedo_changed
+//                                  is set or a pending reassignment moved the ray's material (raytree_recommit_kernel's
+//                                  rule).
 //   raytree_regrow_gather_kernel   ray, coef and in_object of the traced rays to their places in the temporary layer;
 //   (raytree_trace_kernel)         over the temporary layer, secondary = 1, may_spawn = (k + 1 < max_depth);
-//   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow, spawn and (where kept) uvw back to
-//                                  the new layer.
+//   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow, spawn and (where kept) uvw and tri
+//                                  back to the new layer.
 // That regrouping the traced rays changes no bit is the ray-list contract: layer k handed in as an n x 1 list gives the
 // tree's layers k onwards.  None of these kernels writes a plane of the OLD tree.
 struct RayTreeRegrowFlagsArgs {
   RayTreeLayer L;
   const int32_t *src;       // nullptr: layer 0, every ray is kept
   const mt_material *mtls;  // the scene's CURRENT materials
+  const int32_t *tri_mtl;   // layer 0 while a reassignment is pending (its material plane waits for the commit), else nullptr
   uint32_t n_rays;
   int32_t n_materials;
   int32_t may_spawn;        // layer < max_depth
@@ -717,7 +745,7 @@ __global__ __launch_bounds__(256) void raytree_regrow_flags_kernel(RayTreeRegrow
   if (i >= (size_t)A.n_rays) return;
   if (A.src != nullptr && A.src[i] < 0) return;  // (traced: raytree_trace_kernel left its byte)
   const double p0 = A.L.point[i * 3];
-  const int mtl = A.L.material[i];
+  const int mtl = raytree_effective_material(A.L, A.tri_mtl, i);
   const bool lit = p0 == p0 && mtl >= 0 && mtl < A.n_materials;
   // the child conditions, :181-184 and :192, as raytree_trace_kernel states them
   unsigned spawn = 0;
@@ -736,6 +764,7 @@ struct RayTreeRegrowLinkArgs {
   const int32_t *old_child_refl, *old_child_refr;  // of the OLD layer k
   int32_t *child_src;                              // [the child layer's rays]
   const mt_material *mtls;                         // the scene's CURRENT materials
+  const int32_t *tri_mtl;                          // as RayTreeRegrowFlagsArgs has it: the parent is layer 0, else nullptr
   uint32_t n_parent;
 };
 
@@ -753,7 +782,7 @@ __global__ __launch_bounds__(256) void raytree_regrow_link_kernel(RayTreeRegrowL
   if (cr >= 0) {
     A.child_src[cr] = ocr;
     A.child.spawn[cr] = ocr < 0 ? 1 : 0;
-    A.child.coef[cr] = coef * A.mtls[A.parent.material[i]].reflectance;  // :187
+    A.child.coef[cr] = coef * A.mtls[raytree_effective_material(A.parent, A.tri_mtl, i)].reflectance;  // :187
     if (ocr < 0) {  // raytree_spawn_kernel's reflected child
       V3 Nn = v3_load(A.parent.normal + i * 3);  // as GetNormal returned it, :38
       if (dot(Nn, -dir) < 0.0) Nn = -Nn;         // :42-45
@@ -786,7 +815,8 @@ struct RayTreeRegrowCopyArgs {
   int32_t n_materials;
   const mt_material *mtls;        // the scene's CURRENT materials
   const DevTexture *texs;         // and its CURRENT textures
-  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite
+  const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite for a material's own sake
+  const int32_t *tri_mtl;         // the scene's CURRENT assignment while a reassignment is pending, else nullptr
 };
 
 __global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowCopyArgs A) {
@@ -800,10 +830,14 @@ __global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowC
   A.to.in_object[j] = A.from.in_object[s];
   store3(A.to.point, j, v3_load(A.from.point + s * 3));
   store3(A.to.normal, j, v3_load(A.from.normal + s * 3));
-  const int mtl = A.from.material[s];
+  const int was = A.from.material[s];
+  const int mtl = raytree_effective_material(A.from, A.tri_mtl, s);
   A.to.material[j] = mtl;
   if (A.to.uvw != nullptr) store3(A.to.uvw, j, v3_load(A.from.uvw + s * 3));
-  if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
+  if (A.to.tri != nullptr) A.to.tri[j] = A.from.tri[s];
+  if (mtl != was) {
+    store3(A.to.albedo, j, raytree_restated_albedo(A.mtls, A.texs, mtl, A.from.uvw, s));
+  } else if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
     store3(A.to.albedo, j, retextured_albedo(A.mtls + mtl, A.texs, A.from.uvw, s));
   } else {
     store3(A.to.albedo, j, v3_load(A.from.albedo + s * 3));
@@ -844,6 +878,7 @@ __global__ __launch_bounds__(256) void raytree_regrow_scatter_kernel(RayTreeRegr
   store3(A.L.albedo, j, v3_load(A.tmp.albedo + p * 3));
   A.L.material[j] = A.tmp.material[p];
   if (A.L.uvw != nullptr) store3(A.L.uvw, j, v3_load(A.tmp.uvw + p * 3));
+  if (A.L.tri != nullptr) A.L.tri[j] = A.tmp.tri[p];
   for (int li = 0; li < A.n_lights; li++) {
     store3(A.L.power, (size_t)li * n + j, v3_load(A.tmp.power + ((size_t)li * m + p) * 3));
     A.L.in_shadow[(size_t)li * n + j] = A.tmp.in_shadow[(size_t)li * m + p];

@@ -224,6 +224,18 @@ class MythTracer {
   // ray, and UpdateRayTreeMaterials / RegrowRayTree then take texture edits and ambient or texture changes of textured
   // materials, which they refuse for a tree without.  Off by default.
   void SetRayTreeKeepUVW(bool keep);
+  // After triangles were given another MATERIAL (GetScene()->tree.MutableTriangle(i)->mtl pointing at another of
+  // GetScene()->materials, or at none): derives the per-triangle material indices again, in the uploaded order and
+  // through the uploaded dense table, and replaces them on every device replica (mt_scene_set_triangle_materials),
+  // without uploading a triangle again; every later RayTrace, G-buffer, light buffer and BuildRayTree sees them.
+  // Refused with a message when a triangle points at a material that was not uploaded (no triangle used it at the
+  // upload: the call edits, it does not add).  Before the first upload it is Prepare.  RayTrees built before the edit
+  // are stale until UpdateRayTreeMaterials / RegrowRayTree, which need a tree that keeps triangles for it.
+  bool UpdateTriangleMaterials();
+  // RayTrees built from now on also keep the triangle each ray hit (mt_scene_set_raytree_tri): 4 bytes more per ray,
+  // and UpdateRayTreeMaterials / RegrowRayTree then take an UpdateTriangleMaterials, which they refuse for a tree
+  // without.  Off by default; independent of SetRayTreeKeepUVW (a reassignment TO a textured material needs both).
+  void SetRayTreeKeepTriangles(bool keep);
   // Brings `tree` to the materials of the last UpdateMaterials without tracing a primary or secondary ray
   // (mt_raytree_update_materials): new albedo and coefficients, and the light planes again where a shadow ray can see
   // the edit (under GetScene()->lights).  Fails, with the tree exactly as it was, when the edit changes which rays
@@ -278,7 +290,9 @@ class MythTracer {
   void DropDeviceScenes();
   std::vector<std::string> uploaded_names_, dense_names_;  // UpdateMaterials: all names at the upload; the dense table's
   std::vector<const Texture*> uploaded_textures_;          // ... and the texture table's sources
+  std::vector<const Material*> uploaded_materials_;        // UpdateTriangleMaterials: the dense table's sources
   bool keep_uvw_ = false;                                  // SetRayTreeKeepUVW
+  bool keep_tri_ = false;                                  // SetRayTreeKeepTriangles
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
   int adaptive_ss_ = 1, adaptive_threshold_ = 16;

@@ -67,6 +67,9 @@ class OctTree {
   const FlatTree& Flat() const { return flat_; }
   size_t PrimitiveCount() const { return prims_.size(); }
   const Triangle* GetTriangle(size_t add_index) const;
+  // the same triangle, for a caller that gives it another material (Triangle::mtl; MythTracer::UpdateTriangleMaterials).
+  // Vertices, normals and boxes are the finalized tree's: they are not to be changed through it.
+  Triangle* MutableTriangle(size_t add_index);
   const char* LastError() const { return error_.c_str(); }
   static const int SPLIT_BOUNDARY = 16;  // octtree.h:43
 

@@ -597,6 +597,42 @@ int mth_update_texture(void* p, const char* name, int w, int hgt, const double* 
 // MythTracer::SetRayTreeKeepUVW
 void mth_set_raytree_keep_uvw(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepUVW(keep != 0); }
 
+// Triangle::mtl of the listed triangles (AddPrimitive indices) pointed at the material `name` (NULL = none), through
+// OctTree::MutableTriangle; nothing is uploaded (mth_update_triangle_materials does that).  0 with the shim's message for
+// an unknown name or an index outside the scene's triangles: no triangle is changed then.
+int mth_assign_material(void* p, const int32_t* add_indices, int n, const char* name) {
+  Handle* h = static_cast<Handle*>(p);
+  auto* scene = h->mt.GetScene();
+  Material* m = nullptr;
+  if (name != nullptr) {
+    auto it = scene->materials.find(name);
+    if (it == scene->materials.end()) {
+      h->shim_error = std::string("no material named ") + name;
+      return 0;
+    }
+    m = it->second.get();
+  }
+  if (n < 0 || (n > 0 && add_indices == nullptr)) {
+    h->shim_error = "bad triangle index list";
+    return 0;
+  }
+  for (int i = 0; i < n; i++) {
+    if (add_indices[i] < 0 || (size_t)add_indices[i] >= scene->tree.PrimitiveCount()) {
+      h->shim_error = "triangle index " + std::to_string(add_indices[i]) + " outside the scene's " +
+                      std::to_string(scene->tree.PrimitiveCount()) + " triangles";
+      return 0;
+    }
+  }
+  for (int i = 0; i < n; i++) scene->tree.MutableTriangle((size_t)add_indices[i])->mtl = m;
+  return 1;
+}
+
+// MythTracer::UpdateTriangleMaterials; 0 with the facade's message when it refuses
+int mth_update_triangle_materials(void* p) { return static_cast<Handle*>(p)->mt.UpdateTriangleMaterials() ? 1 : 0; }
+
+// MythTracer::SetRayTreeKeepTriangles
+void mth_set_raytree_keep_triangles(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepTriangles(keep != 0); }
+
 // MythTracer::UpdateRayTreeMaterials; stats8 / ms2 as mth_raytree_update fills them
 int mth_raytree_update_materials(void* p, void* t, uint64_t* stats8, double* ms2) {
   Handle* h = static_cast<Handle*>(p);

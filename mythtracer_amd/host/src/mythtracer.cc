@@ -205,6 +205,7 @@ bool MythTracer::Prepare() {
       return false;
     }
     (void)mt_scene_set_raytree_uvw(s, keep_uvw_ ? 1 : 0);
+    (void)mt_scene_set_raytree_tri(s, keep_tri_ ? 1 : 0);
     if (r == 0) dev_ = s;
     else replicas_.push_back(s);
   }
@@ -220,7 +221,49 @@ bool MythTracer::Prepare() {
     }
   }
   uploaded_textures_ = flat.texture_of;
+  uploaded_materials_ = flat.material_of;
   return true;
+}
+
+bool MythTracer::UpdateTriangleMaterials() {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes them as they are
+  // FlatScene::Build's stream order, through the uploaded dense table
+  const FlatTree& f = scene.tree.Flat();
+  std::unordered_map<const Material*, int32_t> index;
+  for (size_t i = 0; i < uploaded_materials_.size(); i++) index[uploaded_materials_[i]] = (int32_t)i;
+  std::vector<int32_t> material(f.tri_id.size());
+  for (size_t s = 0; s < material.size(); s++) {
+    const Triangle* t = scene.tree.GetTriangle((size_t)f.tri_id[s]);
+    if (t->mtl == nullptr) {
+      material[s] = -1;
+      continue;
+    }
+    const auto it = index.find(t->mtl);
+    if (it == index.end()) {
+      return refuse("triangle " + std::to_string(f.tri_id[s]) + " points at a material that was not uploaded: "
+                    "UpdateTriangleMaterials edits, it does not add");
+    }
+    material[s] = it->second;
+  }
+  std::vector<mt_scene*> all(1, dev_);
+  all.insert(all.end(), replicas_.begin(), replicas_.end());
+  for (mt_scene* s : all) {
+    if (mt_scene_set_triangle_materials(s, material.data(), (int)material.size()) != MT_OK) {
+      return refuse(std::string("triangle material update failed: ") + mt_last_error());
+    }
+  }
+  return true;
+}
+
+void MythTracer::SetRayTreeKeepTriangles(bool keep) {
+  keep_tri_ = keep;
+  if (dev_ != nullptr) (void)mt_scene_set_raytree_tri(dev_, keep ? 1 : 0);
+  for (mt_scene* s : replicas_) (void)mt_scene_set_raytree_tri(s, keep ? 1 : 0);
 }
 
 bool MythTracer::UpdateMaterials() {

@@ -38,6 +38,8 @@ const Triangle* OctTree::GetTriangle(size_t i) const {
   return static_cast<const Triangle*>(prims_[i].get());
 }
 
+Triangle* OctTree::MutableTriangle(size_t i) { return static_cast<Triangle*>(prims_[i].get()); }
+
 namespace {
 
 // One node while the tree is being built: its box and its (ordered) members.
