@@ -328,6 +328,13 @@ int upload(mt_scene *s, const T *host, size_t count, const T **dev_out) {
   return MT_OK;
 }
 
+// `kernel` over a flat range of n elements, one thread each in workgroups of 256; returns the launch's status
+template <typename... Params, typename... Args>
+hipError_t launch_flat(void (*kernel)(Params...), size_t n, hipStream_t stream, Args &&...args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, static_cast<Params>(args)...);
+  return hipGetLastError();
+}
+
 bool finite3(const double *p, size_t n) {
   for (size_t i = 0; i < n; i++) {
     if (!std::isfinite(p[i])) return false;
@@ -771,9 +778,8 @@ int launch_kernels(mt_scene *s, ForecastBank &B, const LaunchPlan &L, const Rend
   if (P.tile_list) {
     const int tiles_total = (int)tile_count(P.region_w, P.region_h, P.tile_w, P.tile_h);
     HIP_TRY(hipMemcpyAsync(B.d_tile_list, d_list, (size_t)P.n_tiles * 4, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((tiles_total + 255) / 256), dim3(256), 0, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 0);
-    hipLaunchKernelGGL(tile_slot_kernel, dim3((P.n_tiles + 255) / 256), dim3(256), 0, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 1);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_flat(tile_slot_kernel, (size_t)tiles_total, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 0));
+    HIP_TRY(launch_flat(tile_slot_kernel, (size_t)P.n_tiles, stream, B.d_tile_list.p, P.n_tiles, B.d_tile_slot.p, tiles_total, 1));
   }
   // (launches with a work order: order_forecast_kernel zeroes the counters on its way)
   if (!L.history && L.engine != 2) HIP_TRY(hipMemsetAsync(s->d_work, 0, 16 * sizeof(unsigned), stream));
@@ -956,6 +962,71 @@ void fill_stats(const unsigned long long *c, mt_stats *st) {
   st->bytes_vector = c[ST_BYTES_VECTOR];
 }
 
+// The frame of a host entry point -- a call that comes back with its results, and its mt_stats, on the host: what such
+// a call does around its launches.  From construction (after the argument checks) to destruction the scene counts when
+// the caller asked for `stats`, whatever mt_scene_set_stats says; every way out of the call restores the switch.
+// Between the two: begin -- the scene's work counters cleared, or left alone by a call that has none, and the first of
+// the call's two events --, the launches, then the pieces of the way back in the caller's order: mark_end,
+// counters_home, and close, which waits for the stream, checks the device status and fills `stats`.  Everything is
+// queued on the null stream.
+struct HostCall {
+  mt_scene *const s;
+  mt_stats *const stats;
+  hipEvent_t &ev0, &ev1;  // (references: a tree's two events are created inside its first call)
+  const std::chrono::steady_clock::time_point w0 = std::chrono::steady_clock::now();
+  const bool counters_were;
+  const hipStream_t stream = nullptr;
+  bool begun = false;     // ev0 is on the stream: close waits, kernel_ms is ev0 .. ev1
+  bool counters = false;  // the call has work counters: h_counters is checked and reported
+  HostCall(mt_scene *scene, mt_stats *st, hipEvent_t &e0, hipEvent_t &e1)
+      : s(scene), stats(st), ev0(e0), ev1(e1), counters_were(scene->stats_enabled) {
+    if (stats) s->stats_enabled = true;  // the caller asked for them
+  }
+  ~HostCall() { s->stats_enabled = counters_were; }
+  HostCall(const HostCall &) = delete;
+  HostCall &operator=(const HostCall &) = delete;
+  int clear_counters() {
+    MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+    counters = true;
+    return MT_OK;
+  }
+  int begin(bool with_counters) {
+    if (with_counters) MT_TRY(clear_counters());
+    HIP_TRY(hipEventRecord(ev0, stream));
+    begun = true;
+    return MT_OK;
+  }
+  int mark_end() {
+    HIP_TRY(hipEventRecord(ev1, stream));
+    return MT_OK;
+  }
+  // the counters are queued for the pinned words and cleared behind the copy
+  int counters_home() {
+    HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+    return MT_OK;
+  }
+  // `stats` from what has arrived: the counters in h_counters, kernel_ms between the two events, total_ms since w0
+  int report() {
+    if (!stats) return MT_OK;
+    memset(stats, 0, sizeof *stats);
+    if (counters) fill_stats(s->h_counters, stats);
+    if (begun) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+      stats->kernel_ms = ms;
+    }
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    return MT_OK;
+  }
+  int close() {
+    if (begun) HIP_TRY(hipStreamSynchronize(stream));
+    if (counters) MT_TRY(check_status(s->h_counters));
+    return report();
+  }
+};
+
 int check_image_args(const mt_scene *s, const mt_sensor *sensor, int image_w, int image_h) {
   if (!s) return fail(MT_ERR_ARG, "scene is NULL");
   if (!sensor) return fail(MT_ERR_ARG, "sensor is NULL");
@@ -1042,17 +1113,15 @@ int launch_resolve(int ss, int image_w, int image_h, int tile_w, int tile_h, int
 
 // The two halves of a chunk call with host output around its launches.  begin: the scene's buffers for npx pixels,
 // cleared counters, the first event.
-int begin_host_chunk(mt_scene *s, size_t npx, bool debug, hipStream_t stream) {
+int begin_host_chunk(HostCall &call, size_t npx, bool debug) {
+  mt_scene *s = call.s;
   MT_TRY(s->d_rgb.ensure(npx * 3));
   if (debug) MT_TRY(s->d_debug.ensure(npx * sizeof(mt_debug_px)));
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(s->h_stage.ensure(npx * 3));
   for (hipEvent_t &e : s->ev_stage) {
     if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(s->ev0, stream));
-  return MT_OK;
+  return call.begin(true);
 }
 
 // finish: the chunk in s->d_rgb (and s->d_debug) reaches the caller, with the counters and times of the launches.
@@ -1062,13 +1131,13 @@ int begin_host_chunk(mt_scene *s, size_t npx, bool debug, hipStream_t stream) {
 // a copy into memory that IS registered 0.12 / 0.45 -- but keeping a caller's buffer registered across calls is not
 // safe (a vector freed and allocated again at the same address would receive its frame in the OLD pages).  So: the
 // staging buffer, in pieces, every piece's memcpy under the next piece's DMA: about the memcpy's time.
-int finish_host_chunk(mt_scene *s, size_t npx, uint8_t *out_rgb, mt_debug_px *out_debug, mt_stats *stats,
-                      std::chrono::steady_clock::time_point w0, hipStream_t stream) {
+int finish_host_chunk(HostCall &call, size_t npx, uint8_t *out_rgb, mt_debug_px *out_debug) {
+  mt_scene *s = call.s;
+  const hipStream_t stream = call.stream;
   const size_t out_bytes = npx * 3;
-  HIP_TRY(hipEventRecord(s->ev1, stream));
+  MT_TRY(call.mark_end());
   // everything that comes back is queued behind the kernels: the counters (device status), the frame in pieces
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+  MT_TRY(call.counters_home());
   const int n_pieces = out_bytes < (1u << 20) ? 1 : (out_bytes < (8u << 20) ? 4 : mt_scene::kStagePieces);
   const size_t piece = ((out_bytes + n_pieces - 1) / n_pieces + 4095) & ~(size_t)4095;
   for (int k = 0; k < n_pieces; k++) {
@@ -1090,18 +1159,7 @@ int finish_host_chunk(mt_scene *s, size_t npx, uint8_t *out_rgb, mt_debug_px *ou
     }
     if (off < out_bytes) memcpy(out_rgb + off, s->h_stage + off, std::min(piece, out_bytes - off));
   }
-  HIP_TRY(hipStreamSynchronize(stream));
-  MT_TRY(check_status(s->h_counters));
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    fill_stats(s->h_counters, stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  return call.close();
 }
 
 }  // namespace
@@ -1851,11 +1909,10 @@ int mt_scene_export_costs_device(mt_scene *s, void *d_map, int map_w, int map_h,
   if (P.n_items == 0) return MT_OK;
   const double *tv = s->tune.v;
   const bool hy = s->bank0.last_engine == 3;
-  hipLaunchKernelGGL(export_costs_kernel, dim3((P.n_items + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, s->bank0.last_engine,
-                     (float)(hy ? tv[MT_TUNE_HYBRID_WORK1] : tv[MT_TUNE_POOL_PIECE_WORK1]),
-                     (float)(hy ? tv[MT_TUNE_HYBRID_WORK2] : tv[MT_TUNE_POOL_PIECE_WORK2]), (float)tv[MT_TUNE_SM_CELL_WORK],
-                     (const unsigned char *)s->bank0.d_item_form, (unsigned *)d_map, map_w, map_h);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_flat(export_costs_kernel, (size_t)P.n_items, (hipStream_t)stream, P, s->bank0.last_engine,
+                      (float)(hy ? tv[MT_TUNE_HYBRID_WORK1] : tv[MT_TUNE_POOL_PIECE_WORK1]),
+                      (float)(hy ? tv[MT_TUNE_HYBRID_WORK2] : tv[MT_TUNE_POOL_PIECE_WORK2]), (float)tv[MT_TUNE_SM_CELL_WORK],
+                      (const unsigned char *)s->bank0.d_item_form, (unsigned *)d_map, map_w, map_h));
   return MT_OK;
 }
 
@@ -2007,10 +2064,9 @@ int mt_order_tiles_device(mt_scene *s, const void *d_cost_map, int map_w, int ma
   HIP_TRY(hipSetDevice(s->device));
   MT_TRY(s->d_tile_cost.ensure((size_t)total * 8));
   const int n = (int)total;
-  hipLaunchKernelGGL(tile_cost_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const unsigned *)d_cost_map,
-                     map_w, map_h, image_w, image_h, tile_w, tile_h, tiles_x, n, s->d_tile_cost);
-  hipLaunchKernelGGL(tile_order_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->d_tile_cost, n, (int32_t *)d_order);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_flat(tile_cost_kernel, (size_t)n, (hipStream_t)stream, (const unsigned *)d_cost_map, map_w, map_h, image_w,
+                      image_h, tile_w, tile_h, tiles_x, n, s->d_tile_cost.p));
+  HIP_TRY(launch_flat(tile_order_kernel, (size_t)n, (hipStream_t)stream, s->d_tile_cost.p, n, (int32_t *)d_order));
   return MT_OK;
 }
 
@@ -2030,9 +2086,8 @@ int mt_deal_tiles_device(mt_scene *s, const void *d_order, int image_w, int imag
   if (n <= 0) return n;
   const int total = (int)tile_count(image_w, image_h, tile_w, tile_h);
   HIP_TRY(hipSetDevice(s->device));
-  hipLaunchKernelGGL(deal_tiles_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int32_t *)d_order, total,
-                     world, rank, n, (int32_t *)d_list);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_flat(deal_tiles_kernel, (size_t)n, (hipStream_t)stream, (const int32_t *)d_order, total, world, rank, n,
+                      (int32_t *)d_list));
   return n;
 }
 
@@ -2067,20 +2122,14 @@ int mt_render_chunk(mt_scene *s, const mt_sensor *sensor, int image_w, int image
                     int chunk_y, int chunk_w, int chunk_h, int max_depth, uint8_t *out_rgb,
                     mt_debug_px *out_debug, mt_stats *stats) {
   if (!out_rgb) return fail(MT_ERR_ARG, "out_rgb is NULL");
-  int rc = check_image_args(s, sensor, image_w, image_h);
-  if (rc != MT_OK) return rc;
-  const auto w0 = std::chrono::steady_clock::now();
+  MT_TRY(check_image_args(s, sensor, image_w, image_h));
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)(chunk_w > 0 ? chunk_w : 0) * (size_t)(chunk_h > 0 ? chunk_h : 0);
-  hipStream_t stream = nullptr;
-  MT_TRY(begin_host_chunk(s, npx, out_debug != nullptr, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  rc = mt_render_chunk_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h,
-                              max_depth, s->d_rgb, out_debug ? s->d_debug.p : nullptr, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  MT_TRY(finish_host_chunk(s, npx, out_rgb, out_debug, stats, w0, stream));
+  MT_TRY(begin_host_chunk(call, npx, out_debug != nullptr));
+  MT_TRY(mt_render_chunk_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, max_depth, s->d_rgb,
+                                out_debug ? s->d_debug.p : nullptr, call.stream));
+  MT_TRY(finish_host_chunk(call, npx, out_rgb, out_debug));
 #ifdef MT_PROF
   {  // (the phase profile is printed by mt_scene_read_stats)
     mt_stats dummy;
@@ -2120,18 +2169,13 @@ int mt_render_chunk_ss(mt_scene *s, const mt_sensor *sensor, int image_w, int im
   MT_TRY(check_image_args(s, sensor, ss * image_w, ss * image_h));
   if (!out_rgb) return fail(MT_ERR_ARG, "out_rgb is NULL");
   MT_TRY(check_chunk(image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * chunk_h;
-  hipStream_t stream = nullptr;
-  MT_TRY(begin_host_chunk(s, npx, false, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = mt_render_chunk_ss_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss,
-                                           max_depth, s->d_rgb, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  return finish_host_chunk(s, npx, out_rgb, nullptr, stats, w0, stream);
+  MT_TRY(begin_host_chunk(call, npx, false));
+  MT_TRY(mt_render_chunk_ss_device(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, max_depth, s->d_rgb,
+                                   call.stream));
+  return finish_host_chunk(call, npx, out_rgb, nullptr);
 }
 
 int mt_resolve_tiles_device(mt_scene *s, int image_w, int image_h, int tile_w, int tile_h, int first_tile,
@@ -2321,23 +2365,18 @@ int mt_render_chunk_adaptive(mt_scene *s, const mt_sensor *sensor, const mt_sens
                              uint8_t *out_rgb, uint8_t *out_mask, mt_adaptive_info *info, mt_stats *stats) {
   MT_TRY(check_adaptive_args(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
                              out_rgb, "out_rgb"));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * chunk_h;
   const RefineArgs M = refine_args(image_w, chunk_x, chunk_y, chunk_w, chunk_h, threshold);
   const size_t n_blocks = (size_t)M.mask_w * (size_t)M.mask_h;
-  hipStream_t stream = nullptr;
-  MT_TRY(begin_host_chunk(s, npx, false, stream));
+  MT_TRY(begin_host_chunk(call, npx, false));
   if (out_mask) MT_TRY(s->d_ad_mask.ensure(n_blocks));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
   bool synced = false;
-  const int rc = render_adaptive(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold,
-                                 max_depth, s->d_rgb, out_mask ? s->d_ad_mask.p : nullptr, info, stream, &synced);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, s->d_ad_mask, n_blocks, hipMemcpyDeviceToHost, stream));
-  MT_TRY(finish_host_chunk(s, npx, out_rgb, nullptr, stats, w0, stream));
+  MT_TRY(render_adaptive(s, sensor, sensor_ss, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, ss, threshold, max_depth,
+                         s->d_rgb, out_mask ? s->d_ad_mask.p : nullptr, info, call.stream, &synced));
+  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, s->d_ad_mask, n_blocks, hipMemcpyDeviceToHost, call.stream));
+  MT_TRY(finish_host_chunk(call, npx, out_rgb, nullptr));
   if (stats && synced) {  // (the stream idled between these two while the host read the count)
     float idle = 0;
     HIP_TRY(hipEventElapsedTime(&idle, s->ev_ad[0], s->ev_ad[1]));
@@ -2436,7 +2475,8 @@ int launch_gbuffer(mt_scene *s, const mt_sensor *sensor, int chunk_x, int chunk_
 
 // The host calls' way back: planes in device buffers reach the caller through the page-locked staging buffer in
 // pieces of at most 4 MB, every piece's memcpy under the next piece's DMA (finish_host_chunk's path).  The counters
-// travel first: no planes of a failed launch.  h_stage must hold staged_bytes(planes); ends with the stream idle.
+// travel first: no planes of a failed launch.  h_stage must hold staged_bytes(planes); ends with the stream idle and
+// the call closed.
 struct PlaneCopy { void *host; const void *dev; size_t bytes; };
 
 size_t staged_bytes(const std::vector<PlaneCopy> &planes) {
@@ -2445,9 +2485,10 @@ size_t staged_bytes(const std::vector<PlaneCopy> &planes) {
   return total;
 }
 
-int planes_to_host(mt_scene *s, const std::vector<PlaneCopy> &planes, hipStream_t stream) {
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
+int planes_to_host(HostCall &call, const std::vector<PlaneCopy> &planes) {
+  mt_scene *s = call.s;
+  const hipStream_t stream = call.stream;
+  MT_TRY(call.counters_home());
   struct Piece { uint8_t *dst; size_t off, bytes; };
   std::vector<Piece> pieces;
   constexpr size_t kPiece = 4u << 20;
@@ -2474,8 +2515,7 @@ int planes_to_host(mt_scene *s, const std::vector<PlaneCopy> &planes, hipStream_
     }
     memcpy(pieces[k].dst, s->h_stage + pieces[k].off, pieces[k].bytes);
   }
-  HIP_TRY(hipStreamSynchronize(stream));
-  return check_status(s->h_counters);
+  return call.close();
 }
 
 // Scene-owned device buffers for the planes of `host` that are set (the host calls): the device-side mt_gbuffer in
@@ -2494,17 +2534,6 @@ int scene_planes(mt_scene *s, const mt_gbuffer &host_gb, size_t npx, mt_gbuffer 
   return MT_OK;
 }
 
-// kernel_ms between the scene's two events, total_ms since w0, the counters the launch left in h_counters
-int fill_call_stats(mt_scene *s, mt_stats *stats, std::chrono::steady_clock::time_point w0) {
-  memset(stats, 0, sizeof *stats);
-  fill_stats(s->h_counters, stats);
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-  stats->kernel_ms = ms;
-  stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  return MT_OK;
-}
-
 }  // namespace
 
 int mt_render_gbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
@@ -2518,26 +2547,17 @@ int mt_render_gbuffer_device(mt_scene *s, const mt_sensor *sensor, int image_w, 
 int mt_render_gbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
                       int chunk_w, int chunk_h, const mt_gbuffer *out, mt_stats *stats) {
   MT_TRY(check_gbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, out));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
-  hipStream_t stream = nullptr;
   std::vector<PlaneCopy> copies;
   mt_gbuffer d{};
   MT_TRY(scene_planes(s, *out, npx, &d, &copies));
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(s->ev0, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = launch_gbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, stream));
-  MT_TRY(planes_to_host(s, copies, stream));
-  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
-  return MT_OK;
+  MT_TRY(call.begin(true));
+  MT_TRY(launch_gbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d, call.stream));
+  MT_TRY(call.mark_end());
+  return planes_to_host(call, copies);
 }
 
 // ---- the direct-light buffer and the relight pass (mt_lightbuffer.h).  Like the G-buffer calls, nothing here reads
@@ -2708,11 +2728,10 @@ int mt_render_lightbuffer_device(mt_scene *s, const mt_sensor *sensor, int image
 int mt_render_lightbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
                           int chunk_w, int chunk_h, const mt_gbuffer *gb, const mt_lightbuffer *lb, mt_stats *stats) {
   MT_TRY(check_lightbuffer_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, gb, lb));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
   const size_t n_l = (size_t)s->dev.n_lights;
-  hipStream_t stream = nullptr;
   std::vector<PlaneCopy> copies;
   mt_gbuffer d{};
   if (gb) MT_TRY(scene_planes(s, *gb, npx, &d, &copies));
@@ -2727,19 +2746,11 @@ int mt_render_lightbuffer(mt_scene *s, const mt_sensor *sensor, int image_w, int
     dl.in_shadow = s->d_lb_shadow;
     copies.push_back({lb->in_shadow, dl.in_shadow, n_l * npx});
   }
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(s->ev0, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = launch_lightbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, gb ? &d : nullptr, dl, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, stream));
-  MT_TRY(planes_to_host(s, copies, stream));
-  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
-  return MT_OK;
+  MT_TRY(call.begin(true));
+  MT_TRY(launch_lightbuffer(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, gb ? &d : nullptr, dl, call.stream));
+  MT_TRY(call.mark_end());
+  return planes_to_host(call, copies);
 }
 
 int mt_shade_direct_device(mt_scene *s, const mt_sensor *sensor, int image_w, int image_h, int chunk_x, int chunk_y,
@@ -2758,11 +2769,11 @@ int mt_shade_direct(mt_scene *s, const mt_sensor *sensor, int image_w, int image
                     int n_lights, uint8_t *out_rgb, mt_stats *stats) {
   MT_TRY(check_shade_args(s, sensor, image_w, image_h, chunk_x, chunk_y, chunk_w, chunk_h, gb, lb, lights, n_lights,
                           out_rgb));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
   const size_t n_l = (size_t)n_lights;
-  hipStream_t stream = nullptr;
+  const hipStream_t stream = call.stream;
   MT_TRY(s->d_gb_f64[1].ensure(npx * 24));
   MT_TRY(s->d_gb_f64[2].ensure(npx * 24));
   MT_TRY(s->d_gb_f64[4].ensure(npx * 24));
@@ -2781,19 +2792,11 @@ int mt_shade_direct(mt_scene *s, const mt_sensor *sensor, int image_w, int image
     HIP_TRY(hipMemcpyAsync(dl.power, lb->power, n_l * npx * 24, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(dl.in_shadow, lb->in_shadow, n_l * npx, hipMemcpyHostToDevice, stream));
   }
-  HIP_TRY(hipEventRecord(s->ev0, stream));
+  MT_TRY(call.begin(false));  // (no ray, no traversal: every work counter is zero)
   MT_TRY(launch_shade_direct(s, sensor, chunk_x, chunk_y, chunk_w, chunk_h, d, dl, lights, n_lights, s->d_rgb, stream));
-  HIP_TRY(hipEventRecord(s->ev1, stream));
+  MT_TRY(call.mark_end());
   HIP_TRY(hipMemcpyAsync(out_rgb, s->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  return call.close();
 }
 
 int mt_update_lightbuffer_device(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *d_gb, const int32_t *light_idx,
@@ -2809,11 +2812,11 @@ int mt_update_lightbuffer_device(mt_scene *s, int chunk_w, int chunk_h, const mt
 int mt_update_lightbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb, const int32_t *light_idx, int n_idx,
                           const mt_lightbuffer *lb, mt_stats *stats) {
   MT_TRY(check_update_args(s, chunk_w, chunk_h, gb, light_idx, n_idx, lb));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
   const size_t n_l = (size_t)s->dev.n_lights;
-  hipStream_t stream = nullptr;
+  const hipStream_t stream = call.stream;
   MT_TRY(s->d_gb_f64[1].ensure(npx * 24));
   MT_TRY(s->d_gb_i32[2].ensure(npx * 4));
   mt_gbuffer d{};
@@ -2833,21 +2836,13 @@ int mt_update_lightbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffe
     if (lb->power) copies.push_back({lb->power + l * npx * 3, dl.power + l * npx * 3, npx * 24});
     if (lb->in_shadow) copies.push_back({lb->in_shadow + l * npx, dl.in_shadow + l * npx, npx});
   }
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(s->h_stage.ensure(staged_bytes(copies)));
   HIP_TRY(hipMemcpyAsync(d.point, gb->point, npx * 24, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(d.material, gb->material, npx * 4, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(s->ev0, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = launch_lightbuffer_update(s, chunk_w, chunk_h, d, light_idx, n_idx, dl, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, stream));
-  MT_TRY(planes_to_host(s, copies, stream));
-  if (stats) MT_TRY(fill_call_stats(s, stats, w0));
-  return MT_OK;
+  MT_TRY(call.begin(true));
+  MT_TRY(launch_lightbuffer_update(s, chunk_w, chunk_h, d, light_idx, n_idx, dl, stream));
+  MT_TRY(call.mark_end());
+  return planes_to_host(call, copies);
 }
 
 // ---- edited textures and the deferred path (mt_gbuffer.h, gbuffer_retexture_kernel): stateless, like
@@ -2882,8 +2877,7 @@ int launch_gbuffer_retexture(mt_scene *s, size_t npx, const mt_gbuffer &d_gb, hi
   A.texs = s->dev.texs;
   A.n = npx;
   A.n_materials = s->n_materials;
-  hipLaunchKernelGGL(gbuffer_retexture_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, A);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_flat(gbuffer_retexture_kernel, npx, stream, A));
   return MT_OK;
 }
 
@@ -2898,10 +2892,10 @@ int mt_retexture_gbuffer_device(mt_scene *s, int chunk_w, int chunk_h, const mt_
 // The host form: material and uvw go up into the scene's G-buffer buffers, only the albedo comes back.
 int mt_retexture_gbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer *gb, mt_stats *stats) {
   MT_TRY(check_retexture_args(s, chunk_w, chunk_h, gb));
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(s, stats, s->ev0, s->ev1);
   HIP_TRY(hipSetDevice(s->device));
   const size_t npx = (size_t)chunk_w * (size_t)chunk_h;
-  hipStream_t stream = nullptr;
+  const hipStream_t stream = call.stream;
   MT_TRY(s->d_gb_i32[2].ensure(npx * 4));
   MT_TRY(s->d_gb_f64[4].ensure(npx * 24));
   mt_gbuffer d{};
@@ -2912,19 +2906,11 @@ int mt_retexture_gbuffer(mt_scene *s, int chunk_w, int chunk_h, const mt_gbuffer
     d.uvw = s->d_gb_f64[3];
     HIP_TRY(hipMemcpyAsync(d.uvw, gb->uvw, npx * 24, hipMemcpyHostToDevice, stream));
   }
-  HIP_TRY(hipEventRecord(s->ev0, stream));
+  MT_TRY(call.begin(false));  // (no ray, no traversal: every work counter is zero)
   MT_TRY(launch_gbuffer_retexture(s, npx, d, stream));
-  HIP_TRY(hipEventRecord(s->ev1, stream));
+  MT_TRY(call.mark_end());
   HIP_TRY(hipMemcpyAsync(gb->albedo, d.albedo, npx * 24, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (stats) {  // (no ray, no traversal: every work counter is zero)
-    memset(stats, 0, sizeof *stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  return call.close();
 }
 
 // ---- the ray-tree buffer (mt_raytree.h).  Like the G-buffer and light-buffer calls, nothing here reads or writes what
@@ -3176,10 +3162,7 @@ int raytree_import_rays(mt_raytree *t, const mt_ray_list *rays, bool on_device, 
   unsigned int bad[2] = {0u, 0xffffffffu};
   hipError_t e = hipMemsetAsync(t->d_bad, 0, sizeof(unsigned int), stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_bad + 1, 0xff, sizeof(unsigned int), stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(raytree_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess) e = launch_flat(raytree_rays_kernel, n, stream, A);
   if (e == hipSuccess) e = hipMemcpyAsync(bad, t->d_bad, sizeof bad, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return release(fail(MT_ERR_HIP, "importing the ray list failed: %s", hipGetErrorString(e)));
@@ -3215,20 +3198,38 @@ int launch_raytree_trace(mt_raytree *t, const RayTreeLayer &L, size_t n, int k, 
 
 // Layer after layer: trace, compact, (host: size the next layer), spawn.  Layer 0 comes from the tree's sensor, or from
 // `rays` (a ray-list tree; on_device: its pointers are device pointers).
+// a new tree of scene s with what the scene's switches and lights say now; the caller sets its geometry and depth
+mt_raytree *raytree_new(mt_scene *s) {
+  mt_raytree *t = new mt_raytree();
+  t->scene = s;
+  t->keep_uvw = s->raytree_uvw != 0;
+  t->keep_tri = s->raytree_tri != 0;
+  t->info.n_lights = s->dev.n_lights;
+  return t;
+}
+
+// the tree's snapshot of what its planes are valid for: the scene's materials, textures and assignment as they are now
+void raytree_snapshot(mt_raytree *t) {
+  const mt_scene *s = t->scene;
+  t->mtls = s->mtls_host;
+  t->mtl_generation = s->mtl_generation;
+  t->tex_generation = s->tex_generation;
+  t->tri_mtl = s->tri_mtl_host;
+  t->asg_generation = s->asg_generation;
+}
+
 int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_stats *stats) {
   mt_scene *s = t->scene;
-  const auto w0 = std::chrono::steady_clock::now();
-  hipStream_t stream = nullptr;
+  HostCall call(s, stats, t->ev0, t->ev1);
+  const hipStream_t stream = call.stream;
   const mt_raytree_desc &I = t->info;
   const size_t npx = (size_t)I.chunk_w * (size_t)I.chunk_h;
   if (npx >= 0x80000000ull) return fail(MT_ERR_UNSUPPORTED, "layer 0 of the ray tree would have %zu rays (2^31 or more)", npx);
   HIP_TRY(hipEventCreate(&t->ev0));
   HIP_TRY(hipEventCreate(&t->ev1));
   MT_TRY(raytree_malloc((void **)&t->d_count, sizeof(unsigned long long), "the ray tree's child count"));
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(raytree_alloc_layer(t, 0, npx));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(t->ev0, stream));
+  MT_TRY(call.begin(true));
   if (rays) {
     MT_TRY(raytree_import_rays(t, rays, on_device, stream));
   } else {
@@ -3236,8 +3237,7 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
     A.sensor = t->sensor;
     A.chunk_x = I.chunk_x; A.chunk_y = I.chunk_y; A.chunk_w = I.chunk_w; A.chunk_h = I.chunk_h;
     A.L = t->layer[0];
-    hipLaunchKernelGGL(raytree_primary_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, A);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_flat(raytree_primary_kernel, npx, stream, A));
   }
   for (int k = 0;; k++) {
     const size_t n = (size_t)I.n_rays[k];
@@ -3263,31 +3263,18 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
     SA.child = t->layer[k + 1];
     SA.n_parent = (uint32_t)n;
     SA.mtls = s->dev.mtls;
-    hipLaunchKernelGGL(raytree_spawn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, SA);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_flat(raytree_spawn_kernel, n, stream, SA));
   }
-  HIP_TRY(hipEventRecord(t->ev1, stream));
-  MT_TRY(raytree_read_counters(s, stream));
+  MT_TRY(call.mark_end());
+  MT_TRY(raytree_read_counters(s, stream));  // (the last layer's status, checked before the counters are cleared)
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
   for (int k = 0; k < I.n_layers; k++) {
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, t->ev_layer[k][0], t->ev_layer[k][1]));
     t->info.trace_ms[k] = ms;
   }
-  t->mtls = s->mtls_host;
-  t->mtl_generation = s->mtl_generation;
-  t->tex_generation = s->tex_generation;
-  t->tri_mtl = s->tri_mtl_host;
-  t->asg_generation = s->asg_generation;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    fill_stats(s->h_counters, stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  raytree_snapshot(t);
+  return call.report();
 }
 
 // raytree_shade_kernel over the layers, deepest first; d_rgb, d_color = device pointers, either may be nullptr: layer 0
@@ -3306,27 +3293,21 @@ int launch_raytree_shade(mt_raytree *t, const mt_light *lights, int n_lights, ui
     HIP_TRY(hipMemcpyAsync(s->d_shade_lights, lights, (size_t)n_lights * sizeof(mt_light), hipMemcpyHostToDevice, stream));
     A.d_lights = s->d_shade_lights;
   }
+  void (*const shade)(RayTreeShadeArgs) = in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>;
   for (int k = t->info.n_layers - 1; k >= 0; k--) {
     const size_t n = (size_t)t->info.n_rays[k];
     A.L = t->layer[k];
     A.child_color = k + 1 < t->info.n_layers ? t->layer[k + 1].color : nullptr;
     A.n_rays = (uint32_t)n;
     A.out_rgb = nullptr;
-    if (k > 0 || d_color != nullptr) {
-      hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>,
-                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-      HIP_TRY(hipGetLastError());
-    }
+    if (k > 0 || d_color != nullptr) HIP_TRY(launch_flat(shade, n, stream, A));
     if (k == 0 && d_color != nullptr) {
-      hipLaunchKernelGGL(raytree_color_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                         (const double *)A.L.color, (const int32_t *)A.L.pixel, (uint32_t)n, d_color);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_flat(raytree_color_kernel, n, stream, (const double *)A.L.color, (const int32_t *)A.L.pixel,
+                          (uint32_t)n, d_color));
     }
     if (k == 0 && d_rgb != nullptr) {
       A.out_rgb = d_rgb;
-      hipLaunchKernelGGL(in_args ? raytree_shade_kernel<true> : raytree_shade_kernel<false>,
-                         dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_flat(shade, n, stream, A));
     }
   }
   return MT_OK;
@@ -3370,19 +3351,12 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
     (void)fail(MT_ERR_HIP, "hipSetDevice(%d) failed", s->device);
     return nullptr;
   }
-  mt_raytree *t = new mt_raytree();
-  t->scene = s;
-  t->keep_uvw = s->raytree_uvw != 0;
-  t->keep_tri = s->raytree_tri != 0;
+  mt_raytree *t = raytree_new(s);
   t->sensor = *sensor;
-  t->info.n_lights = s->dev.n_lights;
   t->info.image_w = image_w; t->info.image_h = image_h;
   t->info.chunk_x = chunk_x; t->info.chunk_y = chunk_y; t->info.chunk_w = chunk_w; t->info.chunk_h = chunk_h;
   t->info.max_depth = max_depth;
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
   const int rc = raytree_build(t, nullptr, false, stats);
-  s->stats_enabled = counters_were;
   if (rc != MT_OK) {
     const std::string why = g_err;  // (the text survives the clean-up)
     mt_raytree_destroy(t);
@@ -3400,19 +3374,12 @@ int raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_
   *out = nullptr;
   MT_TRY(check_raytree_rays_args(s, rays, max_depth, !on_device));
   if (hipSetDevice(s->device) != hipSuccess) return fail(MT_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-  mt_raytree *t = new mt_raytree();
-  t->scene = s;
-  t->keep_uvw = s->raytree_uvw != 0;
-  t->keep_tri = s->raytree_tri != 0;
-  t->info.n_lights = s->dev.n_lights;
+  mt_raytree *t = raytree_new(s);
   t->info.image_w = t->info.chunk_w = rays->list_w;
   t->info.image_h = t->info.chunk_h = rays->list_h;
   t->info.max_depth = max_depth;
   t->info.from_rays = 1;
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
   const int rc = raytree_build(t, rays, on_device, stats);
-  s->stats_enabled = counters_were;
   if (rc != MT_OK) {
     const std::string why = g_err;  // (the text survives the clean-up)
     mt_raytree_destroy(t);
@@ -3521,26 +3488,18 @@ namespace {
 // the host forms of the shade: bytes, colours or both, whichever is not NULL
 int raytree_shade_host(mt_raytree *t, const mt_light *lights, int n_lights, uint8_t *out_rgb, double *out_color,
                        mt_stats *stats) {
-  const auto w0 = std::chrono::steady_clock::now();
+  HostCall call(t->scene, stats, t->ev0, t->ev1);
   HIP_TRY(hipSetDevice(t->scene->device));
   const size_t npx = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
-  hipStream_t stream = nullptr;
+  const hipStream_t stream = call.stream;
   if (out_rgb && !t->d_rgb) MT_TRY(raytree_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
   if (out_color && !t->d_out_color) MT_TRY(raytree_malloc((void **)&t->d_out_color, npx * 24, "the ray tree's colours"));
-  HIP_TRY(hipEventRecord(t->ev0, stream));
+  MT_TRY(call.begin(false));  // (no ray, no traversal: every work counter is zero)
   MT_TRY(launch_raytree_shade(t, lights, n_lights, out_rgb ? t->d_rgb : nullptr, out_color ? t->d_out_color : nullptr, stream));
-  HIP_TRY(hipEventRecord(t->ev1, stream));
+  MT_TRY(call.mark_end());
   if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, t->d_rgb, npx * 3, hipMemcpyDeviceToHost, stream));
   if (out_color) HIP_TRY(hipMemcpyAsync(out_color, t->d_out_color, npx * 24, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  return call.close();
 }
 
 }  // namespace
@@ -3585,32 +3544,14 @@ int mt_raytree_update_lights_device(mt_raytree *t, const int32_t *light_idx, int
 // The host form: the tree's planes are where they are; only the counters come back.
 int mt_raytree_update_lights(mt_raytree *t, const int32_t *light_idx, int n_idx, mt_stats *stats) {
   MT_TRY(check_raytree_update_args(t, light_idx, n_idx));
-  const auto w0 = std::chrono::steady_clock::now();
   mt_scene *s = t->scene;
+  HostCall call(s, stats, t->ev0, t->ev1);
   HIP_TRY(hipSetDevice(s->device));
-  hipStream_t stream = nullptr;
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(t->ev0, stream));
-  const bool counters_were = s->stats_enabled;
-  if (stats) s->stats_enabled = true;  // the caller asked for them
-  const int rc = launch_raytree_update(t, light_idx, n_idx, stream);
-  s->stats_enabled = counters_were;
-  if (rc != MT_OK) return rc;
-  HIP_TRY(hipEventRecord(t->ev1, stream));
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  MT_TRY(check_status(s->h_counters));
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    fill_stats(s->h_counters, stats);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
-  return MT_OK;
+  MT_TRY(call.begin(true));
+  MT_TRY(launch_raytree_update(t, light_idx, n_idx, call.stream));
+  MT_TRY(call.mark_end());
+  MT_TRY(call.counters_home());
+  return call.close();
 }
 
 namespace {
@@ -3688,10 +3629,37 @@ int raytree_scratch(void **p, size_t *cap, size_t bytes, const char *what) {
   return MT_OK;
 }
 
+// D.albedo_changed in the tree's byte per material on the device (made on first use)
+int raytree_upload_albedo_changed(mt_raytree *t, const MaterialDiff &D, hipStream_t stream) {
+  const size_t n_mtl = (size_t)t->scene->n_materials;
+  if (!t->d_albedo_changed) {
+    MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, n_mtl, "the ray tree's material flags"));
+  }
+  HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), n_mtl, hipMemcpyHostToDevice, stream));
+  return MT_OK;
+}
+
+// raytree_recommit_kernel's arguments for the n rays of layer L under the edit D
+RayTreeRecommitArgs raytree_recommit_args(const mt_raytree *t, const MaterialDiff &D, const RayTreeLayer &L, size_t n,
+                                          int copy_coef) {
+  const mt_scene *s = t->scene;
+  RayTreeRecommitArgs A{};
+  A.L = L;
+  A.mtls = s->dev.mtls;
+  A.texs = s->dev.texs;
+  A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
+  A.tri_mtl = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
+  A.n_rays = (uint32_t)n;
+  A.n_materials = s->n_materials;
+  A.copy_coef = copy_coef;
+  return A;
+}
+
 // mt_raytree_regrow_materials after a check pass that found mismatches: the new tree under the scene's current
 // materials, built layer by layer next to the old one (mt_raytree.h, "edited materials that change the tree's shape"),
 // then swapped in.  Until the swap only scratch and the new allocations are written: a failure before it leaves every
-// plane of the tree as it was.  The scene's counters are zero at entry and hold the tracing launches' sums at exit.
+// plane of the tree as it was.  The scene's counters are zero at entry (HostCall::clear_counters) and hold the tracing
+// launches' sums at exit.
 int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info *info, hipStream_t stream) {
   mt_scene *s = t->scene;
   mt_raytree_desc &I = t->info;
@@ -3709,7 +3677,6 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     }
     return rc;
   };
-  const auto grid_of = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
   // layer 0 stays where it is; its child indices and spawn bytes are built in scratch and its albedo waits for the commit
   const size_t n0 = (size_t)I.n_rays[0];
   const size_t idx_bytes = (n0 * 4 + 255) & ~(size_t)255;
@@ -3719,13 +3686,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   NL[0].child_refr = (int32_t *)((char *)t->d_regrow0 + idx_bytes);
   NL[0].spawn = (uint8_t *)t->d_regrow0 + 2 * idx_bytes;
   n_new[0] = n0;
-  if (D.albedo) {
-    if (!t->d_albedo_changed) {
-      MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
-    }
-    HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
-  }
-  MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
+  if (D.albedo) MT_TRY(raytree_upload_albedo_changed(t, D, stream));
   int new_layers = 0;
   for (int k = 0;; k++) {
     const size_t n = n_new[k];
@@ -3739,8 +3700,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.n_rays = (uint32_t)n;
       A.n_materials = n_mtl;
       A.may_spawn = k < I.max_depth ? 1 : 0;
-      hipLaunchKernelGGL(raytree_regrow_flags_kernel, grid_of(n), dim3(256), 0, stream, A);
-      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's flags kernel failed"));
+      if (launch_flat(raytree_regrow_flags_kernel, n, stream, A) != hipSuccess) {
+        return release(fail(MT_ERR_HIP, "launching the regrow's flags kernel failed"));
+      }
     }
     new_layers = k + 1;
     if (k == I.max_depth) {  // no ray of the deepest layer has a child
@@ -3786,8 +3748,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.mtls = s->dev.mtls;
       A.tri_mtl = k == 0 ? tri_mtl_now : nullptr;
       A.n_parent = (uint32_t)n;
-      hipLaunchKernelGGL(raytree_regrow_link_kernel, grid_of(n), dim3(256), 0, stream, A);
-      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's link kernel failed"));
+      if (launch_flat(raytree_regrow_link_kernel, n, stream, A) != hipSuccess) {
+        return release(fail(MT_ERR_HIP, "launching the regrow's link kernel failed"));
+      }
     }
     if (k + 1 < old_layers) {  // (else no ray of layer k + 1 has an old index)
       RayTreeRegrowCopyArgs A{};
@@ -3802,8 +3765,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.texs = s->dev.texs;
       A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
       A.tri_mtl = tri_mtl_now;
-      hipLaunchKernelGGL(raytree_regrow_copy_kernel, grid_of(n1), dim3(256), 0, stream, A);
-      if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
+      if (launch_flat(raytree_regrow_copy_kernel, n1, stream, A) != hipSuccess) {
+        return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
+      }
     }
     // the traced rays of layer k + 1: the link kernel left 1 in their spawn bytes, so the layer's own compaction gives
     // their places in the dense list (child_refl) and their number
@@ -3828,11 +3792,13 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     A.n_rays = (uint32_t)n1;
     A.n_list = (uint32_t)m;
     A.n_lights = I.n_lights;
-    hipLaunchKernelGGL(raytree_regrow_gather_kernel, grid_of(n1), dim3(256), 0, stream, A);
-    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's gather kernel failed"));
+    if (launch_flat(raytree_regrow_gather_kernel, n1, stream, A) != hipSuccess) {
+      return release(fail(MT_ERR_HIP, "launching the regrow's gather kernel failed"));
+    }
     if (const int rc = launch_raytree_trace(t, A.tmp, m, k + 1, stream)) return release(rc);
-    hipLaunchKernelGGL(raytree_regrow_scatter_kernel, grid_of(n1), dim3(256), 0, stream, A);
-    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching the regrow's scatter kernel failed"));
+    if (launch_flat(raytree_regrow_scatter_kernel, n1, stream, A) != hipSuccess) {
+      return release(fail(MT_ERR_HIP, "launching the regrow's scatter kernel failed"));
+    }
   }
   // the last tracing launch's status; nothing of the old tree has been written so far, and nothing below fails for size
   if (const int rc = raytree_read_counters(s, stream)) return release(rc);
@@ -3842,17 +3808,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     return release(fail(MT_ERR_HIP, "writing layer 0's child indices failed"));
   }
   if (D.albedo || tri_mtl_now != nullptr) {
-    RayTreeRecommitArgs A{};
-    A.L = t->layer[0];
-    A.mtls = s->dev.mtls;
-    A.texs = s->dev.texs;
-    A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
-    A.tri_mtl = tri_mtl_now;
-    A.n_rays = (uint32_t)n0;
-    A.n_materials = n_mtl;
-    A.copy_coef = 0;
-    hipLaunchKernelGGL(raytree_recommit_kernel, grid_of(n0), dim3(256), 0, stream, A);
-    if (hipGetLastError() != hipSuccess) return release(fail(MT_ERR_HIP, "launching layer 0's commit failed"));
+    if (launch_flat(raytree_recommit_kernel, n0, stream, raytree_recommit_args(t, D, t->layer[0], n0, 0)) != hipSuccess) {
+      return release(fail(MT_ERR_HIP, "launching layer 0's commit failed"));
+    }
   }
   if (hipStreamSynchronize(stream) != hipSuccess) return release(fail(MT_ERR_HIP, "the regrow's commit failed"));
   if (info) {
@@ -3885,20 +3843,10 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   return MT_OK;
 }
 
-// mt_raytree_update_materials, and mt_raytree_regrow_materials when `regrow` is set: the two calls differ in the light
-// count check and in what a check pass with mismatches leads to.
-int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytree_regrow_info *info) {
-  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
-  const auto w0 = std::chrono::steady_clock::now();
-  mt_scene *s = t->scene;
-  const mt_raytree_desc &I = t->info;
-  if (stats) memset(stats, 0, sizeof *stats);
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->n_layers_before = info->n_layers_after = I.n_layers;
-  }
-  if (t->mtl_generation == s->mtl_generation) return MT_OK;
-  MaterialDiff D;
+// What the scene's edits since the tree's snapshot ask of the tree (*out), or why the tree cannot take them
+int raytree_diff(const mt_raytree *t, MaterialDiff *out) {
+  const mt_scene *s = t->scene;
+  MaterialDiff &D = *out;
   diff_materials(t->mtls, s->mtls_host, &D);
   if (D.textured >= 0 && !t->keep_uvw) {
     return fail(MT_ERR_UNSUPPORTED, "material %d has a texture and its ambient or tex changed: the ray tree keeps neither "
@@ -3929,7 +3877,70 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     return fail(MT_ERR_UNSUPPORTED, "triangle %d was given material %d, which has a texture: the ray tree keeps no uvw "
                                     "(mt_scene_set_raytree_uvw), a new tree is needed", D.textured_tri, D.textured_tri_mtl);
   }
-  const int32_t *tri_mtl_now = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
+  return MT_OK;
+}
+
+// The check pass: raytree_recoef_kernel over every layer restates the rays' coefficients under the scene's current
+// materials (aside, in the next layer's colour plane) and counts the rays that would spawn other children: found[0]
+// of them, the first at layer found[1] >> 32, ray found[1] & 0xffffffff.  Synchronises.
+int raytree_check_pass(mt_raytree *t, const MaterialDiff &D, hipStream_t stream, unsigned long long found[2]) {
+  const mt_scene *s = t->scene;
+  const mt_raytree_desc &I = t->info;
+  if (!t->d_mismatch) {
+    MT_TRY(raytree_malloc((void **)&t->d_mismatch, 2 * sizeof(unsigned long long), "the ray tree's mismatch count"));
+  }
+  HIP_TRY(hipMemsetAsync(t->d_mismatch, 0, sizeof(unsigned long long), stream));
+  HIP_TRY(hipMemsetAsync(t->d_mismatch + 1, 0xff, sizeof(unsigned long long), stream));
+  for (int k = 0; k < I.n_layers; k++) {
+    const size_t n = (size_t)I.n_rays[k];
+    RayTreeRecoefArgs A{};
+    A.L = t->layer[k];
+    A.child_scratch = k + 1 < I.n_layers ? t->layer[k + 1].color : nullptr;
+    A.mtls = s->dev.mtls;
+    A.tri_mtl = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
+    A.n_rays = (uint32_t)n;
+    A.n_materials = s->n_materials;
+    A.layer = k;
+    A.may_spawn = k < I.max_depth ? 1 : 0;
+    A.mismatch = t->d_mismatch;
+    HIP_TRY(launch_flat(raytree_recoef_kernel, n, stream, A));
+  }
+  found[0] = found[1] = 0;
+  HIP_TRY(hipMemcpyAsync(found, t->d_mismatch, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return MT_OK;
+}
+
+// The commit of a tree that keeps its shape: raytree_recommit_kernel over the layers the edit touches
+int raytree_commit(mt_raytree *t, const MaterialDiff &D, hipStream_t stream) {
+  const mt_raytree_desc &I = t->info;
+  if (D.albedo) MT_TRY(raytree_upload_albedo_changed(t, D, stream));
+  for (int k = 0; k < I.n_layers; k++) {
+    const size_t n = (size_t)I.n_rays[k];
+    const RayTreeRecommitArgs A = raytree_recommit_args(t, D, t->layer[k], n, D.shape && k > 0 ? 1 : 0);
+    if (!A.copy_coef && !A.albedo_changed && !A.tri_mtl) continue;
+    HIP_TRY(launch_flat(raytree_recommit_kernel, n, stream, A));
+  }
+  return MT_OK;
+}
+
+// mt_raytree_update_materials, and mt_raytree_regrow_materials when `regrow` is set: the two calls differ in the light
+// count check and in what a check pass with mismatches leads to.
+int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytree_regrow_info *info) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  mt_scene *s = t->scene;
+  HostCall call(s, stats, t->ev0, t->ev1);
+  const mt_raytree_desc &I = t->info;
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->n_layers_before = info->n_layers_after = I.n_layers;
+  }
+  if (t->mtl_generation == s->mtl_generation) return MT_OK;
+  // ---- 1. the edit, and the edits this tree cannot take
+  MaterialDiff D;
+  MT_TRY(raytree_diff(t, &D));
+  // ---- 2. the lights the tracing launches would read
   const bool retrace = D.shadow && I.n_lights > 0;
   // (a regrow may trace new rays, whose light planes come from the scene's current lights)
   const bool lights_read = regrow ? (D.shape || D.shadow) && I.n_lights > 0 : retrace;
@@ -3939,33 +3950,12 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
   bool regrown = false;
   if (D.shape || D.albedo || retrace) {
     HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = nullptr;
-    const int n_mtl = s->n_materials;
-    HIP_TRY(hipEventRecord(t->ev0, stream));
+    const hipStream_t stream = call.stream;
+    MT_TRY(call.begin(false));  // (the counters are cleared where a tracing launch follows)
+    // ---- 3. the check pass
     if (D.shape) {
-      if (!t->d_mismatch) {
-        MT_TRY(raytree_malloc((void **)&t->d_mismatch, 2 * sizeof(unsigned long long), "the ray tree's mismatch count"));
-      }
-      HIP_TRY(hipMemsetAsync(t->d_mismatch, 0, sizeof(unsigned long long), stream));
-      HIP_TRY(hipMemsetAsync(t->d_mismatch + 1, 0xff, sizeof(unsigned long long), stream));
-      for (int k = 0; k < I.n_layers; k++) {
-        const size_t n = (size_t)I.n_rays[k];
-        RayTreeRecoefArgs A{};
-        A.L = t->layer[k];
-        A.child_scratch = k + 1 < I.n_layers ? t->layer[k + 1].color : nullptr;
-        A.mtls = s->dev.mtls;
-        A.tri_mtl = tri_mtl_now;
-        A.n_rays = (uint32_t)n;
-        A.n_materials = n_mtl;
-        A.layer = k;
-        A.may_spawn = k < I.max_depth ? 1 : 0;
-        A.mismatch = t->d_mismatch;
-        hipLaunchKernelGGL(raytree_recoef_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-        HIP_TRY(hipGetLastError());
-      }
-      unsigned long long found[2] = {0, 0};
-      HIP_TRY(hipMemcpyAsync(found, t->d_mismatch, sizeof found, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
+      unsigned long long found[2];
+      MT_TRY(raytree_check_pass(t, D, stream, found));
       if (found[0] != 0 && !regrow) {
         return fail(MT_ERR_UNSUPPORTED, "the new materials change the shape of the ray tree: %llu rays spawn other "
                                         "children, the first in layer %d at ray %llu; a new tree is needed",
@@ -3977,78 +3967,29 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
         if (s->dev.n_lights != I.n_lights) {
           return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", s->dev.n_lights, I.n_lights);
         }
-        HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-        const bool counters_were = s->stats_enabled;
-        if (stats) s->stats_enabled = true;  // the caller asked for them
-        const int rc = raytree_regrow(t, D, info, stream);
-        s->stats_enabled = counters_were;
-        if (rc != MT_OK) return rc;
+        // ---- 4a. the regrow, whose tracing launches count from zero
+        MT_TRY(call.clear_counters());
+        MT_TRY(raytree_regrow(t, D, info, stream));
         regrown = true;
       }
     }
-    if (!regrown) {  // the commit of a tree that keeps its shape (a regrown tree has taken everything already)
-      if (D.albedo) {
-        if (!t->d_albedo_changed) {
-          MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, (size_t)n_mtl, "the ray tree's material flags"));
-        }
-        HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), (size_t)n_mtl, hipMemcpyHostToDevice, stream));
-      }
-      for (int k = 0; k < I.n_layers; k++) {
-        const size_t n = (size_t)I.n_rays[k];
-        RayTreeRecommitArgs A{};
-        A.L = t->layer[k];
-        A.mtls = s->dev.mtls;
-        A.texs = s->dev.texs;
-        A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
-        A.tri_mtl = tri_mtl_now;
-        A.n_rays = (uint32_t)n;
-        A.n_materials = n_mtl;
-        A.copy_coef = D.shape && k > 0 ? 1 : 0;
-        if (!A.copy_coef && !A.albedo_changed && !A.tri_mtl) continue;
-        hipLaunchKernelGGL(raytree_recommit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A);
-        HIP_TRY(hipGetLastError());
-      }
-      if (info) {
-        for (int k = 0; k < I.n_layers; k++) info->kept[k] = I.n_rays[k];
-      }
+    // ---- 4b. or the commit of a tree that keeps its shape (a regrown tree has taken everything already)
+    if (!regrown) MT_TRY(raytree_commit(t, D, stream));
+    // ---- 5. the light planes again, and the way back
+    if (retrace) {
+      if (!regrown) MT_TRY(call.clear_counters());  // (a regrown tree's tracing launches have counted already)
+      std::vector<int32_t> all((size_t)I.n_lights);
+      for (int i = 0; i < I.n_lights; i++) all[(size_t)i] = i;
+      MT_TRY(launch_raytree_update(t, all.data(), I.n_lights, stream));
     }
-    if (retrace || regrown) {
-      MT_TRY(s->h_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
-      // (a regrown tree's tracing launches have counted already)
-      if (!regrown) HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-      if (retrace) {
-        std::vector<int32_t> all((size_t)I.n_lights);
-        for (int i = 0; i < I.n_lights; i++) all[(size_t)i] = i;
-        const bool counters_were = s->stats_enabled;
-        if (stats) s->stats_enabled = true;  // the caller asked for them
-        const int rc = launch_raytree_update(t, all.data(), I.n_lights, stream);
-        s->stats_enabled = counters_were;
-        if (rc != MT_OK) return rc;
-      }
-      HIP_TRY(hipEventRecord(t->ev1, stream));
-      HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipMemsetAsync(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long), stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      MT_TRY(check_status(s->h_counters));
-      if (stats) fill_stats(s->h_counters, stats);
-    } else {
-      HIP_TRY(hipEventRecord(t->ev1, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (stats) {
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-      stats->kernel_ms = ms;
-    }
-  } else if (info) {
+    MT_TRY(call.mark_end());
+    if (call.counters) MT_TRY(call.counters_home());
+  }
+  if (!regrown && info) {
     for (int k = 0; k < I.n_layers; k++) info->kept[k] = I.n_rays[k];
   }
-  t->mtls = s->mtls_host;
-  t->mtl_generation = s->mtl_generation;
-  t->tex_generation = s->tex_generation;
-  t->tri_mtl = s->tri_mtl_host;
-  t->asg_generation = s->asg_generation;
-  if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  MT_TRY(call.close());
+  raytree_snapshot(t);
   return MT_OK;
 }
 
