@@ -863,6 +863,73 @@ int mt_scene_set_raytree_tri(mt_scene *scene, int keep);
 int mt_raytree_read_tri(mt_raytree *tree, int layer, int32_t *out_tri);
 int mt_raytree_keeps_tri(const mt_raytree *tree);
 
+/* Per-vertex ATTRIBUTES replaced in place: shading normals and texture coordinates.  (No reference counterpart.)  For a
+ * look-dev session that smooths or flattens an object's shading, or tiles, offsets or rotates a texture on a surface.
+ * The arrays are n_tris x 9 doubles in node-stream order, exactly as mt_scene_desc::tri_normal / tri_uvw have them.
+ * Every kernel reads them at run time and nothing mt_scene_create derives from the description reads them (node
+ * records, lists and boxes come from vertices alone), so the edit is one copy.  Vertex POSITIONS are out of scope: they
+ * change the octree and every derived record; a moved vertex needs a new scene.
+ * The set is synchronous, like mt_scene_set_triangle_materials: it waits until the scene's device is idle.  The scene
+ * keeps NO host copy of the attributes (144 bytes per triangle): the new array goes to a staging buffer on the GPU and
+ * mt::tri_attr_stamp_kernel, one thread per triangle, compares each triangle's 9 doubles BY THEIR BITS with the live
+ * array, copies the triangles that differ, writes the new generation into a per-triangle uint32 STAMP plane (one plane
+ * per attribute, mirrored on the host, 4 bytes per triangle each), counts the changed triangles and keeps the lowest
+ * changed index.  A staging buffer or stamp plane that does not fit is MT_ERR_NOMEM with the scene exactly as it was.
+ * The scene keeps a NORMAL generation and a UVW generation, both 0 at creation; a set with at least one changed triangle
+ * bumps its own and the material generation too, so every ray tree of the scene becomes stale exactly as after a
+ * material edit.  A set that changes nothing bumps nothing and copies nothing into the live array.  (The generations are
+ * 32 bits wide, like the stamps: after 2^32 - 1 sets that changed a triangle the next is MT_ERR_UNSUPPORTED.)  The getters read
+ * the live array back from the device.  Zero triangles and n_tris = 0 is MT_OK and does nothing.  No _device form.
+ * CONTRACT: after the set, every call that renders or shades -- mt_scene_set_materials's list, both frame engines, the
+ * hybrid, the lean kernel and its redo launch, supersampled and adaptive frames, tile lists, mt_render_gbuffer, the
+ * light-buffer calls, mt_raytree_create[_rays], mt_trace_rays and mt_render_frame_multi replicas that share a device --
+ * gives, byte for byte and plane for plane, what the same call gives on a scene newly created from the same description
+ * with that array.  Cost history, forecasts and engine choice are left alone.  G-buffer planes are the caller's and
+ * describe the old attributes; they hold no stream index, so there is no G-buffer counterpart: render it again.
+ * Argument checks come before any device call, in this order, all MT_ERR_ARG: the scene (NULL); n_tris unequal to the
+ * scene's; a NULL array with n_tris > 0.  Values are not checked: NaN, zero and unnormalised normals are legal input, as
+ * they are in a description. */
+int mt_scene_set_triangle_normals(mt_scene *scene, const double *tri_normal, int n_tris);
+int mt_scene_set_triangle_uvw(mt_scene *scene, const double *tri_uvw, int n_tris);
+int mt_scene_get_triangle_normals(mt_scene *scene, double *out, int n_tris);
+int mt_scene_get_triangle_uvw(mt_scene *scene, double *out, int n_tris);
+
+/* Ray trees that keep tri take the attribute edit in mt_raytree_update_materials / mt_raytree_regrow_materials.  A
+ * tree's snapshot also holds the two attribute generations, taken at creation and after each successful update or
+ * regrow.  Ray i is UVW-DIRTY when tri[i] >= 0 and uvw_stamp[tri[i]] is greater than the snapshot's uvw generation;
+ * NORMAL-DIRTY likewise with the normal stamps.  (A -> B -> A counts as dirty: the recomputation gives the old bits
+ * back, so the contract below still holds.)
+ * Refusal, after the texture and reassignment refusals and before any device call, MT_ERR_UNSUPPORTED with the tree
+ * untouched and still stale: a tree WITHOUT tri while any triangle carries a stamp newer than the snapshot, in either
+ * attribute; the message gives the attribute, the count and the first triangle.  (Without it an attribute-only edit
+ * would compare equal tables and declare a wrong tree fresh.)
+ * A uvw-dirty ray: uvw' = interpolate(tri_uvw[tri], barycentric(tri_vertex[tri], point)), the tracing kernel's
+ * expressions from the stored point, goes to the uvw plane where the tree keeps one (the stored uvw is not required);
+ * albedo = ambient, times the texel at uvw' where the ray's effective material has tex >= 0.  The retexture and
+ * reassignment paths read uvw' for such a ray.  No light plane is traced for a uvw edit alone; the tree's shape never
+ * changes.
+ * A normal-dirty ray: normal' = interpolate(tri_normal[tri], ...) goes to the normal plane, unflipped.  Its reflected
+ * child, if any, is no longer KEPT: it is spawned again from normal' and TRACED, with everything below it.  The
+ * refracted child and its subtree stay kept; the ray's own light planes stay (their loop starts from point).
+ * mt_raytree_update_materials: the check pass also counts normal-dirty rays with a reflected child; a non-zero count is
+ * MT_ERR_UNSUPPORTED with the count and the first (layer, ray), as for a shape mismatch.  Otherwise
+ * mt::raytree_reattr_kernel, one thread per ray, rewrites the dirty rays' planes in the commit.
+ * mt_raytree_regrow_materials: a child is kept when its path exists in the old tree AND (it is the refracted child OR
+ * its parent is not normal-dirty); a respawned reflected child's ray comes from the parent's EFFECTIVE normal.  The
+ * copy kernel rewrites normal, uvw and albedo of kept dirty rays; layer 0 is rewritten in place at the commit.  The
+ * light count check (4) also fires when any triangle is normal-stamped since the snapshot.
+ * CONTRACT, unchanged in form: after MT_OK the tree is bit-identical in every plane of every layer, tri and uvw included
+ * where kept, and in n_layers, n_rays and bytes, to mt_raytree_create[_rays] on a scene newly created with the current
+ * attributes, assignment, materials, textures and lights and the same switches; after a refusal it is bit-identical to
+ * what it was.
+ * mt_raytree_attr_info_last: counts of the tree's last update or regrow (zero before the first): the rays whose normal /
+ * uvw-dependent planes were rewritten, and the reflected children traced because of a dirty parent normal.
+ * MT_ERR_ARG: tree or out NULL. */
+typedef struct mt_raytree_attr_info {
+  int64_t renormaled, reuvwed, respawned;
+} mt_raytree_attr_info;
+int mt_raytree_attr_info_last(const mt_raytree *tree, mt_raytree_attr_info *out);
+
 /* A ray tree over the CALLER's rays, and the shade's colours before V3DtoRGB: TraceRay(ray) (mythtracer.h:77) for a ray
  * list at full depth -- a panorama or fisheye camera, an orthographic view, a probe, any ray a caller wants the colour
  * of.  Everything after layer 0 of a ray tree already runs over a ray list and never looks at a sensor or an image, so

@@ -42,6 +42,8 @@ HIP_SYMBOLS = [
     "mt_raytree_keeps_uvw", "mt_retexture_gbuffer", "mt_retexture_gbuffer_device",
     "mt_scene_set_triangle_materials", "mt_scene_get_triangle_materials", "mt_scene_set_raytree_tri",
     "mt_raytree_read_tri", "mt_raytree_keeps_tri",
+    "mt_scene_set_triangle_normals", "mt_scene_set_triangle_uvw", "mt_scene_get_triangle_normals",
+    "mt_scene_get_triangle_uvw", "mt_raytree_attr_info_last",
 ]
 MT_MAX_RECURSION = 16
 
@@ -114,6 +116,13 @@ class mt_raytree_regrow_info(C.Structure):
                     kept=[int(v) for v in self.kept][:self.n_layers_after],
                     traced=[int(v) for v in self.traced][:self.n_layers_after],
                     dropped=[int(v) for v in self.dropped][:self.n_layers_before])
+
+
+class mt_raytree_attr_info(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("renormaled", "reuvwed", "respawned")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class mt_lean_info(C.Structure):
@@ -322,6 +331,11 @@ class HipAbi:
         L.mt_scene_set_raytree_tri.argtypes = [vp, ci]
         L.mt_raytree_read_tri.argtypes = [vp, ci, vp]
         L.mt_raytree_keeps_tri.argtypes = [vp]
+        L.mt_scene_set_triangle_normals.argtypes = [vp, vp, ci]
+        L.mt_scene_set_triangle_uvw.argtypes = [vp, vp, ci]
+        L.mt_scene_get_triangle_normals.argtypes = [vp, vp, ci]
+        L.mt_scene_get_triangle_uvw.argtypes = [vp, vp, ci]
+        L.mt_raytree_attr_info_last.argtypes = [vp, C.POINTER(mt_raytree_attr_info)]
         L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
@@ -533,6 +547,42 @@ class HipAbi:
         """mt_scene_set_raytree_tri: ray trees made from now on keep (True) or do not keep (False, the default) a tri
         plane per layer, which update_materials / regrow need to take a set_triangle_materials."""
         self.check(self.lib.mt_scene_set_raytree_tri(h, 1 if keep else 0))
+
+    def _set_triangle_attr(self, fn, h, attr):
+        a = np.ascontiguousarray(attr, dtype=np.float64)
+        if a.size % 9:
+            raise ValueError("a triangle attribute array holds 9 doubles per triangle, not %d in all" % a.size)
+        self.check(fn(h, a.ctypes.data if a.size else None, a.size // 9))
+
+    def _get_triangle_attr(self, fn, h, n_tris) -> np.ndarray:
+        out = np.zeros((max(n_tris, 0), 3, 3), dtype=np.float64)
+        self.check(fn(h, out.ctypes.data if out.size else None, n_tris))
+        return out
+
+    def set_triangle_normals(self, h, tri_normal):
+        """mt_scene_set_triangle_normals: the whole per-vertex normal array replaced, (n_tris, 3, 3) doubles in
+        node-stream order as flat["tri_normal"] of MythTracer.flatten() has it.  Every ray tree of the scene is stale
+        afterwards when a triangle changed."""
+        self._set_triangle_attr(self.lib.mt_scene_set_triangle_normals, h, tri_normal)
+
+    def set_triangle_uvw(self, h, tri_uvw):
+        """mt_scene_set_triangle_uvw: the same for the per-vertex texture coordinates, flat["tri_uvw"]."""
+        self._set_triangle_attr(self.lib.mt_scene_set_triangle_uvw, h, tri_uvw)
+
+    def get_triangle_normals(self, h, n_tris) -> np.ndarray:
+        """mt_scene_get_triangle_normals: the scene's current normals, (n_tris, 3, 3) float64, read from the device."""
+        return self._get_triangle_attr(self.lib.mt_scene_get_triangle_normals, h, n_tris)
+
+    def get_triangle_uvw(self, h, n_tris) -> np.ndarray:
+        """mt_scene_get_triangle_uvw: the scene's current texture coordinates, (n_tris, 3, 3) float64."""
+        return self._get_triangle_attr(self.lib.mt_scene_get_triangle_uvw, h, n_tris)
+
+    def raytree_attr_info(self, tree) -> dict:
+        """mt_raytree_attr_info_last: what the tree's last update_materials / regrow did for edited vertex attributes
+        -- renormaled, reuvwed (rays whose planes were rewritten), respawned (reflected children traced again)."""
+        info = mt_raytree_attr_info()
+        self.check(self.lib.mt_raytree_attr_info_last(tree, C.byref(info)))
+        return info.as_dict()
 
     def retexture_gbuffer(self, h, gbuffer) -> dict:
         """mt_retexture_gbuffer: the albedo plane of `gbuffer` (dict with `material` (ch, cw) int32 and, unless no
@@ -1148,6 +1198,8 @@ def host_lib():
     L.mth_update_triangle_materials.argtypes = [vp]
     L.mth_set_raytree_keep_triangles.argtypes = [vp, ci]
     L.mth_set_raytree_keep_triangles.restype = None
+    L.mth_set_triangle_attr.argtypes = [vp, ci, vp, ci, vp]
+    L.mth_update_triangle_attributes.argtypes = [vp]
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1197,6 +1249,10 @@ class RayTree:
 
     def layer(self, k, planes=None) -> dict:
         return hip_abi().raytree_read_layer(self._tree(), k, planes)
+
+    def attr_info(self) -> dict:
+        """mt_raytree_attr_info_last: renormaled, reuvwed, respawned of the tree's last update_materials / regrow."""
+        return hip_abi().raytree_attr_info(self._tree())
 
     def shade(self, lights=None) -> dict:
         """MythTracer::ShadeRayTree.  `lights` (n x 12) replaces the facade's lights first, as set_lights does; None
@@ -1486,6 +1542,32 @@ class MythTracer:
         regrow(), which take the edit only for a tree built after set_raytree_keep_triangles(True)."""
         if not self.L.mth_update_triangle_materials(self.h):
             raise RuntimeError("UpdateTriangleMaterials failed: " + self.last_error())
+
+    def _set_triangle_attr(self, which, add_indices, attr):
+        a = np.ascontiguousarray(add_indices, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(attr, dtype=np.float64)
+        if v.size != a.size * 9:
+            raise ValueError("%d triangles need %d doubles, not %d" % (a.size, a.size * 9, v.size))
+        if not self.L.mth_set_triangle_attr(self.h, which, a.ctypes.data if a.size else None, int(a.size),
+                                            v.ctypes.data if v.size else None):
+            raise RuntimeError("set_triangle_%s failed: %s" % (("normals", "uvw")[which], self.last_error()))
+
+    def set_triangle_normals(self, add_indices, normals):
+        """Triangle::normal of the triangles `add_indices` (add_triangle / .obj order) replaced by `normals`
+        (n x 3 x 3).  Only the host scene changes: update_triangle_attributes() pushes it.  RuntimeError for an index
+        outside the scene's triangles; no triangle is changed then."""
+        self._set_triangle_attr(0, add_indices, normals)
+
+    def set_triangle_uvw(self, add_indices, uvw):
+        """The same for Triangle::uvw, `uvw` (n x 3 x 3)."""
+        self._set_triangle_attr(1, add_indices, uvw)
+
+    def update_triangle_attributes(self):
+        """MythTracer::UpdateTriangleAttributes: the triangles' current normals and texture coordinates replaced on
+        every device replica.  RayTrees built before are stale until update_materials() / regrow(), which need a tree
+        that keeps triangles."""
+        if not self.L.mth_update_triangle_attributes(self.h):
+            raise RuntimeError("UpdateTriangleAttributes failed: " + self.last_error())
 
     def set_raytree_keep_triangles(self, keep: bool):
         """MythTracer::SetRayTreeKeepTriangles: RayTrees built from now on keep the triangle each ray hit."""

@@ -301,6 +301,14 @@ struct mt_scene {
   std::shared_ptr<const std::vector<int32_t>> tri_mtl_host;
   unsigned long long asg_generation = 0;
   int raytree_tri = 0;
+  // mt_scene_set_triangle_normals ([0]) / _uvw ([1]), allocated by the first set: the staging buffer and
+  // tri_attr_stamp_kernel's two words, shared; per attribute the stamp plane, its host mirror (empty: every stamp is 0)
+  // and the generation.  No host copy of the attributes themselves.
+  Buf<double> d_attr_stage;
+  Buf<unsigned int> d_attr_found;
+  Buf<uint32_t> d_attr_stamp[2];
+  std::vector<uint32_t> attr_stamp_host[2];
+  uint32_t attr_generation[2] = {0, 0};
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -1810,6 +1818,90 @@ int mt_scene_get_triangle_materials(const mt_scene *s, int32_t *out, int n) {
   return MT_OK;
 }
 
+namespace {
+
+const char *const kAttrName[2] = {"normal", "uvw"};
+
+// checked before any device call, in the order of the header
+int check_triangle_attr_args(const mt_scene *s, const void *attr, int n, int which) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (n != s->dev.n_tris) return fail(MT_ERR_ARG, "%d triangles for a scene made with %d", n, s->dev.n_tris);
+  if (n > 0 && !attr) return fail(MT_ERR_ARG, "the triangle %s array is NULL", kAttrName[which]);
+  return MT_OK;
+}
+
+// the status of a Buf::ensure for an attribute set: what does not fit is MT_ERR_NOMEM (nothing of the scene has changed
+// by then)
+int attr_nomem(int rc, size_t bytes, const char *what) {
+  if (rc == MT_OK) return MT_OK;
+  (void)hipGetLastError();
+  const std::string why = g_err;
+  return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s: %s", bytes, what, why.c_str());
+}
+
+// mt_scene_set_triangle_normals (which = 0) / _uvw (1): the array staged on the device, tri_attr_stamp_kernel, and --
+// only when a triangle changed -- the stamp plane's way home and the generations
+int set_triangle_attr(mt_scene *s, const double *attr, int n, int which) {
+  MT_TRY(check_triangle_attr_args(s, attr, n, which));
+  if (n == 0) return MT_OK;
+  if (s->attr_generation[which] == 0xffffffffu) {  // (the stamps are 32 bits wide)
+    return fail(MT_ERR_UNSUPPORTED, "the scene's %s generation is used up (2^32 - 1 sets that changed a triangle): a new "
+                                    "scene is needed", kAttrName[which]);
+  }
+  const size_t nt = (size_t)n;
+  HostCall call(s, nullptr, s->ev0, s->ev1);
+  HIP_TRY(hipSetDevice(s->device));
+  // everything that may not fit comes first: until the kernel runs the scene is exactly what it was
+  MT_TRY(attr_nomem(s->d_attr_stage.ensure(nt * 72), nt * 72, "the staged triangle attributes"));
+  MT_TRY(attr_nomem(s->d_attr_found.ensure(2 * sizeof(unsigned int)), 2 * sizeof(unsigned int), "the attribute set's count"));
+  const bool first_set = s->d_attr_stamp[which].p == nullptr;
+  MT_TRY(attr_nomem(s->d_attr_stamp[which].ensure(nt * sizeof(uint32_t)), nt * sizeof(uint32_t), "the triangles' stamp plane"));
+  if (first_set) HIP_TRY(hipMemset(s->d_attr_stamp[which], 0, nt * sizeof(uint32_t)));  // (generation 0: creation)
+  try {
+    s->attr_stamp_host[which].resize(nt, 0u);
+  } catch (const std::bad_alloc &) {
+    return fail(MT_ERR_NOMEM, "no room for the %zu bytes of the stamp plane's host mirror", nt * sizeof(uint32_t));
+  }
+  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the array while it changes
+  const hipStream_t stream = call.stream;
+  HIP_TRY(hipMemcpyAsync(s->d_attr_stage, attr, nt * 72, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(s->d_attr_found, 0, sizeof(unsigned int), stream));
+  HIP_TRY(hipMemsetAsync(s->d_attr_found + 1, 0xff, sizeof(unsigned int), stream));
+  MT_TRY(call.begin(false));
+  TriAttrStampArgs A{};
+  A.staged = s->d_attr_stage;
+  A.live = const_cast<double *>(which == 0 ? s->dev.tri_normal : s->dev.tri_uvw);
+  A.stamp = s->d_attr_stamp[which];
+  A.n_tris = (uint32_t)n;
+  A.generation = s->attr_generation[which] + 1u;
+  A.found = s->d_attr_found;
+  HIP_TRY(launch_flat(tri_attr_stamp_kernel, nt, stream, A));
+  MT_TRY(call.mark_end());
+  unsigned int found[2] = {0u, 0u};
+  HIP_TRY(hipMemcpyAsync(found, s->d_attr_found, sizeof found, hipMemcpyDeviceToHost, stream));
+  MT_TRY(call.close());  // (waits for the stream)
+  if (found[0] == 0) return MT_OK;
+  HIP_TRY(hipMemcpy(s->attr_stamp_host[which].data(), s->d_attr_stamp[which], nt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  s->attr_generation[which]++;
+  s->mtl_generation++;  // every ray tree of the scene is stale, as after a material edit
+  return MT_OK;
+}
+
+int get_triangle_attr(mt_scene *s, double *out, int n, int which) {
+  MT_TRY(check_triangle_attr_args(s, out, n, which));
+  if (n == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipMemcpy(out, which == 0 ? s->dev.tri_normal : s->dev.tri_uvw, (size_t)n * 72, hipMemcpyDeviceToHost));
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_scene_set_triangle_normals(mt_scene *s, const double *tri_normal, int n) { return set_triangle_attr(s, tri_normal, n, 0); }
+int mt_scene_set_triangle_uvw(mt_scene *s, const double *tri_uvw, int n) { return set_triangle_attr(s, tri_uvw, n, 1); }
+int mt_scene_get_triangle_normals(mt_scene *s, double *out, int n) { return get_triangle_attr(s, out, n, 0); }
+int mt_scene_get_triangle_uvw(mt_scene *s, double *out, int n) { return get_triangle_attr(s, out, n, 1); }
+
 int mt_scene_set_raytree_tri(mt_scene *s, int keep) {
   if (!s) return fail(MT_ERR_ARG, "scene is NULL");
   if (keep != 0 && keep != 1) return fail(MT_ERR_ARG, "keep must be 0 or 1");
@@ -2939,6 +3031,11 @@ struct mt_raytree {
   std::shared_ptr<const std::vector<int32_t>> tri_mtl;
   unsigned long long asg_generation = 0;
   bool keep_tri = false;
+  // the scene's two attribute generations then (mt_scene_set_triangle_normals / _uvw), the kernels' kRayTreeAttrWords
+  // counts (first use) and what the last update or regrow made of them (mt_raytree_attr_info_last)
+  uint32_t attr_generation[2] = {0, 0};
+  unsigned long long *d_attr_count = nullptr;
+  mt_raytree_attr_info attr_last{};
   unsigned long long *d_mismatch = nullptr;
   uint8_t *d_albedo_changed = nullptr;
   // mt_raytree_regrow_materials (first use, grown when a call needs more): `src` of the new layers k and k + 1 in turn,
@@ -3216,6 +3313,8 @@ void raytree_snapshot(mt_raytree *t) {
   t->tex_generation = s->tex_generation;
   t->tri_mtl = s->tri_mtl_host;
   t->asg_generation = s->asg_generation;
+  t->attr_generation[0] = s->attr_generation[0];
+  t->attr_generation[1] = s->attr_generation[1];
 }
 
 int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_stats *stats) {
@@ -3327,6 +3426,7 @@ void mt_raytree_destroy(mt_raytree *t) {
   if (t->d_out_color) (void)hipFree(t->d_out_color);
   if (t->d_bad) (void)hipFree(t->d_bad);
   if (t->d_mismatch) (void)hipFree(t->d_mismatch);
+  if (t->d_attr_count) (void)hipFree(t->d_attr_count);
   if (t->d_albedo_changed) (void)hipFree(t->d_albedo_changed);
   for (int32_t *p : t->d_src) {
     if (p) (void)hipFree(p);
@@ -3569,7 +3669,37 @@ struct MaterialDiff {
   // snapshot, the first of them, and the first whose NEW material has a texture (with that material)
   long long reassigned = 0;
   int first_reassigned = -1, textured_tri = -1, textured_tri_mtl = -1;
+  // pending attribute edits (mt_scene_set_triangle_normals / _uvw): some triangle's stamp is newer than the tree's snapshot
+  bool normals = false, uvws = false;
 };
+
+// the kernels' view of the pending attribute edits D of tree t (mt_raytree.h, RayTreeAttr)
+RayTreeAttr raytree_attr_args(const mt_raytree *t, const MaterialDiff &D) {
+  const mt_scene *s = t->scene;
+  RayTreeAttr T{};
+  if (D.normals) T.normal_stamp = s->d_attr_stamp[0];
+  if (D.uvws) T.uvw_stamp = s->d_attr_stamp[1];
+  T.normal_gen = t->attr_generation[0];
+  T.uvw_gen = t->attr_generation[1];
+  T.tri_vertex = s->dev.tri_vertex;
+  T.tri_normal = s->dev.tri_normal;
+  T.tri_uvw = s->dev.tri_uvw;
+  T.count = t->d_attr_count;
+  return T;
+}
+
+// raytree_reattr_kernel (or, check = true, raytree_attr_check_kernel) over the n rays of layer k
+hipError_t launch_raytree_reattr(const mt_raytree *t, const MaterialDiff &D, const RayTreeLayer &L, size_t n, int k, bool check,
+                                 hipStream_t stream) {
+  RayTreeReattrArgs A{};
+  A.L = L;
+  A.attr = raytree_attr_args(t, D);
+  A.mtls = t->scene->dev.mtls;
+  A.texs = t->scene->dev.texs;
+  A.n_rays = (uint32_t)n;
+  A.layer = k;
+  return launch_flat(check ? raytree_attr_check_kernel : raytree_reattr_kernel, n, stream, A);
+}
 
 // CHANGED of the assignment `was` -> `now`, and whether a shadow ray may see it: a = the old material under the tree's
 // constants `mtls_was`, b = the new one under the scene's `mtls_now`
@@ -3668,6 +3798,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
   const int old_layers = I.n_layers;
   // a pending reassignment: layer 0's material plane waits for the commit, the copy kernel restates the kept rays'
   const int32_t *tri_mtl_now = D.reassigned != 0 ? s->dev.tri_mtl : nullptr;
+  // pending attribute edits: the link kernel respawns the reflected children of kept normal-dirty parents, the copy
+  // kernel restates the kept rays' planes, layer 0's wait for the commit
+  const RayTreeAttr attr = raytree_attr_args(t, D);
   void *alloc[MT_MAX_RECURSION + 1] = {};  // the new layers >= 1, aside
   RayTreeLayer NL[MT_MAX_RECURSION + 1] = {};
   size_t n_new[MT_MAX_RECURSION + 1] = {}, n_traced[MT_MAX_RECURSION + 1] = {};
@@ -3748,6 +3881,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.mtls = s->dev.mtls;
       A.tri_mtl = k == 0 ? tri_mtl_now : nullptr;
       A.n_parent = (uint32_t)n;
+      A.attr = attr;
       if (launch_flat(raytree_regrow_link_kernel, n, stream, A) != hipSuccess) {
         return release(fail(MT_ERR_HIP, "launching the regrow's link kernel failed"));
       }
@@ -3765,6 +3899,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
       A.texs = s->dev.texs;
       A.albedo_changed = D.albedo ? t->d_albedo_changed : nullptr;
       A.tri_mtl = tri_mtl_now;
+      A.attr = attr;
       if (launch_flat(raytree_regrow_copy_kernel, n1, stream, A) != hipSuccess) {
         return release(fail(MT_ERR_HIP, "launching the regrow's copy kernel failed"));
       }
@@ -3811,6 +3946,9 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     if (launch_flat(raytree_recommit_kernel, n0, stream, raytree_recommit_args(t, D, t->layer[0], n0, 0)) != hipSuccess) {
       return release(fail(MT_ERR_HIP, "launching layer 0's commit failed"));
     }
+  }
+  if ((D.normals || D.uvws) && launch_raytree_reattr(t, D, t->layer[0], n0, 0, false, stream) != hipSuccess) {
+    return release(fail(MT_ERR_HIP, "launching layer 0's attribute commit failed"));
   }
   if (hipStreamSynchronize(stream) != hipSuccess) return release(fail(MT_ERR_HIP, "the regrow's commit failed"));
   if (info) {
@@ -3877,6 +4015,34 @@ int raytree_diff(const mt_raytree *t, MaterialDiff *out) {
     return fail(MT_ERR_UNSUPPORTED, "triangle %d was given material %d, which has a texture: the ray tree keeps no uvw "
                                     "(mt_scene_set_raytree_uvw), a new tree is needed", D.textured_tri, D.textured_tri_mtl);
   }
+  // an attribute set since the snapshot: the generation moves only with a changed triangle, so some stamp is newer
+  for (int w = 0; w < 2; w++) {
+    if (t->attr_generation[w] == s->attr_generation[w]) continue;
+    if (!t->keep_tri) {
+      long long stamped = 0, first = -1;
+      const std::vector<uint32_t> &stamp = s->attr_stamp_host[w];
+      for (size_t i = 0; i < stamp.size(); i++) {
+        if (stamp[i] > t->attr_generation[w] && stamped++ == 0) first = (long long)i;
+      }
+      return fail(MT_ERR_UNSUPPORTED, "the %s of %lld triangles was set after the ray tree was made, the first is triangle "
+                                      "%lld: the ray tree keeps no tri (mt_scene_set_raytree_tri), a new tree is needed",
+                  kAttrName[w], stamped, first);
+    }
+    (w == 0 ? D.normals : D.uvws) = true;
+  }
+  return MT_OK;
+}
+
+// The attribute part of the check pass: raytree_attr_check_kernel over every layer counts the normal-dirty rays that
+// have a reflected child: found[0] of them, the first at layer found[1] >> 32, ray found[1] & 0xffffffff.  Synchronises.
+int raytree_attr_check_pass(mt_raytree *t, const MaterialDiff &D, hipStream_t stream, unsigned long long found[2]) {
+  const mt_raytree_desc &I = t->info;
+  for (int k = 0; k < I.n_layers; k++) {
+    HIP_TRY(launch_raytree_reattr(t, D, t->layer[k], (size_t)I.n_rays[k], k, true, stream));
+  }
+  found[0] = found[1] = 0;
+  HIP_TRY(hipMemcpyAsync(found, t->d_attr_count + kRayTreeAttrBlocked, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return MT_OK;
 }
 
@@ -3921,6 +4087,12 @@ int raytree_commit(mt_raytree *t, const MaterialDiff &D, hipStream_t stream) {
     if (!A.copy_coef && !A.albedo_changed && !A.tri_mtl) continue;
     HIP_TRY(launch_flat(raytree_recommit_kernel, n, stream, A));
   }
+  // the dirty rays' normal, uvw and albedo, behind the materials' commit: the material plane is the effective one
+  if (D.normals || D.uvws) {
+    for (int k = 0; k < I.n_layers; k++) {
+      HIP_TRY(launch_raytree_reattr(t, D, t->layer[k], (size_t)I.n_rays[k], k, false, stream));
+    }
+  }
   return MT_OK;
 }
 
@@ -3936,32 +4108,49 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     memset(info, 0, sizeof *info);
     info->n_layers_before = info->n_layers_after = I.n_layers;
   }
+  t->attr_last = mt_raytree_attr_info{};
   if (t->mtl_generation == s->mtl_generation) return MT_OK;
   // ---- 1. the edit, and the edits this tree cannot take
   MaterialDiff D;
   MT_TRY(raytree_diff(t, &D));
+  const bool attrs = D.normals || D.uvws;
   // ---- 2. the lights the tracing launches would read
   const bool retrace = D.shadow && I.n_lights > 0;
   // (a regrow may trace new rays, whose light planes come from the scene's current lights)
-  const bool lights_read = regrow ? (D.shape || D.shadow) && I.n_lights > 0 : retrace;
+  const bool lights_read = regrow ? (D.shape || D.shadow || D.normals) && I.n_lights > 0 : retrace;
   if (lights_read && s->dev.n_lights != I.n_lights) {
     return fail(MT_ERR_ARG, "the scene has %d lights, the ray tree was made with %d", s->dev.n_lights, I.n_lights);
   }
   bool regrown = false;
-  if (D.shape || D.albedo || retrace) {
+  unsigned long long attr_count[kRayTreeAttrWords] = {};
+  if (D.shape || D.albedo || retrace || attrs) {
     HIP_TRY(hipSetDevice(s->device));
     const hipStream_t stream = call.stream;
+    if (attrs) {
+      if (!t->d_attr_count) {
+        MT_TRY(raytree_malloc((void **)&t->d_attr_count, sizeof attr_count, "the ray tree's attribute counts"));
+      }
+      HIP_TRY(hipMemsetAsync(t->d_attr_count, 0, sizeof attr_count, stream));
+      HIP_TRY(hipMemsetAsync(t->d_attr_count + kRayTreeAttrFirst, 0xff, sizeof(unsigned long long), stream));
+    }
     MT_TRY(call.begin(false));  // (the counters are cleared where a tracing launch follows)
     // ---- 3. the check pass
-    if (D.shape) {
-      unsigned long long found[2];
-      MT_TRY(raytree_check_pass(t, D, stream, found));
+    if (D.shape || D.normals) {
+      unsigned long long found[2] = {0, 0}, blocked[2] = {0, 0};
+      if (D.shape) MT_TRY(raytree_check_pass(t, D, stream, found));
+      if (D.normals) MT_TRY(raytree_attr_check_pass(t, D, stream, blocked));
       if (found[0] != 0 && !regrow) {
         return fail(MT_ERR_UNSUPPORTED, "the new materials change the shape of the ray tree: %llu rays spawn other "
                                         "children, the first in layer %d at ray %llu; a new tree is needed",
                     found[0], (int)(found[1] >> 32), found[1] & 0xffffffffull);
       }
-      if (found[0] != 0) {
+      if (blocked[0] != 0 && !regrow) {
+        return fail(MT_ERR_UNSUPPORTED, "the new normals move reflected rays of the ray tree: %llu rays on edited triangles "
+                                        "have a reflected child, the first in layer %d at ray %llu; "
+                                        "mt_raytree_regrow_materials or a new tree is needed",
+                    blocked[0], (int)(blocked[1] >> 32), blocked[1] & 0xffffffffull);
+      }
+      if (found[0] != 0 || blocked[0] != 0) {
         // (only a tree of zero lights gets here with another count: the tracing kernel runs the SCENE's lights' loops,
         // and the new layers have planes for the tree's)
         if (s->dev.n_lights != I.n_lights) {
@@ -3984,11 +4173,17 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     }
     MT_TRY(call.mark_end());
     if (call.counters) MT_TRY(call.counters_home());
+    if (attrs) {
+      HIP_TRY(hipMemcpyAsync(attr_count, t->d_attr_count, sizeof attr_count, hipMemcpyDeviceToHost, stream));
+    }
   }
   if (!regrown && info) {
     for (int k = 0; k < I.n_layers; k++) info->kept[k] = I.n_rays[k];
   }
   MT_TRY(call.close());
+  t->attr_last.renormaled = (int64_t)attr_count[kRayTreeAttrNormal];
+  t->attr_last.reuvwed = (int64_t)attr_count[kRayTreeAttrUVW];
+  t->attr_last.respawned = (int64_t)attr_count[kRayTreeAttrRespawned];
   raytree_snapshot(t);
   return MT_OK;
 }
@@ -3999,6 +4194,13 @@ int mt_raytree_update_materials(mt_raytree *t, mt_stats *stats) { return raytree
 
 int mt_raytree_regrow_materials(mt_raytree *t, mt_raytree_regrow_info *info, mt_stats *stats) {
   return raytree_take_materials(t, stats, true, info);
+}
+
+int mt_raytree_attr_info_last(const mt_raytree *t, mt_raytree_attr_info *out) {
+  if (!t) return fail(MT_ERR_ARG, "the ray tree is NULL");
+  if (!out) return fail(MT_ERR_ARG, "the mt_raytree_attr_info is NULL");
+  *out = t->attr_last;
+  return MT_OK;
 }
 
 // ---- one frame on several GPUs of this process (main_net_master.cc:195-236) --------------------------

@@ -62,6 +62,76 @@ __device__ __forceinline__ int raytree_effective_material(const RayTreeLayer &L,
   return tri < 0 ? -1 : tri_mtl[tri];
 }
 
+// ---- edited vertex attributes (include/mythtracer_hip.h, mt_scene_set_triangle_normals / _uvw) ----
+// tri_attr_stamp_kernel  one thread per triangle: the staged array's 9 doubles against the live array's BY THEIR BITS;
+//                        a triangle that differs is copied into the live array and gets `generation` in its stamp.
+//                        found[0] += the changed triangles, found[1] = min(the lowest changed index): one atomic pair per
+//                        wave that has any.  At launch found = {0, 0xffffffff}.
+struct TriAttrStampArgs {
+  const double *staged;  // [n_tris][9]
+  double *live;          // [n_tris][9]
+  uint32_t *stamp;       // [n_tris]
+  uint32_t n_tris;
+  uint32_t generation;
+  unsigned int *found;   // [2]
+};
+
+__global__ __launch_bounds__(256) void tri_attr_stamp_kernel(TriAttrStampArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_tris) return;
+  const unsigned long long *a = (const unsigned long long *)(A.staged + i * 9);
+  unsigned long long *b = (unsigned long long *)(A.live + i * 9);
+  unsigned long long v[9];
+  bool differ = false;
+  for (int k = 0; k < 9; k++) {
+    v[k] = a[k];
+    differ = differ || v[k] != b[k];
+  }
+  if (differ) {
+    for (int k = 0; k < 9; k++) b[k] = v[k];
+    A.stamp[i] = A.generation;
+  }
+  const unsigned long long changed = __ballot(differ);
+  if (differ && (int)__lane_id() == __ffsll((long long)changed) - 1) {  // (the wave's lowest changed triangle)
+    atomicAdd(A.found, (unsigned)__popcll(changed));
+    atomicMin(A.found + 1, (unsigned)i);
+  }
+}
+
+// What a stored tree needs to follow an attribute edit: the scene's stamp planes and live arrays, and the generations of
+// the tree's snapshot.  A stamp pointer is nullptr while no triangle carries a stamp newer than the snapshot: nothing of
+// that attribute is dirty.  Only trees that keep tri get a non-null one.
+struct RayTreeAttr {
+  const uint32_t *normal_stamp, *uvw_stamp;  // [n_tris]
+  uint32_t normal_gen, uvw_gen;              // the snapshot's
+  const double *tri_vertex, *tri_normal, *tri_uvw;
+  unsigned long long *count;                 // kRayTreeAttr* words (below); nullptr where a kernel counts nothing
+};
+enum { kRayTreeAttrBlocked = 0, kRayTreeAttrFirst = 1, kRayTreeAttrNormal = 2, kRayTreeAttrUVW = 3,
+       kRayTreeAttrRespawned = 4, kRayTreeAttrWords = 5 };
+
+__device__ __forceinline__ bool raytree_normal_dirty(const RayTreeAttr &T, const RayTreeLayer &L, size_t i) {
+  if (T.normal_stamp == nullptr) return false;
+  const int tri = L.tri[i];
+  return tri >= 0 && T.normal_stamp[tri] > T.normal_gen;
+}
+__device__ __forceinline__ bool raytree_uvw_dirty(const RayTreeAttr &T, const RayTreeLayer &L, size_t i) {
+  if (T.uvw_stamp == nullptr) return false;
+  const int tri = L.tri[i];
+  return tri >= 0 && T.uvw_stamp[tri] > T.uvw_gen;
+}
+// Triangle::GetNormal / GetUVW at the stored point of ray i of L, write_gbuffer_planes's expressions in its order
+__device__ __forceinline__ V3 raytree_attr_at(const RayTreeAttr &T, const double *attr, const RayTreeLayer &L, size_t i) {
+  const size_t tri = (size_t)L.tri[i];
+  const Bary w = barycentric(T.tri_vertex + tri * 9, v3_load(L.point + i * 3));
+  return interpolate(attr + tri * 9, w);
+}
+// one atomic per wave: *at += the lanes of the wave that are here with `flag` set
+__device__ __forceinline__ void raytree_wave_count(unsigned long long *at, bool flag) {
+  const unsigned long long b = __ballot(flag);
+  if (flag && (int)__lane_id() == __ffsll((long long)b) - 1) atomicAdd(at, (unsigned long long)__popcll(b));
+}
+
 // index of chunk pixel (x, y) in layer 0's list
 __host__ __device__ inline size_t raytree_layer0_index(int x, int y, int chunk_w, int chunk_h) {
   const int bx = x >> 3, by = y >> 3;
@@ -698,6 +768,53 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
   }
 }
 
+// ---- edited vertex attributes in a stored tree (include/mythtracer_hip.h, mt_raytree_attr_info_last ff.) ----
+// raytree_attr_check_kernel  part of the CHECK pass, one launch per layer while normal stamps are pending: counts the
+//                            normal-dirty rays that have a reflected child (count[Blocked]) and offers
+//                            (layer << 32 | i) to count[First].  Such a child's ray depends on the edited normal: an
+//                            update refuses, a regrow traces it.  Writes nothing but the two words.
+// raytree_reattr_kernel      part of the COMMIT, one launch per layer, behind raytree_recommit_kernel (the material plane
+//                            holds the effective material by then): normal' to the normal plane of a normal-dirty ray;
+//                            uvw' to the uvw plane (where kept) and the albedo restated from uvw' for a uvw-dirty one.
+//                            Counts both kinds.  Plain grids, one thread per ray.
+struct RayTreeReattrArgs {
+  RayTreeLayer L;
+  RayTreeAttr attr;
+  const mt_material *mtls;  // the scene's CURRENT materials
+  const DevTexture *texs;   // and its CURRENT textures
+  uint32_t n_rays;
+  int32_t layer;
+};
+
+__global__ __launch_bounds__(256) void raytree_attr_check_kernel(RayTreeReattrArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_rays) return;
+  const bool blocked = A.L.child_refl[i] >= 0 && raytree_normal_dirty(A.attr, A.L, i);
+  raytree_wave_count(A.attr.count + kRayTreeAttrBlocked, blocked);
+  if (blocked) atomicMin(A.attr.count + kRayTreeAttrFirst, ((unsigned long long)(unsigned)A.layer << 32) | (unsigned long long)i);
+}
+
+// the albedo of a stored ray with material `mtl` (-1: none) at texture coordinates `uvw`
+__device__ __forceinline__ V3 raytree_albedo_at(const mt_material *mtls, const DevTexture *texs, int mtl, V3 uvw) {
+  const double c[3] = {uvw.x, uvw.y, uvw.z};
+  const double nan = __builtin_nan("");
+  return mtl >= 0 ? retextured_albedo(mtls + mtl, texs, c, 0) : v3(nan, nan, nan);
+}
+
+__global__ __launch_bounds__(256) void raytree_reattr_kernel(RayTreeReattrArgs A) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)A.n_rays) return;
+  const bool nd = raytree_normal_dirty(A.attr, A.L, i), ud = raytree_uvw_dirty(A.attr, A.L, i);
+  if (nd) store3(A.L.normal, i, raytree_attr_at(A.attr, A.attr.tri_normal, A.L, i));
+  if (ud) {
+    const V3 uvw = raytree_attr_at(A.attr, A.attr.tri_uvw, A.L, i);
+    if (A.L.uvw != nullptr) store3(A.L.uvw, i, uvw);
+    store3(A.L.albedo, i, raytree_albedo_at(A.mtls, A.texs, A.L.material[i], uvw));
+  }
+  raytree_wave_count(A.attr.count + kRayTreeAttrNormal, nd);
+  raytree_wave_count(A.attr.count + kRayTreeAttrUVW, ud);
+}
+
 // ---- edited materials that change the tree's shape (include/mythtracer_hip.h, mt_raytree_regrow_materials) ----
 // The NEW tree is built layer by layer, top-down, next to the old one.  A ray of the new tree is KEPT when its path from
 // the pixel exists in the old tree -- every ray of layer 0; a child whose parent is kept and had a child in the same
@@ -728,6 +845,10 @@ __global__ __launch_bounds__(256) void raytree_recommit_kernel(RayTreeRecommitAr
 //   (raytree_trace_kernel)         over the temporary layer, secondary = 1, may_spawn = (k + 1 < max_depth);
 //   raytree_regrow_scatter_kernel  point, normal, albedo, material, power, in_shadow, spawn and (where kept) uvw and tri
 //                                  back to the new layer.
+// A pending NORMAL edit (RayTreeAttr, a tree that keeps tri) adds one reason for a child to be traced rather than kept: the
+// link kernel gives the reflected child of a KEPT normal-dirty parent no old index and spawns it from the parent's
+// effective normal (layer 0's normal plane waits for the commit); the refracted child keeps its index.  The copy kernel
+// restates normal, uvw and albedo of kept dirty rays by raytree_reattr_kernel's rule.
 // That regrouping the traced rays changes no bit is the ray-list contract: layer k handed in as an n x 1 list gives the
 // tree's layers k onwards.  None of these kernels writes a plane of the OLD tree.
 struct RayTreeRegrowFlagsArgs {
@@ -766,6 +887,9 @@ struct RayTreeRegrowLinkArgs {
   const mt_material *mtls;                         // the scene's CURRENT materials
   const int32_t *tri_mtl;                          // as RayTreeRegrowFlagsArgs has it: the parent is layer 0, else nullptr
   uint32_t n_parent;
+  // a pending normal edit: the reflected child of a KEPT normal-dirty parent is not kept -- it is spawned from the
+  // parent's effective normal and traced (counted in count[Respawned])
+  RayTreeAttr attr;
 };
 
 __global__ __launch_bounds__(256) void raytree_regrow_link_kernel(RayTreeRegrowLinkArgs A) {
@@ -774,7 +898,14 @@ __global__ __launch_bounds__(256) void raytree_regrow_link_kernel(RayTreeRegrowL
   const int cr = A.parent.child_refl[i], ct = A.parent.child_refr[i];
   if (cr < 0 && ct < 0) return;
   const int s = A.parent_src != nullptr ? A.parent_src[i] : (int)i;
-  const int ocr = s >= 0 ? A.old_child_refl[s] : -1, oct = s >= 0 ? A.old_child_refr[s] : -1;
+  int ocr = s >= 0 ? A.old_child_refl[s] : -1;
+  const int oct = s >= 0 ? A.old_child_refr[s] : -1;
+  // (a traced parent's normal plane comes from the current attributes already)
+  const bool renormal = s >= 0 && raytree_normal_dirty(A.attr, A.parent, i);
+  if (renormal) {
+    raytree_wave_count(A.attr.count + kRayTreeAttrRespawned, cr >= 0 && ocr >= 0);
+    ocr = -1;
+  }
   const V3 dir = v3_load(A.parent.ray + i * 6 + 3);
   const V3 Pt = v3_load(A.parent.point + i * 3);
   const double coef = A.parent.coef[i];
@@ -784,7 +915,8 @@ __global__ __launch_bounds__(256) void raytree_regrow_link_kernel(RayTreeRegrowL
     A.child.spawn[cr] = ocr < 0 ? 1 : 0;
     A.child.coef[cr] = coef * A.mtls[raytree_effective_material(A.parent, A.tri_mtl, i)].reflectance;  // :187
     if (ocr < 0) {  // raytree_spawn_kernel's reflected child
-      V3 Nn = v3_load(A.parent.normal + i * 3);  // as GetNormal returned it, :38
+      // as GetNormal returned it, :38 (layer 0's normal plane waits for the commit: the effective normal)
+      V3 Nn = renormal ? raytree_attr_at(A.attr, A.attr.tri_normal, A.parent, i) : v3_load(A.parent.normal + i * 3);
       if (dot(Nn, -dir) < 0.0) Nn = -Nn;         // :42-45
       const V3 Rd = dir - Nn * (2 * dot(dir, Nn));  // :68-69
       const V3 ro = Pt + (Rd * 0.0001);             // :70-74
@@ -817,6 +949,7 @@ struct RayTreeRegrowCopyArgs {
   const DevTexture *texs;         // and its CURRENT textures
   const uint8_t *albedo_changed;  // [n_materials], nullptr: no albedo to rewrite for a material's own sake
   const int32_t *tri_mtl;         // the scene's CURRENT assignment while a reassignment is pending, else nullptr
+  RayTreeAttr attr;               // pending attribute edits: raytree_reattr_kernel's rule for the kept rays (counted)
 };
 
 __global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowCopyArgs A) {
@@ -829,13 +962,22 @@ __global__ __launch_bounds__(256) void raytree_regrow_copy_kernel(RayTreeRegrowC
   store3(A.to.ray, j * 2 + 1, v3_load(A.from.ray + s * 6 + 3));
   A.to.in_object[j] = A.from.in_object[s];
   store3(A.to.point, j, v3_load(A.from.point + s * 3));
-  store3(A.to.normal, j, v3_load(A.from.normal + s * 3));
+  const bool nd = raytree_normal_dirty(A.attr, A.from, s), ud = raytree_uvw_dirty(A.attr, A.from, s);
+  store3(A.to.normal, j, nd ? raytree_attr_at(A.attr, A.attr.tri_normal, A.from, s) : v3_load(A.from.normal + s * 3));
   const int was = A.from.material[s];
   const int mtl = raytree_effective_material(A.from, A.tri_mtl, s);
   A.to.material[j] = mtl;
-  if (A.to.uvw != nullptr) store3(A.to.uvw, j, v3_load(A.from.uvw + s * 3));
   if (A.to.tri != nullptr) A.to.tri[j] = A.from.tri[s];
-  if (mtl != was) {
+  if (A.attr.count != nullptr) {
+    raytree_wave_count(A.attr.count + kRayTreeAttrNormal, nd);
+    raytree_wave_count(A.attr.count + kRayTreeAttrUVW, ud);
+  }
+  if (!ud && A.to.uvw != nullptr) store3(A.to.uvw, j, v3_load(A.from.uvw + s * 3));
+  if (ud) {  // uvw' in the stored uvw's place, for the plane and for the albedo whatever else changed
+    const V3 uvw = raytree_attr_at(A.attr, A.attr.tri_uvw, A.from, s);
+    if (A.to.uvw != nullptr) store3(A.to.uvw, j, uvw);
+    store3(A.to.albedo, j, raytree_albedo_at(A.mtls, A.texs, mtl, uvw));
+  } else if (mtl != was) {
     store3(A.to.albedo, j, raytree_restated_albedo(A.mtls, A.texs, mtl, A.from.uvw, s));
   } else if (A.albedo_changed != nullptr && mtl >= 0 && mtl < A.n_materials && A.albedo_changed[mtl] != 0) {
     store3(A.to.albedo, j, retextured_albedo(A.mtls + mtl, A.texs, A.from.uvw, s));

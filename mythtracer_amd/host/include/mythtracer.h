@@ -232,6 +232,12 @@ class MythTracer {
   // upload: the call edits, it does not add).  Before the first upload it is Prepare.  RayTrees built before the edit
   // are stale until UpdateRayTreeMaterials / RegrowRayTree, which need a tree that keeps triangles for it.
   bool UpdateTriangleMaterials();
+  // After triangles' per-vertex NORMALS or texture coordinates were edited (GetScene()->tree.MutableTriangle(i)->normal
+  // / ->uvw): flattens them again in the uploaded order and replaces them on every device replica
+  // (mt_scene_set_triangle_normals, mt_scene_set_triangle_uvw), without uploading a triangle again.  Vertex positions
+  // are not covered: a moved vertex needs a new upload.  Before the first upload it is Prepare.  RayTrees built before
+  // the edit are stale until UpdateRayTreeMaterials / RegrowRayTree, which need a tree that keeps triangles for it.
+  bool UpdateTriangleAttributes();
   // RayTrees built from now on also keep the triangle each ray hit (mt_scene_set_raytree_tri): 4 bytes more per ray,
   // and UpdateRayTreeMaterials / RegrowRayTree then take an UpdateTriangleMaterials, which they refuse for a tree
   // without.  Off by default; independent of SetRayTreeKeepUVW (a reassignment TO a textured material needs both).

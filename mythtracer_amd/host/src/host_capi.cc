@@ -630,6 +630,33 @@ int mth_assign_material(void* p, const int32_t* add_indices, int n, const char* 
 // MythTracer::UpdateTriangleMaterials; 0 with the facade's message when it refuses
 int mth_update_triangle_materials(void* p) { return static_cast<Handle*>(p)->mt.UpdateTriangleMaterials() ? 1 : 0; }
 
+// Triangle::normal (which = 0) or Triangle::uvw (1) of the listed triangles (AddPrimitive indices) replaced by
+// attr[n][9], through OctTree::MutableTriangle; nothing is uploaded (mth_update_triangle_attributes does that).  0 with
+// the shim's message for a bad list or an index outside the scene's triangles: no triangle is changed then.
+int mth_set_triangle_attr(void* p, int which, const int32_t* add_indices, int n, const double* attr) {
+  Handle* h = static_cast<Handle*>(p);
+  auto* scene = h->mt.GetScene();
+  if ((which != 0 && which != 1) || n < 0 || (n > 0 && (add_indices == nullptr || attr == nullptr))) {
+    h->shim_error = "bad triangle attribute list";
+    return 0;
+  }
+  for (int i = 0; i < n; i++) {
+    if (add_indices[i] < 0 || (size_t)add_indices[i] >= scene->tree.PrimitiveCount()) {
+      h->shim_error = "triangle index " + std::to_string(add_indices[i]) + " outside the scene's " +
+                      std::to_string(scene->tree.PrimitiveCount()) + " triangles";
+      return 0;
+    }
+  }
+  for (int i = 0; i < n; i++) {
+    auto* t = scene->tree.MutableTriangle((size_t)add_indices[i]);
+    memcpy(which == 0 ? (void*)t->normal : (void*)t->uvw, attr + (size_t)i * 9, 72);
+  }
+  return 1;
+}
+
+// MythTracer::UpdateTriangleAttributes; 0 with the facade's message when it refuses
+int mth_update_triangle_attributes(void* p) { return static_cast<Handle*>(p)->mt.UpdateTriangleAttributes() ? 1 : 0; }
+
 // MythTracer::SetRayTreeKeepTriangles
 void mth_set_raytree_keep_triangles(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepTriangles(keep != 0); }
 

@@ -260,6 +260,30 @@ bool MythTracer::UpdateTriangleMaterials() {
   return true;
 }
 
+bool MythTracer::UpdateTriangleAttributes() {
+  if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes them as they are
+  // FlatScene::Build's stream order
+  const FlatTree& f = scene.tree.Flat();
+  const size_t nt = f.tri_id.size();
+  std::vector<double> normal(nt * 9), uvw(nt * 9);
+  for (size_t s = 0; s < nt; s++) {
+    const Triangle* t = scene.tree.GetTriangle((size_t)f.tri_id[s]);
+    memcpy(&normal[s * 9], t->normal, 72);
+    memcpy(&uvw[s * 9], t->uvw, 72);
+  }
+  std::vector<mt_scene*> all(1, dev_);
+  all.insert(all.end(), replicas_.begin(), replicas_.end());
+  for (mt_scene* s : all) {
+    if (mt_scene_set_triangle_normals(s, normal.data(), (int)nt) != MT_OK ||
+        mt_scene_set_triangle_uvw(s, uvw.data(), (int)nt) != MT_OK) {
+      error_ = std::string("triangle attribute update failed: ") + mt_last_error();
+      fprintf(stderr, "error: %s\n", error_.c_str());
+      return false;
+    }
+  }
+  return true;
+}
+
 void MythTracer::SetRayTreeKeepTriangles(bool keep) {
   keep_tri_ = keep;
   if (dev_ != nullptr) (void)mt_scene_set_raytree_tri(dev_, keep ? 1 : 0);
