@@ -1190,6 +1190,83 @@ int mt_intersect_rays(mt_scene *scene, int n, const double *rays,
  * reference's, never the other way round). */
 int mt_scene_set_traversal_mode(mt_scene *scene, int mode);
 
+/* The octree built ON THE GPU from triangles in ADD order (AddPrimitive order): node for node and bit for bit the tree
+ * OctTree::Finalize builds on the host (the reference's AttemptSplit, octtree.cc:52-135).  (No reference counterpart:
+ * the reference builds on one host thread.)  tri_vertex is a HOST array of n_tris x 9 doubles.  The result is opaque
+ * and lives on `device`; NULL with mt_last_error set on failure, and nothing is left allocated then.
+ * The rules, each the host builder's with the same fp64 operations in the same order:
+ *   triangle box (Triangle::CacheAABB): {v0, v0} extended by v1, then v2, with std::min(box, p) / std::max(box, p): a
+ *     NaN in v0 stays, a NaN in v1 or v2 is ignored;
+ *   root box (OctTree::AddPrimitive): {0,0,0}-{0,0,0} extended by every triangle box: a NaN bound never enters, a bound
+ *     that comes out as zero is +0.0;
+ *   a node splits iff at least 16 triangles reached it, at c = lo + (hi - lo) / 2.0 per axis, into the eight octants
+ *     of mt_scene_desc's child order; a triangle goes to the FIRST child whose box contains its box (closed intervals:
+ *     any NaN means not contained), else it stays; the children of one level's nodes are numbered in the order of their
+ *     parents, so a level is a contiguous range of node indices; centre is zero for a node that does not split;
+ *   the stream: nodes in index order, a node's triangles in ascending add index.
+ * How: mt_build.h -- a level-by-level descent with integer counters (one host round trip per level reads how many
+ * nodes split), then one stable sort of (node, add index).  Nothing depends on the order in which atomics arrive: two
+ * builds of the same input give the same bytes.
+ * Limits: a node that would have to split at depth MT_MAX_TREE_DEPTH (root = 1) ends the build with
+ * MT_ERR_UNSUPPORTED and mt_scene_create's message ("octree depth %d exceeds MT_MAX_TREE_DEPTH %d"), the verdict
+ * mt_scene_create gives for such a tree built on the host; more nodes than an int32 indexes are MT_ERR_UNSUPPORTED; an
+ * allocation that does not fit is MT_ERR_NOMEM.  n_tris = 0 is a tree of one node, the box {0,0,0}-{0,0,0}.
+ * Argument checks come before any device call, in this order, all MT_ERR_ARG: n_tris negative; tri_vertex NULL with
+ * n_tris > 0; then the device ordinal (mt_device_count: "device %d outside 0..%d").  Values are not checked.
+ * info (nullable): n_nodes; depth (root = 1); levels = the host round trips made (= depth); kernel_ms by HIP events from
+ * the first to the last kernel, the per-level round trips included; total_ms = wall time of the call. */
+typedef struct mt_octree mt_octree;
+typedef struct mt_build_info {
+  int32_t n_nodes, depth, levels;
+  double kernel_ms, total_ms;
+} mt_build_info;
+/* The arrays of a tree, the FlatTree of the facade.  n_nodes, n_tris and depth are always written by a read; every
+ * pointer is the caller's buffer of the size given, or NULL for an array that is not wanted. */
+typedef struct mt_octree_arrays {
+  int32_t n_nodes, n_tris, depth;
+  double *node_aabb;     /* n_nodes x 6 */
+  double *node_center;   /* n_nodes x 3 */
+  int32_t *first_child;  /* n_nodes */
+  int32_t *prim_begin;   /* n_nodes */
+  int32_t *prim_count;   /* n_nodes */
+  int32_t *tri_id;       /* n_tris: stream position -> add index */
+  double *tri_aabb;      /* n_tris x 6, in ADD order */
+} mt_octree_arrays;
+mt_octree *mt_octree_build(int device, int n_tris, const double *tri_vertex, mt_build_info *info);
+/* MT_ERR_ARG: tree or out NULL. */
+int mt_octree_info(const mt_octree *tree, mt_build_info *out);
+int mt_octree_read(const mt_octree *tree, mt_octree_arrays *out);
+void mt_octree_destroy(mt_octree *tree);
+
+/* A scene from triangles in ADD order: the tree is built on the GPU (mt_octree_build on d->device), the triangle arrays
+ * are gathered into node-stream order with its tri_id, and the description goes through mt_scene_create's own
+ * path: validation, derived records and every message are mt_scene_create's.
+ * CONTRACT: the scene is indistinguishable from mt_scene_create on the host-built description of the same triangles --
+ * every frame, plane, statistic and getter, and tri_id (the G-buffer's `prim` plane).
+ * Checks before any device call, in this order, all MT_ERR_ARG: d NULL; struct_size / abi_version; a negative count;
+ * a triangle array missing with n_tris > 0 (tri_vertex, tri_normal, tri_uvw, tri_material, tri_line_no); the material
+ * or texture array missing with a count > 0; then mt_octree_build's device check.  What mt_scene_create checks in the
+ * description (material and texture indices, texture sizes) it checks here too, after the build.
+ * info (nullable): the build's, as mt_octree_build reports it. */
+typedef struct mt_triangle_desc {
+  uint32_t struct_size; /* sizeof(mt_triangle_desc) */
+  uint32_t abi_version; /* MT_ABI_VERSION */
+  int32_t device;
+  int32_t n_tris, n_materials, n_textures;
+  const double *tri_vertex;     /* n_tris x 9, ADD order like the four below */
+  const double *tri_normal;
+  const double *tri_uvw;
+  const int32_t *tri_material;
+  const int32_t *tri_line_no;
+  const mt_material *materials;
+  const mt_texture *textures;
+} mt_triangle_desc;
+mt_scene *mt_scene_create_triangles(const mt_triangle_desc *d, mt_build_info *info);
+
+/* The same arrays from ANY scene: its node records and triangle boxes read back from the device, its tri_id mirror.
+ * Checks, in this order, all MT_ERR_ARG: scene NULL; out NULL; a scene made without tri_id. */
+int mt_scene_read_tree(const mt_scene *scene, mt_octree_arrays *out);
+
 #ifdef __cplusplus
 }
 #endif

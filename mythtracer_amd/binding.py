@@ -44,6 +44,8 @@ HIP_SYMBOLS = [
     "mt_raytree_read_tri", "mt_raytree_keeps_tri",
     "mt_scene_set_triangle_normals", "mt_scene_set_triangle_uvw", "mt_scene_get_triangle_normals",
     "mt_scene_get_triangle_uvw", "mt_raytree_attr_info_last",
+    "mt_octree_build", "mt_octree_info", "mt_octree_read", "mt_octree_destroy", "mt_scene_create_triangles",
+    "mt_scene_read_tree",
 ]
 MT_MAX_RECURSION = 16
 
@@ -123,6 +125,28 @@ class mt_raytree_attr_info(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class mt_build_info(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("depth", C.c_int32), ("levels", C.c_int32),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class mt_octree_arrays(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("n_tris", C.c_int32), ("depth", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("node_aabb", "node_center", "first_child", "prim_begin", "prim_count", "tri_id",
+                                  "tri_aabb")]
+
+
+class mt_triangle_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("device", C.c_int32),
+                ("n_tris", C.c_int32), ("n_materials", C.c_int32), ("n_textures", C.c_int32),
+                ("tri_vertex", C.c_void_p), ("tri_normal", C.c_void_p), ("tri_uvw", C.c_void_p),
+                ("tri_material", C.c_void_p), ("tri_line_no", C.c_void_p),
+                ("materials", C.c_void_p), ("textures", C.c_void_p)]
 
 
 class mt_lean_info(C.Structure):
@@ -336,6 +360,15 @@ class HipAbi:
         L.mt_scene_get_triangle_normals.argtypes = [vp, vp, ci]
         L.mt_scene_get_triangle_uvw.argtypes = [vp, vp, ci]
         L.mt_raytree_attr_info_last.argtypes = [vp, C.POINTER(mt_raytree_attr_info)]
+        L.mt_octree_build.restype = vp
+        L.mt_octree_build.argtypes = [ci, ci, vp, C.POINTER(mt_build_info)]
+        L.mt_octree_info.argtypes = [vp, C.POINTER(mt_build_info)]
+        L.mt_octree_read.argtypes = [vp, C.POINTER(mt_octree_arrays)]
+        L.mt_octree_destroy.argtypes = [vp]
+        L.mt_octree_destroy.restype = None
+        L.mt_scene_create_triangles.restype = vp
+        L.mt_scene_create_triangles.argtypes = [C.POINTER(mt_triangle_desc), C.POINTER(mt_build_info)]
+        L.mt_scene_read_tree.argtypes = [vp, C.POINTER(mt_octree_arrays)]
         L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
@@ -462,13 +495,7 @@ class HipAbi:
         mats = flat.get("materials", [])
         marr = self._material_array(mats)
         texs = flat.get("textures", [])
-        tarr = (mt_texture * max(len(texs), 1))()
-        for i, t in enumerate(texs):
-            texels = np.ascontiguousarray(t["texels"])
-            keep.append(texels)
-            tarr[i].height, tarr[i].width = texels.shape[0], texels.shape[1]
-            tarr[i].format = MT_TEX_RGB8 if texels.dtype == np.uint8 else MT_TEX_F64
-            tarr[i].texels = texels.ctypes.data
+        tarr = self._texture_array(texs, keep)
         keep += [marr, tarr]
         d.n_materials = len(mats)
         d.n_textures = len(texs)
@@ -481,6 +508,91 @@ class HipAbi:
 
     def scene_destroy(self, h):
         self.lib.mt_scene_destroy(h)
+
+    def _texture_array(self, texs, keep):
+        tarr = (mt_texture * max(len(texs), 1))()
+        for i, t in enumerate(texs):
+            texels = np.ascontiguousarray(t["texels"])
+            keep.append(texels)
+            tarr[i].height, tarr[i].width = texels.shape[0], texels.shape[1]
+            tarr[i].format = MT_TEX_RGB8 if texels.dtype == np.uint8 else MT_TEX_F64
+            tarr[i].texels = texels.ctypes.data
+        return tarr
+
+    def _read_tree(self, fn, h) -> dict:
+        """The arrays of mt_octree_arrays through `fn` (mt_octree_read / mt_scene_read_tree): first the counts, then
+        the arrays."""
+        a = mt_octree_arrays()
+        self.check(fn(h, C.byref(a)))
+        nn, nt = int(a.n_nodes), int(a.n_tris)
+        out = dict(node_aabb=np.zeros((nn, 6)), node_center=np.zeros((nn, 3)),
+                   first_child=np.zeros(nn, dtype=np.int32), prim_begin=np.zeros(nn, dtype=np.int32),
+                   prim_count=np.zeros(nn, dtype=np.int32), tri_id=np.zeros(max(nt, 1), dtype=np.int32),
+                   tri_aabb=np.zeros((max(nt, 1), 6)))
+        for name, arr in out.items():
+            setattr(a, name, arr.ctypes.data)
+        self.check(fn(h, C.byref(a)))
+        out["tri_id"], out["tri_aabb"] = out["tri_id"][:nt], out["tri_aabb"][:nt]
+        out["depth"] = int(a.depth)
+        return out
+
+    def octree_build(self, tri_vertex, device: int = 0):
+        """mt_octree_build: the octree of the triangles `tri_vertex` ((n, 3, 3) or (n, 9) doubles in add order) built on
+        the GPU.  Returns (handle, info) with info = dict(n_nodes, depth, levels, kernel_ms, total_ms); the handle goes to
+        octree_read / octree_destroy.  RuntimeError with the library's message when the build fails."""
+        v = np.ascontiguousarray(tri_vertex, dtype=np.float64)
+        if v.size % 9:
+            raise ValueError("a triangle has 9 doubles, not %d in all" % v.size)
+        info = mt_build_info()
+        h = self.lib.mt_octree_build(device, v.size // 9, v.ctypes.data if v.size else None, C.byref(info))
+        if not h:
+            raise RuntimeError("mt_octree_build failed: " + self.last_error())
+        return h, info.as_dict()
+
+    def octree_read(self, tree) -> dict:
+        """mt_octree_read: dict(depth, node_aabb, node_center, first_child, prim_begin, prim_count, tri_id, tri_aabb);
+        tri_aabb is in add order."""
+        return self._read_tree(self.lib.mt_octree_read, tree)
+
+    def octree_destroy(self, tree):
+        self.lib.mt_octree_destroy(tree)
+
+    def scene_read_tree(self, h) -> dict:
+        """mt_scene_read_tree: the same arrays from any scene made with tri_id."""
+        return self._read_tree(self.lib.mt_scene_read_tree, h)
+
+    def scene_create_triangles(self, tris: dict, device: int = 0):
+        """mt_scene_create_triangles.  tris: tri_vertex, tri_normal, tri_uvw ((n, 9) doubles), tri_material, tri_line_no
+        (n int32) in ADD order, materials and textures as in scene_create's flat.  Returns (scene handle, build info)."""
+        keep = []
+
+        def arr(name, dt):
+            a = np.ascontiguousarray(tris[name], dtype=dt)
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        d = mt_triangle_desc()
+        d.struct_size = C.sizeof(mt_triangle_desc)
+        d.abi_version = MT_ABI_VERSION
+        d.device = device
+        d.n_tris = len(tris["tri_material"])
+        d.tri_vertex = arr("tri_vertex", np.float64)
+        d.tri_normal = arr("tri_normal", np.float64)
+        d.tri_uvw = arr("tri_uvw", np.float64)
+        d.tri_material = arr("tri_material", np.int32)
+        d.tri_line_no = arr("tri_line_no", np.int32)
+        mats = tris.get("materials", [])
+        texs = tris.get("textures", [])
+        marr = self._material_array(mats)
+        tarr = self._texture_array(texs, keep)
+        d.n_materials, d.n_textures = len(mats), len(texs)
+        d.materials = C.cast(marr, C.c_void_p)
+        d.textures = C.cast(tarr, C.c_void_p)
+        info = mt_build_info()
+        h = self.lib.mt_scene_create_triangles(C.byref(d), C.byref(info))
+        if not h:
+            raise RuntimeError("mt_scene_create_triangles failed: " + self.last_error())
+        return h, info.as_dict()
 
     def set_lights(self, h, lights):
         l = _f64(lights).reshape(-1, 12)
@@ -1200,6 +1312,11 @@ def host_lib():
     L.mth_set_raytree_keep_triangles.restype = None
     L.mth_set_triangle_attr.argtypes = [vp, ci, vp, ci, vp]
     L.mth_update_triangle_attributes.argtypes = [vp]
+    L.mth_set_device_tree_build.argtypes = [vp, ci]
+    L.mth_set_device_tree_build.restype = None
+    L.mth_set_triangle_vertices.argtypes = [vp, vp, ci, vp]
+    L.mth_update_geometry.argtypes = [vp]
+    L.mth_update_geometry.restype = None
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1568,6 +1685,37 @@ class MythTracer:
         that keeps triangles."""
         if not self.L.mth_update_triangle_attributes(self.h):
             raise RuntimeError("UpdateTriangleAttributes failed: " + self.last_error())
+
+    def set_device_tree_build(self, on: bool):
+        """MythTracer::SetDeviceTreeBuild: the next finalize / prepare builds the octree on the GPU (mt_octree_build),
+        bit for bit the host builder's tree.  Off by default; with it on, no GPU or a failed build is an error, never
+        the host builder instead."""
+        self.L.mth_set_device_tree_build(self.h, 1 if on else 0)
+
+    def set_triangle_vertices(self, add_indices, vertices):
+        """MythTracer::SetTriangleVertices: the vertices of the triangles `add_indices` (add_triangle / .obj order)
+        replaced by `vertices` (n x 3 x 3) and their boxes cached again.  Only the host scene changes:
+        update_geometry() must follow.  RuntimeError for an index outside the scene's triangles; no triangle is
+        changed then."""
+        a = np.ascontiguousarray(add_indices, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        if v.size != a.size * 9:
+            raise ValueError("%d triangles need %d doubles, not %d" % (a.size, a.size * 9, v.size))
+        if not self.L.mth_set_triangle_vertices(self.h, a.ctypes.data if a.size else None, int(a.size),
+                                                v.ctypes.data if v.size else None):
+            raise RuntimeError("set_triangle_vertices failed: " + self.last_error())
+
+    def update_geometry(self):
+        """MythTracer::UpdateGeometry: the root box again over all triangles, the tree unfinalized and the device
+        scenes dropped; the next prepare / render builds and uploads again, with either builder.  The RayTrees of this
+        object live on the dropped scene: they are closed first (a closed RayTree raises on use, it never reports
+        itself fresh)."""
+        for ref in getattr(self, "_trees", []):
+            t = ref()
+            if t is not None:
+                t.close()
+        self._trees = []
+        self.L.mth_update_geometry(self.h)
 
     def set_raytree_keep_triangles(self, keep: bool):
         """MythTracer::SetRayTreeKeepTriangles: RayTrees built from now on keep the triangle each ray hit."""

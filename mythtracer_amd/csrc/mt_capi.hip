@@ -31,6 +31,7 @@
 #include "mt_gbuffer.h"
 #include "mt_lightbuffer.h"
 #include "mt_raytree.h"
+#include "mt_build.h"
 
 using namespace mt;
 
@@ -976,7 +977,8 @@ void fill_stats(const unsigned long long *c, mt_stats *st) {
 // Between the two: begin -- the scene's work counters cleared, or left alone by a call that has none, and the first of
 // the call's two events --, the launches, then the pieces of the way back in the caller's order: mark_end,
 // counters_home, and close, which waits for the stream, checks the device status and fills `stats`.  Everything is
-// queued on the null stream.
+// queued on the null stream.  (mt_octree_build has no scene yet: a frame without one has no counters and no stats, only
+// the two events and the wait.)
 struct HostCall {
   mt_scene *const s;
   mt_stats *const stats;
@@ -987,10 +989,12 @@ struct HostCall {
   bool begun = false;     // ev0 is on the stream: close waits, kernel_ms is ev0 .. ev1
   bool counters = false;  // the call has work counters: h_counters is checked and reported
   HostCall(mt_scene *scene, mt_stats *st, hipEvent_t &e0, hipEvent_t &e1)
-      : s(scene), stats(st), ev0(e0), ev1(e1), counters_were(scene->stats_enabled) {
-    if (stats) s->stats_enabled = true;  // the caller asked for them
+      : s(scene), stats(st), ev0(e0), ev1(e1), counters_were(scene != nullptr && scene->stats_enabled) {
+    if (stats && s) s->stats_enabled = true;  // the caller asked for them
   }
-  ~HostCall() { s->stats_enabled = counters_were; }
+  ~HostCall() {
+    if (s) s->stats_enabled = counters_were;
+  }
   HostCall(const HostCall &) = delete;
   HostCall &operator=(const HostCall &) = delete;
   int clear_counters() {
@@ -4479,6 +4483,347 @@ int mt_intersect_rays(mt_scene *s, int n, const double *rays, int32_t *tri, int3
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     stats->kernel_ms = ms;
+  }
+  return MT_OK;
+}
+
+// ---- the octree built on the GPU (mt_build.h) ---------------------------------------------------------------------
+struct mt_octree {
+  int device = 0;
+  int32_t n_tris = 0, n_nodes = 0, depth = 0;
+  mt_build_info info{};
+  Buf<double> d_aabb, d_center, d_tri_aabb;
+  Buf<int32_t> d_first_child, d_prim_begin, d_prim_count, d_tri_id;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace {
+
+extern "C++" {
+
+// b grown to `want` elements with its first `keep` kept; what does not fit is MT_ERR_NOMEM with b as it was
+template <typename T>
+int build_grow(Buf<T> &b, size_t keep, size_t want, const char *what, hipStream_t stream) {
+  Buf<T> grown;
+  MT_TRY(attr_nomem(grown.ensure(want * sizeof(T)), want * sizeof(T), what));
+  if (keep) HIP_TRY(hipMemcpyAsync(grown.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  std::swap(b.p, grown.p);
+  std::swap(b.bytes, grown.bytes);
+  return MT_OK;
+}
+
+template <typename T>
+int build_room(Buf<T> &b, size_t count, const char *what) {
+  return attr_nomem(b.ensure(count * sizeof(T)), count * sizeof(T), what);
+}
+
+// rocPRIM's exclusive scan of n values of `in` into out, on `stream`, through the scratch buffer `temp`
+template <typename In>
+int build_scan(Buf<char> &temp, In in, int32_t *out, size_t n, hipStream_t stream) {
+  size_t bytes = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, (int32_t)0, n, rocprim::plus<int32_t>(), stream));
+  MT_TRY(build_room(temp, bytes, "the scan's scratch memory"));
+  HIP_TRY(rocprim::exclusive_scan((void *)temp.p, bytes, in, out, (int32_t)0, n, rocprim::plus<int32_t>(), stream));
+  return MT_OK;
+}
+
+}  // extern "C++"
+
+// The build of t->n_tris triangles on t->device: mt_build.h's kernels level by level, one round trip per level.
+int octree_build(mt_octree *t, const double *tri_vertex) {
+  const auto w0 = std::chrono::steady_clock::now();
+  const int32_t n = t->n_tris;
+  const size_t nt = (size_t)n;
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipEventCreate(&t->ev0));
+  HIP_TRY(hipEventCreate(&t->ev1));
+  HostCall call(nullptr, nullptr, t->ev0, t->ev1);
+  const hipStream_t stream = call.stream;
+  // ---- everything whose size is known: the triangles' arrays, the first nodes
+  Buf<double> d_vertex;
+  Buf<int32_t> d_cur, d_reached, d_split_before, d_value;
+  Buf<uint32_t> d_key, d_key_sorted;
+  Buf<unsigned long long> d_root_key;
+  Buf<char> d_temp;
+  size_t cap = nt / 2 + 1024;  // nodes the arrays hold; doubled when a level does not fit
+  MT_TRY(build_room(d_vertex, nt * 9, "the triangles' vertices"));
+  MT_TRY(build_room(t->d_tri_aabb, nt * 6, "the triangles' boxes"));
+  MT_TRY(build_room(d_cur, nt, "the triangles' nodes"));
+  MT_TRY(build_room(d_key, nt, "the sort's keys"));
+  MT_TRY(build_room(d_key_sorted, nt, "the sort's keys"));
+  MT_TRY(build_room(d_value, nt, "the sort's values"));
+  MT_TRY(build_room(t->d_tri_id, nt, "the tree's tri_id"));
+  MT_TRY(build_room(d_root_key, 6, "the root box"));
+  MT_TRY(build_room(t->d_aabb, cap * 6, "the nodes' boxes"));
+  MT_TRY(build_room(t->d_center, cap * 3, "the nodes' centres"));
+  MT_TRY(build_room(t->d_first_child, cap, "the nodes' children"));
+  MT_TRY(build_room(d_reached, cap, "the nodes' counters"));
+  MT_TRY(build_room(t->d_prim_count, cap, "the nodes' counts"));
+  const unsigned long long zero_keys[6] = {kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero};
+  HIP_TRY(hipMemcpy(d_root_key, zero_keys, sizeof zero_keys, hipMemcpyHostToDevice));
+  if (n > 0) {
+    HIP_TRY(hipMemcpy(d_vertex, tri_vertex, nt * 72, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_cur, 0, nt * sizeof(int32_t), stream));  // every triangle starts at the root
+  }
+  auto tree = [&]() {
+    BuildTree T{};
+    T.aabb = t->d_aabb;
+    T.center = t->d_center;
+    T.first_child = t->d_first_child;
+    T.reached = d_reached;
+    T.prim_count = t->d_prim_count;
+    return T;
+  };
+  MT_TRY(call.begin(false));
+  if (n > 0) HIP_TRY(launch_flat(build_tri_box_kernel, nt, stream, d_vertex.p, (uint32_t)n, t->d_tri_aabb.p, d_root_key.p));
+  hipLaunchKernelGGL(build_root_kernel, dim3(1), dim3(64), 0, stream, tree(), d_root_key.p, n);
+  HIP_TRY(hipGetLastError());
+  // ---- level by level: a level is the contiguous range [level_begin, level_begin + level_n) of node indices
+  int32_t level_begin = 0, level_n = 1, n_nodes = 1;
+  int depth = 1, levels = 0;
+  for (int level = 1; level <= MT_MAX_TREE_DEPTH; level++) {
+    levels++;
+    MT_TRY(build_room(d_split_before, (size_t)level_n, "the level's split counts"));
+    MT_TRY(build_scan(d_temp, rocprim::make_transform_iterator((const int32_t *)d_reached.p + level_begin, BuildSplits()),
+                      d_split_before.p, (size_t)level_n, stream));
+    int32_t last[2] = {0, 0};  // the splitting nodes before the level's last node; what reached that node
+    HIP_TRY(hipMemcpyAsync(&last[0], d_split_before.p + (level_n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&last[1], d_reached.p + level_begin + (level_n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const long long splits = (long long)last[0] + (last[1] >= kBuildSplit ? 1 : 0);
+    if (splits == 0) break;
+    if (level == MT_MAX_TREE_DEPTH) {
+      return fail(MT_ERR_UNSUPPORTED, "octree depth %d exceeds MT_MAX_TREE_DEPTH %d", level + 1, MT_MAX_TREE_DEPTH);
+    }
+    const long long grown = (long long)n_nodes + 8 * splits;
+    if (grown > 0x7fffffffll) {
+      return fail(MT_ERR_UNSUPPORTED, "the octree needs %lld nodes, more than an int32 indexes", grown);
+    }
+    if ((size_t)grown > cap) {
+      size_t want = cap;
+      while (want < (size_t)grown) want *= 2;
+      MT_TRY(build_grow(t->d_aabb, (size_t)n_nodes * 6, want * 6, "the nodes' boxes", stream));
+      MT_TRY(build_grow(t->d_center, (size_t)n_nodes * 3, want * 3, "the nodes' centres", stream));
+      MT_TRY(build_grow(t->d_first_child, (size_t)n_nodes, want, "the nodes' children", stream));
+      MT_TRY(build_grow(d_reached, (size_t)n_nodes, want, "the nodes' counters", stream));
+      MT_TRY(build_grow(t->d_prim_count, (size_t)n_nodes, want, "the nodes' counts", stream));
+      cap = want;
+    }
+    HIP_TRY(launch_flat(build_split_kernel, (size_t)level_n, stream, tree(), level_begin, level_n, (const int32_t *)d_split_before.p, n_nodes));
+    HIP_TRY(launch_flat(build_descend_kernel, nt, stream, tree(), (const double *)t->d_tri_aabb.p, d_cur.p, (uint32_t)n));
+    level_begin = n_nodes;
+    level_n = (int32_t)(8 * splits);
+    n_nodes = (int32_t)grown;
+    depth = level + 1;
+  }
+  // ---- the stream: prim_count, prim_begin, and the stable sort of (node, add index)
+  MT_TRY(build_room(t->d_prim_begin, (size_t)n_nodes, "the nodes' prim_begin"));
+  if (n > 0) {
+    HIP_TRY(launch_flat(build_finish_kernel, nt, stream, tree(), (const int32_t *)d_cur.p, (uint32_t)n, d_key.p, d_value.p));
+  }
+  MT_TRY(build_scan(d_temp, (const int32_t *)t->d_prim_count.p, t->d_prim_begin.p, (size_t)n_nodes, stream));
+  if (n > 0) {
+    unsigned end_bit = 1;
+    while (end_bit < 32 && ((unsigned)(n_nodes - 1) >> end_bit) != 0) end_bit++;
+    size_t bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, d_key.p, d_key_sorted.p, d_value.p, t->d_tri_id.p, nt, 0u, end_bit, stream));
+    MT_TRY(build_room(d_temp, bytes, "the sort's scratch memory"));
+    HIP_TRY(rocprim::radix_sort_pairs((void *)d_temp.p, bytes, d_key.p, d_key_sorted.p, d_value.p, t->d_tri_id.p, nt, 0u, end_bit, stream));
+  }
+  MT_TRY(call.mark_end());
+  MT_TRY(call.close());  // (waits for the stream)
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+  t->n_nodes = n_nodes;
+  t->depth = depth;
+  t->info.n_nodes = n_nodes;
+  t->info.depth = depth;
+  t->info.levels = levels;
+  t->info.kernel_ms = ms;
+  t->info.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  return MT_OK;
+}
+
+// checked before any device call, in the order of the header
+int check_octree_build_args(int device, int n_tris, const double *tri_vertex) {
+  if (n_tris < 0) return fail(MT_ERR_ARG, "%d triangles", n_tris);
+  if (n_tris > 0 && !tri_vertex) return fail(MT_ERR_ARG, "the triangle vertex array is NULL");
+  const int n_dev = mt_device_count();
+  if (n_dev < 0) return n_dev;
+  if (device < 0 || device >= n_dev) return fail(MT_ERR_ARG, "device %d outside 0..%d", device, n_dev - 1);
+  return MT_OK;
+}
+
+// out's counts, and the arrays it asks for, from device arrays of one tree
+int octree_read_arrays(int32_t n_nodes, int32_t n_tris, int32_t depth, const double *d_aabb, const double *d_center,
+                       const int32_t *d_first_child, const int32_t *d_prim_begin, const int32_t *d_prim_count,
+                       const int32_t *d_tri_id, const double *d_tri_aabb, mt_octree_arrays *out) {
+  out->n_nodes = n_nodes;
+  out->n_tris = n_tris;
+  out->depth = depth;
+  const size_t nn = (size_t)n_nodes, nt = (size_t)n_tris;
+  if (out->node_aabb) HIP_TRY(hipMemcpy(out->node_aabb, d_aabb, nn * 48, hipMemcpyDeviceToHost));
+  if (out->node_center) HIP_TRY(hipMemcpy(out->node_center, d_center, nn * 24, hipMemcpyDeviceToHost));
+  if (out->first_child) HIP_TRY(hipMemcpy(out->first_child, d_first_child, nn * 4, hipMemcpyDeviceToHost));
+  if (out->prim_begin) HIP_TRY(hipMemcpy(out->prim_begin, d_prim_begin, nn * 4, hipMemcpyDeviceToHost));
+  if (out->prim_count) HIP_TRY(hipMemcpy(out->prim_count, d_prim_count, nn * 4, hipMemcpyDeviceToHost));
+  if (nt && out->tri_id) HIP_TRY(hipMemcpy(out->tri_id, d_tri_id, nt * 4, hipMemcpyDeviceToHost));
+  if (nt && out->tri_aabb) HIP_TRY(hipMemcpy(out->tri_aabb, d_tri_aabb, nt * 48, hipMemcpyDeviceToHost));
+  return MT_OK;
+}
+
+}  // namespace
+
+void mt_octree_destroy(mt_octree *t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);  // (the buffers are freed with the tree)
+  if (t->ev0) (void)hipEventDestroy(t->ev0);
+  if (t->ev1) (void)hipEventDestroy(t->ev1);
+  delete t;
+}
+
+mt_octree *mt_octree_build(int device, int n_tris, const double *tri_vertex, mt_build_info *info) {
+  if (check_octree_build_args(device, n_tris, tri_vertex) != MT_OK) return nullptr;
+  mt_octree *t = new mt_octree();
+  t->device = device;
+  t->n_tris = n_tris;
+  const int rc = octree_build(t, tri_vertex);
+  if (rc != MT_OK) {
+    const std::string why = g_err;  // (the text survives the clean-up)
+    (void)hipGetLastError();
+    mt_octree_destroy(t);
+    (void)fail(rc, "%s", why.c_str());
+    return nullptr;
+  }
+  if (info) *info = t->info;
+  return t;
+}
+
+int mt_octree_info(const mt_octree *t, mt_build_info *out) {
+  if (!t) return fail(MT_ERR_ARG, "the octree is NULL");
+  if (!out) return fail(MT_ERR_ARG, "the mt_build_info is NULL");
+  *out = t->info;
+  return MT_OK;
+}
+
+int mt_octree_read(const mt_octree *t, mt_octree_arrays *out) {
+  if (!t) return fail(MT_ERR_ARG, "the octree is NULL");
+  if (!out) return fail(MT_ERR_ARG, "the mt_octree_arrays is NULL");
+  HIP_TRY(hipSetDevice(t->device));
+  return octree_read_arrays(t->n_nodes, t->n_tris, t->depth, t->d_aabb, t->d_center, t->d_first_child, t->d_prim_begin,
+                            t->d_prim_count, t->d_tri_id, t->d_tri_aabb, out);
+}
+
+mt_scene *mt_scene_create_triangles(const mt_triangle_desc *d, mt_build_info *info) {
+  if (!d) {
+    fail(MT_ERR_ARG, "desc is NULL");
+    return nullptr;
+  }
+  if (d->struct_size != sizeof(mt_triangle_desc) || d->abi_version != MT_ABI_VERSION) {
+    fail(MT_ERR_ARG, "mt_triangle_desc size/version mismatch (%u/%u, want %zu/%d)", d->struct_size, d->abi_version,
+         sizeof(mt_triangle_desc), MT_ABI_VERSION);
+    return nullptr;
+  }
+  if (d->n_tris < 0 || d->n_materials < 0 || d->n_textures < 0) {
+    fail(MT_ERR_ARG, "negative or empty counts");
+    return nullptr;
+  }
+  if (d->n_tris > 0 && (!d->tri_vertex || !d->tri_normal || !d->tri_uvw || !d->tri_material || !d->tri_line_no)) {
+    fail(MT_ERR_ARG, "triangle arrays missing");
+    return nullptr;
+  }
+  if ((d->n_materials > 0 && !d->materials) || (d->n_textures > 0 && !d->textures)) {
+    fail(MT_ERR_ARG, "material/texture arrays missing");
+    return nullptr;
+  }
+  mt_build_info built{};
+  mt_octree *t = mt_octree_build(d->device, d->n_tris, d->tri_vertex, &built);
+  if (!t) return nullptr;
+  // the tree on the host, and the triangles gathered into its stream order
+  const size_t nn = (size_t)t->n_nodes, nt = (size_t)d->n_tris;
+  std::vector<double> node_aabb(nn * 6), node_center(nn * 3), box_add(nt * 6);
+  std::vector<int32_t> first_child(nn), prim_begin(nn), prim_count(nn), tri_id(nt ? nt : 1);  // (never NULL: the scene has a tri_id)
+  mt_octree_arrays a{};
+  a.node_aabb = node_aabb.data();
+  a.node_center = node_center.data();
+  a.first_child = first_child.data();
+  a.prim_begin = prim_begin.data();
+  a.prim_count = prim_count.data();
+  a.tri_id = tri_id.data();
+  a.tri_aabb = box_add.data();
+  const int rc = mt_octree_read(t, &a);
+  mt_octree_destroy(t);
+  if (rc != MT_OK) return nullptr;
+  std::vector<double> vertex(nt * 9), normal(nt * 9), uvw(nt * 9), box(nt * 6);
+  std::vector<int32_t> material(nt), line_no(nt);
+  for (size_t s = 0; s < nt; s++) {
+    const size_t i = (size_t)tri_id[s];
+    memcpy(&vertex[s * 9], d->tri_vertex + i * 9, 72);
+    memcpy(&normal[s * 9], d->tri_normal + i * 9, 72);
+    memcpy(&uvw[s * 9], d->tri_uvw + i * 9, 72);
+    memcpy(&box[s * 6], &box_add[i * 6], 48);
+    material[s] = d->tri_material[i];
+    line_no[s] = d->tri_line_no[i];
+  }
+  mt_scene_desc sd;
+  memset(&sd, 0, sizeof sd);
+  sd.struct_size = sizeof sd;
+  sd.abi_version = MT_ABI_VERSION;
+  sd.device = d->device;
+  sd.n_nodes = a.n_nodes;
+  sd.n_tris = d->n_tris;
+  sd.n_materials = d->n_materials;
+  sd.n_textures = d->n_textures;
+  sd.tree_depth = a.depth;
+  sd.node_aabb = node_aabb.data();
+  sd.node_center = node_center.data();
+  sd.node_first_child = first_child.data();
+  sd.node_prim_begin = prim_begin.data();
+  sd.node_prim_count = prim_count.data();
+  sd.tri_vertex = vertex.data();
+  sd.tri_normal = normal.data();
+  sd.tri_uvw = uvw.data();
+  sd.tri_aabb = box.data();
+  sd.tri_material = material.data();
+  sd.tri_line_no = line_no.data();
+  sd.tri_id = tri_id.data();
+  sd.materials = d->materials;
+  sd.textures = d->textures;
+  mt_scene *s = mt_scene_create(&sd);
+  if (s && info) *info = built;
+  return s;
+}
+
+int mt_scene_read_tree(const mt_scene *s, mt_octree_arrays *out) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (!out) return fail(MT_ERR_ARG, "the mt_octree_arrays is NULL");
+  if (!s->have_tri_id) return fail(MT_ERR_ARG, "the scene was made without tri_id");
+  const size_t nn = (size_t)s->dev.n_nodes, nt = (size_t)s->dev.n_tris;
+  out->n_nodes = s->dev.n_nodes;
+  out->n_tris = s->dev.n_tris;
+  out->depth = s->dev.tree_depth;
+  HIP_TRY(hipSetDevice(s->device));
+  std::vector<NodeRec> recs(nn);
+  HIP_TRY(hipMemcpy(recs.data(), s->dev.nodes, nn * sizeof(NodeRec), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < nn; i++) {
+    const NodeRec &r = recs[i];
+    for (int k = 0; k < 3; k++) {
+      if (out->node_aabb) {
+        out->node_aabb[i * 6 + k] = r.lo[k];
+        out->node_aabb[i * 6 + 3 + k] = r.hi[k];
+      }
+      if (out->node_center) out->node_center[i * 3 + k] = r.c[k];
+    }
+    if (out->first_child) out->first_child[i] = r.first_child;
+    if (out->prim_begin) out->prim_begin[i] = r.prim_begin;
+    if (out->prim_count) out->prim_count[i] = r.prim_count;
+  }
+  if (nt && out->tri_id) memcpy(out->tri_id, s->tri_id_host.data(), nt * sizeof(int32_t));
+  if (nt && out->tri_aabb) {  // (the scene holds the boxes in stream order)
+    std::vector<double> box(nt * 6);
+    HIP_TRY(hipMemcpy(box.data(), s->dev.tri_aabb, nt * 48, hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < nt; p++) memcpy(out->tri_aabb + (size_t)s->tri_id_host[p] * 6, &box[p * 6], 48);
   }
   return MT_OK;
 }

@@ -88,7 +88,7 @@ struct LightBuffer {
 // TraceRayWorker for every pixel, traced once by BuildRayTree and kept on the GPU, from which ShadeRayTree makes the
 // full-depth frame under edited light colours without tracing a ray.  Move-only; destroys its mt_raytree.  It belongs
 // to the MythTracer that built it and must be destroyed (or Reset) before that MythTracer, and before anything that
-// uploads the scene again (LoadObj, SetDevices).
+// uploads the scene again (LoadObj, SetDevices, UpdateGeometry).
 class RayTree {
  public:
   RayTree() = default;
@@ -238,6 +238,24 @@ class MythTracer {
   // are not covered: a moved vertex needs a new upload.  Before the first upload it is Prepare.  RayTrees built before
   // the edit are stale until UpdateRayTreeMaterials / RegrowRayTree, which need a tree that keeps triangles for it.
   bool UpdateTriangleAttributes();
+  // The octree of the next Prepare is built on the GPU (OctTree::SetDeviceBuild, mt_octree_build on the facade's first
+  // device) instead of by OctTree::Finalize on the host: the same tree, bit for bit, so everything downstream -- the
+  // upload, the edit calls' stream order, IntersectRays -- runs as it does with the host builder.  Off by default.  With
+  // the switch on, no GPU or a failed build makes Prepare return false with the reason in LastError(): the host builder
+  // is never used instead.
+  void SetDeviceTreeBuild(bool on) { scene.tree.SetDeviceBuild(on); }
+  // MOVING geometry: the three vertices of each of the triangles `add_indices` (LoadObj / AddPrimitive order) replaced
+  // by vertices[3 k .. 3 k + 2], and the triangle's box cached again (Triangle::CacheAABB).  Only the host scene
+  // changes; refused with a message, and no triangle changed, for an index outside the scene's triangles or another
+  // number of vertices than three per index.  UpdateGeometry() must follow before the scene is used again.
+  bool SetTriangleVertices(const std::vector<int>& add_indices, const std::vector<V3D>& vertices);
+  // After SetTriangleVertices (or any edit of MutableTriangle(i)->vertex followed by its CacheAABB): the root box is
+  // recomputed from {0,0,0}-{0,0,0} over all triangles -- it can shrink --, the tree is marked unfinalized and the device
+  // scenes are dropped, so the next Prepare (every rendering call makes one) builds the tree again, with either
+  // builder, and uploads.  RayTree objects follow SetDevices's rule: a RayTree built before the call belongs to a device
+  // scene that no longer exists and must have been destroyed or Reset BEFORE the call (see RayTree); there is no way
+  // to bring such a tree to the moved geometry, and none to ask it whether it is fresh: build a new one.
+  void UpdateGeometry();
   // RayTrees built from now on also keep the triangle each ray hit (mt_scene_set_raytree_tri): 4 bytes more per ray,
   // and UpdateRayTreeMaterials / RegrowRayTree then take an UpdateTriangleMaterials, which they refuse for a tree
   // without.  Off by default; independent of SetRayTreeKeepUVW (a reassignment TO a textured material needs both).

@@ -46,6 +46,16 @@ class OctTree {
   // Builds the tree.  Prints "Triangles: N" like the reference.
   void Finalize();
   bool IsFinalized() const { return finalized_; }
+  // extension: Finalize() builds the tree on the GPU (mt_octree_build on the device of SetDevice) instead of on the
+  // host: the same FlatTree, bit for bit.  Off by default.  When it is on and the build fails -- no GPU, no memory, a
+  // tree deeper than MT_MAX_TREE_DEPTH -- Finalize() leaves the tree unfinalized with the reason in LastError(): it
+  // never falls back to the host builder.
+  void SetDeviceBuild(bool on) { device_build_ = on; }
+  bool DeviceBuild() const { return device_build_; }
+  // extension, after triangles were MOVED (MutableTriangle(i)->vertex, then its CacheAABB): the root box again from
+  // {0,0,0}-{0,0,0} over all triangles in add order -- it can shrink --, and the tree is unfinalized: the next
+  // Finalize() builds it again.  The standalone IntersectRay's upload is dropped.
+  void Refit();
   // extension: no "Triangles: N" line on stdout
   void SetQuiet(bool quiet) { quiet_ = quiet; }
   // extension: HIP device of the standalone IntersectRay(s) (MythTracer::SetDevice forwards to it)
@@ -68,7 +78,8 @@ class OctTree {
   size_t PrimitiveCount() const { return prims_.size(); }
   const Triangle* GetTriangle(size_t add_index) const;
   // the same triangle, for a caller that gives it another material (Triangle::mtl; MythTracer::UpdateTriangleMaterials).
-  // Vertices, normals and boxes are the finalized tree's: they are not to be changed through it.
+  // Vertices and boxes are the finalized tree's: a caller that changes them calls Refit() before the tree is used again
+  // (MythTracer::SetTriangleVertices / UpdateGeometry do).
   Triangle* MutableTriangle(size_t add_index);
   const char* LastError() const { return error_.c_str(); }
   static const int SPLIT_BOUNDARY = 16;  // octtree.h:43
@@ -79,6 +90,8 @@ class OctTree {
   FlatTree flat_;
   bool finalized_ = false;
   bool quiet_ = false;
+  bool device_build_ = false;
+  bool FinalizeOnDevice();
   int device_ = 0;
   mutable mt_scene* geometry_only_ = nullptr;  // for standalone IntersectRay
   mutable std::string error_;

@@ -657,6 +657,27 @@ int mth_set_triangle_attr(void* p, int which, const int32_t* add_indices, int n,
 // MythTracer::UpdateTriangleAttributes; 0 with the facade's message when it refuses
 int mth_update_triangle_attributes(void* p) { return static_cast<Handle*>(p)->mt.UpdateTriangleAttributes() ? 1 : 0; }
 
+// MythTracer::SetDeviceTreeBuild
+void mth_set_device_tree_build(void* p, int on) { static_cast<Handle*>(p)->mt.SetDeviceTreeBuild(on != 0); }
+
+// MythTracer::SetTriangleVertices: vertices[n][9] for the triangles add_indices[n]; 0 with the facade's message (or the
+// shim's for a bad list) when it refuses: no triangle is changed then
+int mth_set_triangle_vertices(void* p, const int32_t* add_indices, int n, const double* vertices) {
+  Handle* h = static_cast<Handle*>(p);
+  if (n < 0 || (n > 0 && (add_indices == nullptr || vertices == nullptr))) {
+    h->shim_error = "bad triangle vertex list";
+    return 0;
+  }
+  std::vector<int> idx(add_indices, add_indices + n);
+  std::vector<raytracer::V3D> v((size_t)n * 3);
+  for (size_t k = 0; k < v.size(); k++) v[k] = {vertices[k * 3], vertices[k * 3 + 1], vertices[k * 3 + 2]};
+  h->shim_error.clear();
+  return h->mt.SetTriangleVertices(idx, v) ? 1 : 0;
+}
+
+// MythTracer::UpdateGeometry
+void mth_update_geometry(void* p) { static_cast<Handle*>(p)->mt.UpdateGeometry(); }
+
 // MythTracer::SetRayTreeKeepTriangles
 void mth_set_raytree_keep_triangles(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepTriangles(keep != 0); }
 

@@ -183,8 +183,12 @@ bool MythTracer::Prepare() {
   if (!was_scene_finalized) {
     if (!quiet_) puts("Finalizing tree.");
     scene.tree.Finalize();
+    DropDeviceScenes();  // geometry changed (LoadObj after a render, UpdateGeometry): upload again
+    if (!scene.tree.IsFinalized()) {  // (SetDeviceTreeBuild: the build on the GPU failed, and the host builder is not asked instead)
+      error_ = scene.tree.LastError();
+      return false;
+    }
     was_scene_finalized = true;
-    DropDeviceScenes();  // geometry changed (LoadObj after a render): upload again
   }
   if (dev_) return true;
   FlatScene flat;
@@ -223,6 +227,36 @@ bool MythTracer::Prepare() {
   uploaded_textures_ = flat.texture_of;
   uploaded_materials_ = flat.material_of;
   return true;
+}
+
+bool MythTracer::SetTriangleVertices(const std::vector<int>& add_indices, const std::vector<V3D>& vertices) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (vertices.size() != add_indices.size() * 3) {
+    return refuse(std::to_string(add_indices.size()) + " triangles need " + std::to_string(add_indices.size() * 3) +
+                  " vertices, not " + std::to_string(vertices.size()));
+  }
+  for (int i : add_indices) {
+    if (i < 0 || (size_t)i >= scene.tree.PrimitiveCount()) {
+      return refuse("triangle index " + std::to_string(i) + " outside the scene's " +
+                    std::to_string(scene.tree.PrimitiveCount()) + " triangles");
+    }
+  }
+  for (size_t k = 0; k < add_indices.size(); k++) {
+    Triangle* t = scene.tree.MutableTriangle((size_t)add_indices[k]);
+    for (int v = 0; v < 3; v++) t->vertex[v] = vertices[k * 3 + (size_t)v];
+    t->CacheAABB();
+  }
+  return true;
+}
+
+void MythTracer::UpdateGeometry() {
+  scene.tree.Refit();
+  was_scene_finalized = false;
+  DropDeviceScenes();
 }
 
 bool MythTracer::UpdateTriangleMaterials() {

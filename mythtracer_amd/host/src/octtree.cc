@@ -66,9 +66,65 @@ const int kBuilderDepthLimit = 4096;
 
 }  // namespace
 
+void OctTree::Refit() {
+  root_aabb_ = AABB();
+  for (const auto& p : prims_) root_aabb_.Extend(p->GetAABB());
+  finalized_ = false;
+  flat_ = FlatTree();
+  if (geometry_only_) mt_scene_destroy(geometry_only_);
+  geometry_only_ = nullptr;
+}
+
+// flat_ from mt_octree_build + mt_octree_read on device_; false with error_ set, and flat_ empty, when the build fails
+bool OctTree::FinalizeOnDevice() {
+  const size_t nt = prims_.size();
+  if (nt > 0x7fffffffu) {
+    error_ = "device tree build: more triangles than an int32 indexes";
+    return false;
+  }
+  std::vector<double> vtx(nt * 9);
+  for (size_t i = 0; i < nt; i++) memcpy(&vtx[i * 9], GetTriangle(i)->vertex, 72);
+  mt_build_info info;
+  mt_octree* t = mt_octree_build(device_, (int)nt, vtx.data(), &info);
+  if (t == nullptr) {
+    error_ = std::string("device tree build failed: ") + mt_last_error();
+    return false;
+  }
+  FlatTree f;
+  const size_t n = (size_t)info.n_nodes;
+  f.node_aabb.resize(n * 6);
+  f.node_center.resize(n * 3);
+  f.first_child.resize(n);
+  f.prim_begin.resize(n);
+  f.prim_count.resize(n);
+  f.tri_id.resize(nt);
+  mt_octree_arrays a;
+  memset(&a, 0, sizeof a);
+  a.node_aabb = f.node_aabb.data();
+  a.node_center = f.node_center.data();
+  a.first_child = f.first_child.data();
+  a.prim_begin = f.prim_begin.data();
+  a.prim_count = f.prim_count.data();
+  a.tri_id = f.tri_id.data();
+  const int rc = mt_octree_read(t, &a);
+  mt_octree_destroy(t);
+  if (rc != MT_OK) {
+    error_ = std::string("device tree build failed: ") + mt_last_error();
+    return false;
+  }
+  f.depth = a.depth;
+  flat_ = std::move(f);
+  return true;
+}
+
 void OctTree::Finalize() {
   if (finalized_) return;
   if (!quiet_) printf("Triangles: %u\n", (unsigned int)prims_.size());
+  if (device_build_) {  // never the host builder instead: a failed build leaves the tree unfinalized
+    if (FinalizeOnDevice()) finalized_ = true;
+    else fprintf(stderr, "error: %s\n", error_.c_str());
+    return;
+  }
 
   // Breadth-first construction.  A node's split depends only on its own box
   // and member list, so the result equals the reference's depth-first
