@@ -33,11 +33,11 @@ def device_scene(tris):
     return m
 
 
-def compare(m, rays, want, modes, exact_counters=(1, 2, 4, 7), what=""):
+def compare(m, rays, want, modes, exact_counters=(1, 2, 4, 7), what="", describe=None):
     """mt_intersect_rays in every mode of `modes` against the oracle's answers `want`, as
     test_random_triangle_soups_all_modes does: line everywhere, t and point bit for bit on hits and NaN on misses,
     mt_tests equal (>= in the automatic mode, which may look behind the reference's early exit), all four work counters
-    equal in the modes that skip no subtree."""
+    equal in the modes that skip no subtree.  describe(r), where given, names ray r in the message of a wrong line."""
     abi, h = M.hip_abi(), m.device_scene()
     hit = want["line"] >= 0
     for mode in modes:
@@ -47,7 +47,9 @@ def compare(m, rays, want, modes, exact_counters=(1, 2, 4, 7), what=""):
         print("%s mode %d: %d of %d lines differ; mt_tests %d (oracle %d)"
               % (what, mode, int((got["line"] != want["line"]).sum()), len(rays), got["stats"]["mt_tests"],
                  want["counters"]["mt_tests"]))
-        assert np.array_equal(got["line"], want["line"]), tag
+        wrong = np.nonzero(got["line"] != want["line"])[0]
+        assert len(wrong) == 0, (tag, "%d of %d lines wrong" % (len(wrong), len(rays)), "got line %d" % got["line"][wrong[0]],
+                                 describe(int(wrong[0])) if describe else "ray %d" % wrong[0])
         assert np.array_equal(got["t"][hit], want["t"][hit]), tag
         assert np.array_equal(got["point"][hit], want["point"][hit]), tag
         assert np.isnan(got["t"][~hit]).all() and np.isnan(got["point"][~hit]).all(), tag

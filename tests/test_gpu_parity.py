@@ -414,8 +414,10 @@ def _render_both(m, o, cam, W, H, lights):
     return g
 
 
-@pytest.mark.parametrize("ext,jit,depth,layout", [(0.08, 0.015, 10, 1), (0.04, 0.008, 11, 1), (0.01, 0.002, 13, 1), (0.01, 0.002, 13, 0),
+@pytest.mark.parametrize("ext,jit,depth,layout", [(0.08, 0.015, 10, 1), (0.04, 0.008, 11, 1), (0.02, 0.004, 12, 1), (0.02, 0.004, 12, 0),
+                                                   (0.01, 0.002, 13, 1), (0.01, 0.002, 13, 0),
                                                    (0.005, 0.001, 14, 1), (0.0012, 0.00025, 16, 1), (0.0012, 0.00025, 16, 0),
+                                                   (0.0006, 0.00012, 17, 1), (0.0006, 0.00012, 17, 0),
                                                    (0.0003, 0.00006, 18, 1), (0.0003, 0.00006, 18, 0), (0.00004, 0.000008, 21, 1),
                                                    (0.000005, 0.000001, 24, 1), (0.0000025, 0.0000005, 25, 1)])
 def test_deep_octrees(ext, jit, depth, layout):
