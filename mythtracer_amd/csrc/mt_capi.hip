@@ -32,6 +32,7 @@
 #include "mt_lightbuffer.h"
 #include "mt_raytree.h"
 #include "mt_build.h"
+#include "mt_layout.h"
 
 using namespace mt;
 
@@ -46,6 +47,8 @@ int fail(int code, const char *fmt, ...) {
   va_end(ap);
   return code;
 }
+
+int fail(const LayoutError &err) { return fail(err.code, "%s", err.msg.c_str()); }
 
 #define HIP_TRY(expr)                                                                   \
   do {                                                                                  \
@@ -342,13 +345,6 @@ template <typename... Params, typename... Args>
 hipError_t launch_flat(void (*kernel)(Params...), size_t n, hipStream_t stream, Args &&...args) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, static_cast<Params>(args)...);
   return hipGetLastError();
-}
-
-bool finite3(const double *p, size_t n) {
-  for (size_t i = 0; i < n; i++) {
-    if (!std::isfinite(p[i])) return false;
-  }
-  return true;
 }
 
 // tiles of tile_w x tile_h over an image of image_w x image_h
@@ -1214,393 +1210,44 @@ void mt_scene_destroy(mt_scene *s) {
 
 // a texture's size and format (mt_scene_create, mt_scene_set_texture)
 static int check_texture(const mt_texture &t, int i) {
-  if (t.width <= 0 || t.height <= 0 || t.width > 30000 || t.height > 30000 || !t.texels ||
-      (t.format != MT_TEX_RGB8 && t.format != MT_TEX_F64)) {
-    return fail(MT_ERR_ARG, "texture %d: bad size/format", i);
-  }
-  return MT_OK;
+  LayoutError err;
+  return mt::check_texture(t, i, &err) ? MT_OK : fail(err);
 }
 
-static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
-  if (d->struct_size != sizeof(mt_scene_desc) || d->abi_version != MT_ABI_VERSION) {
-    return fail(MT_ERR_ARG, "mt_scene_desc size/version mismatch (%u/%u, want %zu/%d)",
-                d->struct_size, d->abi_version, sizeof(mt_scene_desc), MT_ABI_VERSION);
-  }
-  if (d->n_nodes < 1 || d->n_tris < 0 || d->n_materials < 0 || d->n_textures < 0) {
-    return fail(MT_ERR_ARG, "negative or empty counts");
-  }
-  if (!d->node_aabb || !d->node_center || !d->node_first_child || !d->node_prim_begin ||
-      !d->node_prim_count) {
-    return fail(MT_ERR_ARG, "node arrays missing");
-  }
-  if (d->n_tris > 0 && (!d->tri_vertex || !d->tri_normal || !d->tri_uvw || !d->tri_aabb ||
-                        !d->tri_material || !d->tri_line_no)) {
-    return fail(MT_ERR_ARG, "triangle arrays missing");
-  }
-  if ((d->n_materials > 0 && !d->materials) || (d->n_textures > 0 && !d->textures)) {
-    return fail(MT_ERR_ARG, "material/texture arrays missing");
-  }
-  // --- structural validation: the kernel indexes all of this unchecked.
-  const int nn = d->n_nodes;
-  std::vector<int> depth_of((size_t)nn, 0);
-  depth_of[0] = 1;
-  int max_depth = 1;
-  long long prim_total = 0;
-  for (int i = 0; i < nn; i++) {
-    const int fc = d->node_first_child[i];
-    const int pb = d->node_prim_begin[i], pc = d->node_prim_count[i];
-    if (pb < 0 || pc < 0 || (long long)pb + pc > d->n_tris) {
-      return fail(MT_ERR_ARG, "node %d: primitive range [%d,+%d) outside 0..%d", i, pb, pc, d->n_tris);
-    }
-    prim_total += pc;
-    if (depth_of[i] == 0) return fail(MT_ERR_ARG, "node %d is not reachable in BFS order", i);
-    if (fc != 0) {
-      if (fc <= i || (long long)fc + 8 > nn) {
-        return fail(MT_ERR_ARG, "node %d: first_child %d invalid (n_nodes %d)", i, fc, nn);
-      }
-      for (int k = 0; k < 8; k++) {
-        if (depth_of[fc + k] != 0) return fail(MT_ERR_ARG, "node %d has two parents", fc + k);
-        depth_of[fc + k] = depth_of[i] + 1;
-      }
-      if (depth_of[i] + 1 > max_depth) max_depth = depth_of[i] + 1;
-    }
-  }
-  if (prim_total != d->n_tris) {
-    return fail(MT_ERR_ARG, "nodes reference %lld primitives, scene has %d", prim_total, d->n_tris);
-  }
-  if (max_depth > MT_MAX_TREE_DEPTH) {
-    return fail(MT_ERR_UNSUPPORTED, "octree depth %d exceeds MT_MAX_TREE_DEPTH %d", max_depth,
-                MT_MAX_TREE_DEPTH);
-  }
-  for (int i = 0; i < d->n_tris; i++) {
-    const int m = d->tri_material[i];
-    if (m < -1 || m >= d->n_materials) {
-      return fail(MT_ERR_ARG, "triangle %d: material index %d outside -1..%d", i, m, d->n_materials - 1);
-    }
-  }
-  for (int i = 0; i < d->n_materials; i++) {
-    const int t = d->materials[i].tex;
-    if (t < -1 || t >= d->n_textures) {
-      return fail(MT_ERR_ARG, "material %d: texture index %d outside -1..%d", i, t, d->n_textures - 1);
-    }
-  }
-  for (int i = 0; i < d->n_textures; i++) MT_TRY(check_texture(d->textures[i], i));
-  // --- is the min/max-instruction path admissible for this scene?
-  bool regular = finite3(d->node_aabb, (size_t)nn * 6) && finite3(d->node_center, (size_t)nn * 3) &&
-                 finite3(d->tri_aabb, (size_t)d->n_tris * 6);
-  for (int i = 0; regular && i < nn; i++) {
-    for (int k = 0; k < 3; k++) {
-      const double lo = d->node_aabb[i * 6 + k], hi = d->node_aabb[i * 6 + 3 + k];
-      const double c = d->node_center[i * 3 + k];
-      if (!(lo <= hi)) regular = false;
-      if (d->node_first_child[i] != 0 && !(lo <= c && c <= hi)) regular = false;
-    }
-  }
-  for (int i = 0; regular && i < d->n_tris; i++) {
-    for (int k = 0; k < 3; k++) {
-      if (!(d->tri_aabb[i * 6 + k] <= d->tri_aabb[i * 6 + 3 + k])) regular = false;
-    }
-  }
-
+// The derived arrays (mt_layout.h) and the caller's own reach the device; the host keeps what the edit calls mirror.
+static int upload_layout(mt_scene *s, const mt_scene_desc *d, const SceneLayout &L) {
   HIP_TRY(hipSetDevice(d->device));
   s->device = d->device;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, d->device));
   s->n_cu = prop.multiProcessorCount;
 
-  std::vector<NodeRec> recs((size_t)nn);
-  for (int i = 0; i < nn; i++) {
-    NodeRec &r = recs[i];
-    memset(&r, 0, sizeof r);
-    for (int k = 0; k < 3; k++) {
-      r.lo[k] = d->node_aabb[i * 6 + k];
-      r.hi[k] = d->node_aabb[i * 6 + 3 + k];
-      r.c[k] = d->node_center[i * 3 + k];
-    }
-    r.first_child = d->node_first_child[i];
-    r.prim_begin = d->node_prim_begin[i];
-    r.prim_count = d->node_prim_count[i];
-    r.level = depth_of[i] - 1;
-  }
-  // Block boxes (mt_device.h kGroupTris): union of the fp64 boxes of each
-  // block of kGroupTris consecutive stream triangles, then rounded to fp32
-  // exactly like the per-triangle copies (the filter's margin covers it).
-  std::vector<float> groups;
-  for (int t0 = 0; t0 < d->n_tris; t0 += kGroupTris) {
-    const int e = std::min(t0 + kGroupTris, d->n_tris);
-    double u[6];
-    for (int k = 0; k < 6; k++) u[k] = d->tri_aabb[(size_t)t0 * 6 + k];
-    for (int t = t0 + 1; t < e; t++) {
-      const double *b = d->tri_aabb + (size_t)t * 6;
-      for (int k = 0; k < 3; k++) {
-        u[k] = std::min(u[k], b[k]);
-        u[3 + k] = std::max(u[3 + k], b[3 + k]);
-      }
-    }
-    for (int k = 0; k < 6; k++) groups.push_back((float)u[k]);
-  }
-  // Subtree boxes (mt_trace.h tight_keep_mask): union of the fp64 boxes of all
-  // triangles stored in a node or below it, rounded to fp32 like the others.
-  // Breadth-first order: children have larger indices than their parent.  An
-  // empty subtree gets an inverted box, which every ray misses.
-  std::vector<float> subs((size_t)nn * 6 + 8 * 6, 0.0f);
-  {
-    std::vector<double> sb((size_t)nn * 6);
-    for (int i = nn - 1; i >= 0; i--) {
-      double *u = &sb[(size_t)i * 6];
-      for (int k = 0; k < 3; k++) {
-        u[k] = 3.0e38;
-        u[3 + k] = -3.0e38;
-      }
-      const NodeRec &r = recs[i];
-      for (int t = r.prim_begin; t < r.prim_begin + r.prim_count; t++) {
-        const double *b = d->tri_aabb + (size_t)t * 6;
-        for (int k = 0; k < 3; k++) {
-          u[k] = std::min(u[k], b[k]);
-          u[3 + k] = std::max(u[3 + k], b[3 + k]);
-        }
-      }
-      if (r.first_child != 0) {
-        for (int c = 0; c < 8; c++) {
-          const double *b = &sb[(size_t)(r.first_child + c) * 6];
-          for (int k = 0; k < 3; k++) {
-            u[k] = std::min(u[k], b[k]);
-            u[3 + k] = std::max(u[3 + k], b[3 + k]);
-          }
-        }
-      }
-      for (int k = 0; k < 6; k++) subs[(size_t)i * 6 + k] = (float)u[k];
-      if (r.first_child != 0) {
-        int mask = 0;
-        for (int c = 0; c < 8; c++) {
-          const double *b = &sb[(size_t)(r.first_child + c) * 6];
-          if (b[0] <= b[3]) mask |= 1 << c;  // an empty subtree keeps the inverted box
-        }
-        recs[i].child_mask = mask;
-      }
-    }
-  }
-  // Records of the hit-set traversal (mt_device.h HsRec).
-  static_assert(offsetof(HsRec, kid) == 16 && offsetof(HsRec, own) == kHsRecOwn && offsetof(HsRec, planes) == kHsRecPlanes &&
-                    offsetof(HsRec, sl_begin) == kHsRecSl && offsetof(HsRec, ll_begin) == kHsRecLl, "the walk reads the record at these offsets");
-  std::vector<HsRec> hsr((size_t)nn + 1);
-  memset(hsr.data(), 0, hsr.size() * sizeof(HsRec));
-  std::vector<float> sl_box;  // DevScene::sl_box32
-  for (int i = 0; i < nn; i++) {
-    HsRec &h = hsr[i];
-    const NodeRec &r = recs[i];
-    h.first_child = r.first_child;
-    h.prim_begin = r.prim_begin;
-    h.prim_count = r.prim_count;
-    h.child_mask = r.first_child != 0 ? (r.child_mask & 0xff) : 0;
-    for (int c = 0; c < 8; c++) {
-      for (int a = 0; a < 3; a++) {
-        const float lo = r.first_child != 0 ? subs[(size_t)(r.first_child + c) * 6 + a] : 3.0e38f;
-        const float hi = r.first_child != 0 ? subs[(size_t)(r.first_child + c) * 6 + 3 + a] : -3.0e38f;
-        h.kid[a][c] = lo;
-        h.kid[a][8 + c] = hi;
-        h.kid[a][16 + c] = lo;
-      }
-    }
-    double u[6] = {3.0e38, 3.0e38, 3.0e38, -3.0e38, -3.0e38, -3.0e38};
-    for (int t = r.prim_begin; t < r.prim_begin + r.prim_count; t++) {
-      const double *b = d->tri_aabb + (size_t)t * 6;
-      for (int k = 0; k < 3; k++) {
-        u[k] = std::min(u[k], b[k]);
-        u[3 + k] = std::max(u[3 + k], b[3 + k]);
-      }
-    }
-    for (int a = 0; a < 3; a++) {
-      h.own[a][0] = h.own[a][2] = (float)u[a];
-      h.own[a][1] = (float)u[3 + a];
-    }
-    h.sl_begin = -1;
-    if (r.prim_count >= 1 && r.prim_count <= kHsShortList) {
-      h.sl_begin = (int32_t)(sl_box.size() / kSlQuadFloats);
-      for (int q = 0; q < r.prim_count; q += 4) {
-        float quad[kSlQuadFloats];
-        for (int j = 0; j < 4; j++) {
-          for (int a = 0; a < 3; a++) {
-            const bool real = q + j < r.prim_count;
-            const float lo = real ? (float)d->tri_aabb[(size_t)(r.prim_begin + q + j) * 6 + a] : 3.0e38f;
-            const float hi = real ? (float)d->tri_aabb[(size_t)(r.prim_begin + q + j) * 6 + 3 + a] : -3.0e38f;
-            quad[a * 12 + j] = lo;
-            quad[a * 12 + 4 + j] = hi;
-            quad[a * 12 + 8 + j] = lo;
-          }
-        }
-        sl_box.insert(sl_box.end(), quad, quad + kSlQuadFloats);
-      }
-    }
-    for (int k = 0; k < 3; k++) {
-      h.planes[k] = r.lo[k];
-      h.planes[3 + k] = r.c[k];
-      h.planes[6 + k] = r.hi[k];
-    }
-  }
-  // Spatially sorted copies of the long lists (DevScene::ll_*): a median-split tree over the boxes' centres, cut on
-  // the longest axis of the centres' extent at a multiple of 64 (16 below 64) entries, so that 16 consecutive entries
-  // -- one block box -- and 64 -- one super box -- are spatial neighbours.  Every list is padded to a multiple of kLlPad.
-  std::vector<int32_t> ll_tri;
-  std::vector<float> ll_box, ll_grp, ll_sup;
-  std::vector<double> ll_exact;
-  {
-    const float inv[6] = {3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
-    std::vector<int32_t> order, work;
-    for (int i = 0; i < nn; i++) {
-      HsRec &h = hsr[i];
-      h.ll_begin = -1;
-      const int pb = recs[i].prim_begin, pc = recs[i].prim_count;
-      if (pc <= kHsShortList) continue;
-      order.resize((size_t)pc);
-      for (int k = 0; k < pc; k++) order[(size_t)k] = pb + k;
-      // iterative median split over [lo, hi) of `order`
-      std::vector<std::pair<int, int>> todo{{0, pc}};
-      while (!todo.empty()) {
-        const int lo = todo.back().first, hi = todo.back().second;
-        todo.pop_back();
-        const int n = hi - lo;
-        if (n <= 16) continue;
-        double cmin[3] = {1e300, 1e300, 1e300}, cmax[3] = {-1e300, -1e300, -1e300};
-        for (int k = lo; k < hi; k++) {
-          const double *b = d->tri_aabb + (size_t)order[(size_t)k] * 6;
-          for (int a = 0; a < 3; a++) {
-            const double c = b[a] * 0.5 + b[3 + a] * 0.5;
-            cmin[a] = std::min(cmin[a], c);
-            cmax[a] = std::max(cmax[a], c);
-          }
-        }
-        int ax = 0;
-        for (int a = 1; a < 3; a++) {
-          if (cmax[a] - cmin[a] > cmax[ax] - cmin[ax]) ax = a;
-        }
-        const int unit = n > 64 ? 64 : 16;
-        int left = ((n / 2 + unit - 1) / unit) * unit;
-        if (left >= n) left = n - (n % unit ? n % unit : unit);
-        if (left <= 0 || left >= n) continue;
-        auto key = [&](int32_t t) {
-          const double *b = d->tri_aabb + (size_t)t * 6;
-          return b[ax] * 0.5 + b[3 + ax] * 0.5;
-        };
-        std::nth_element(order.begin() + lo, order.begin() + lo + left, order.begin() + hi,
-                         [&](int32_t x, int32_t y) { const double kx = key(x), ky = key(y); return kx < ky || (kx == ky && x < y); });
-        todo.push_back({lo, lo + left});
-        todo.push_back({lo + left, hi});
-      }
-      h.ll_begin = (int32_t)ll_tri.size();
-      const int padded = ((pc + kLlPad - 1) / kLlPad) * kLlPad;
-      for (int k = 0; k < padded; k++) {
-        if (k < pc) {
-          const int32_t t = order[(size_t)k];
-          ll_tri.push_back(t);
-          for (int q = 0; q < 6; q++) ll_box.push_back((float)d->tri_aabb[(size_t)t * 6 + q]);
-          for (int q = 0; q < 6; q++) ll_exact.push_back(d->tri_aabb[(size_t)t * 6 + q]);
-          for (int q = 0; q < 9; q++) ll_exact.push_back(d->tri_vertex[(size_t)t * 9 + q]);
-        } else {
-          ll_tri.push_back(-1);
-          for (int q = 0; q < 6; q++) ll_box.push_back(inv[q]);
-          for (int q = 0; q < 15; q++) ll_exact.push_back(0.0);
-        }
-      }
-    }
-    auto unions = [&](const std::vector<float> &src, size_t per, std::vector<float> *dst) {
-      const size_t n = src.size() / 6;
-      for (size_t b = 0; b < n; b += per) {
-        float u[6] = {inv[0], inv[1], inv[2], inv[3], inv[4], inv[5]};
-        for (size_t j = b; j < std::min(b + per, n); j++) {
-          if (!(src[j * 6] <= src[j * 6 + 3])) continue;  // padding (inverted)
-          for (int q = 0; q < 3; q++) {
-            u[q] = std::min(u[q], src[j * 6 + q]);
-            u[3 + q] = std::max(u[3 + q], src[j * 6 + 3 + q]);
-          }
-        }
-        for (int q = 0; q < 6; q++) dst->push_back(u[q]);
-      }
-    };
-    unions(ll_box, 16, &ll_grp);
-    unions(ll_grp, 4, &ll_sup);
-    ll_tri.resize(ll_tri.size() + 64, -1);  // (never empty)
-    ll_exact.resize(ll_exact.size() + 15, 0.0);
-  }
-  // Second level (mt_device.h kSuperBlocks): one fp32 union box per 8 consecutive blocks, for the long lists.
-  std::vector<float> supers;
-  {
-    const size_t nblk = groups.size() / 6;
-    for (size_t b = 0; b < nblk; b += kSuperBlocks) {
-      float u[6];
-      for (int k = 0; k < 6; k++) u[k] = groups[b * 6 + k];
-      for (size_t j = b + 1; j < std::min(b + (size_t)kSuperBlocks, nblk); j++) {
-        for (int k = 0; k < 3; k++) {
-          u[k] = std::min(u[k], groups[j * 6 + k]);
-          u[3 + k] = std::max(u[3 + k], groups[j * 6 + 3 + k]);
-        }
-      }
-      for (int k = 0; k < 6; k++) supers.push_back(u[k]);
-    }
-    supers.resize(supers.size() + 8 * 6, 0.0f);  // look-ahead padding
-  }
-  groups.resize(groups.size() + 8 * 6, 0.0f);  // the scan looks four boxes ahead
-  int rc;
-  if ((rc = upload(s, groups.data(), groups.size(), &s->dev.grp_aabb32)) != MT_OK) return rc;
-  if ((rc = upload(s, supers.data(), supers.size(), &s->dev.sup_aabb32)) != MT_OK) return rc;
-  if ((rc = upload(s, subs.data(), subs.size(), &s->dev.sub_aabb32)) != MT_OK) return rc;
-  if ((rc = upload(s, hsr.data(), hsr.size(), &s->dev.hs_rec)) != MT_OK) return rc;
-  if ((rc = upload(s, ll_tri.data(), ll_tri.size(), &s->dev.ll_tri)) != MT_OK) return rc;
-  if ((rc = upload(s, ll_exact.data(), ll_exact.size(), &s->dev.ll_exact)) != MT_OK) return rc;
-  {  // the three levels once more as quads for the walk's per-lane reads (DevScene::ll_*_q; layout of sl_box32)
-    auto quads = [&](const std::vector<float> &src, size_t n_boxes) {
-      std::vector<float> q(((n_boxes + 3) / 4 + 1) * (size_t)kSlQuadFloats, 0.0f);
-      for (size_t i = 0; i < ((n_boxes + 3) / 4) * 4; i++) {
-        for (int a = 0; a < 3; a++) {
-          const float lo = i < n_boxes ? src[i * 6 + a] : 3.0e38f, hi = i < n_boxes ? src[i * 6 + 3 + a] : -3.0e38f;
-          float *d4 = &q[(i / 4) * kSlQuadFloats + (size_t)a * 12 + (i & 3)];
-          d4[0] = lo;
-          d4[4] = hi;
-          d4[8] = lo;
-        }
-      }
-      return q;
-    };
-    const size_t n_entries = ll_tri.size() - 64;
-    const std::vector<float> qb = quads(ll_box, n_entries), qg = quads(ll_grp, n_entries / 16), qs = quads(ll_sup, n_entries / 64);
-    if ((rc = upload(s, qb.data(), qb.size(), &s->dev.ll_box_q)) != MT_OK) return rc;
-    if ((rc = upload(s, qg.data(), qg.size(), &s->dev.ll_grp_q)) != MT_OK) return rc;
-    if ((rc = upload(s, qs.data(), qs.size(), &s->dev.ll_sup_q)) != MT_OK) return rc;
-  }
-  sl_box.resize(sl_box.size() + 2 * kSlQuadFloats, 0.0f);  // (the copies are whole 16-byte pieces; never empty)
-  if ((rc = upload(s, sl_box.data(), sl_box.size(), &s->dev.sl_box32)) != MT_OK) return rc;
-  if ((rc = upload(s, recs.data(), recs.size(), &s->dev.nodes)) != MT_OK) return rc;
+  MT_TRY(upload(s, L.groups.data(), L.groups.size(), &s->dev.grp_aabb32));
+  MT_TRY(upload(s, L.supers.data(), L.supers.size(), &s->dev.sup_aabb32));
+  MT_TRY(upload(s, L.subs.data(), L.subs.size(), &s->dev.sub_aabb32));
+  MT_TRY(upload(s, L.hsr.data(), L.hsr.size(), &s->dev.hs_rec));
+  MT_TRY(upload(s, L.ll_tri.data(), L.ll_tri.size(), &s->dev.ll_tri));
+  MT_TRY(upload(s, L.ll_exact.data(), L.ll_exact.size(), &s->dev.ll_exact));
+  MT_TRY(upload(s, L.ll_box_q.data(), L.ll_box_q.size(), &s->dev.ll_box_q));
+  MT_TRY(upload(s, L.ll_grp_q.data(), L.ll_grp_q.size(), &s->dev.ll_grp_q));
+  MT_TRY(upload(s, L.ll_sup_q.data(), L.ll_sup_q.size(), &s->dev.ll_sup_q));
+  MT_TRY(upload(s, L.sl_box.data(), L.sl_box.size(), &s->dev.sl_box32));
+  MT_TRY(upload(s, L.recs.data(), L.recs.size(), &s->dev.nodes));
+  MT_TRY(upload(s, L.tri_aabb.data(), L.tri_aabb.size(), &s->dev.tri_aabb));
+  MT_TRY(upload(s, L.tri_aabb32.data(), L.tri_aabb32.size(), &s->dev.tri_aabb32));
+  for (int k = 0; k < 3; k++) s->dev.bmax[k] = L.bmax[k];
   const size_t nt = (size_t)d->n_tris;
-  {
-    // The scan loop looks two boxes ahead (mt_trace.h): pad the stream.
-    std::vector<double> boxes(nt * 6 + 4 * 6, 0.0);
-    if (nt) memcpy(boxes.data(), d->tri_aabb, nt * 6 * sizeof(double));
-    if ((rc = upload(s, boxes.data(), boxes.size(), &s->dev.tri_aabb)) != MT_OK) return rc;
-    // fp32 copy for the conservative pre-filter (mt_trace.h Filter32); padded by
-    // 8 boxes because that loop looks four boxes ahead.
-    std::vector<float> boxes32(nt * 6 + 64 * 6, 0.0f);  // (padding: the look-ahead of the scans; the hit-set traversal copies whole 16-byte pieces)
-    double bmax[3] = {0.0, 0.0, 0.0};
-    for (size_t i = 0; i < nt * 6; i++) {
-      boxes32[i] = (float)boxes[i];
-      const double a = std::fabs(boxes[i]);
-      if (a > bmax[i % 3]) bmax[i % 3] = a;
-    }
-    if ((rc = upload(s, boxes32.data(), boxes32.size(), &s->dev.tri_aabb32)) != MT_OK) return rc;
-    // Never below 2^-7: make_filter32's check M = (bmax + |o|) |1/d| <= 2^120 then bounds |1/d| by 2^127 as well, the
-    // range in which its fp32 copy is finite (mt_trace.h, Filter32's preconditions).
-    for (int k = 0; k < 3; k++) s->dev.bmax[k] = std::max(bmax[k], 0x1p-7);
-  }
-  if ((rc = upload(s, d->tri_vertex, nt * 9, &s->dev.tri_vertex)) != MT_OK) return rc;
-  if ((rc = upload(s, d->tri_normal, nt * 9, &s->dev.tri_normal)) != MT_OK) return rc;
-  if ((rc = upload(s, d->tri_uvw, nt * 9, &s->dev.tri_uvw)) != MT_OK) return rc;
-  if ((rc = upload(s, d->tri_material, nt, &s->dev.tri_mtl)) != MT_OK) return rc;
+  MT_TRY(upload(s, d->tri_vertex, nt * 9, &s->dev.tri_vertex));
+  MT_TRY(upload(s, d->tri_normal, nt * 9, &s->dev.tri_normal));
+  MT_TRY(upload(s, d->tri_uvw, nt * 9, &s->dev.tri_uvw));
+  MT_TRY(upload(s, d->tri_material, nt, &s->dev.tri_mtl));
   s->tri_mtl_host = std::make_shared<const std::vector<int32_t>>(d->tri_material, d->tri_material + nt);
-  if ((rc = upload(s, d->tri_line_no, nt, &s->dev.tri_line)) != MT_OK) return rc;
+  MT_TRY(upload(s, d->tri_line_no, nt, &s->dev.tri_line));
   if (d->tri_id != nullptr) {  // (mt_render_gbuffer's `prim` plane; not part of DevScene)
     s->tri_id_host.assign(d->tri_id, d->tri_id + nt);
     s->have_tri_id = true;
   }
-  if ((rc = upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls)) != MT_OK) return rc;
+  MT_TRY(upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls));
   s->n_materials = d->n_materials;
   s->n_textures = d->n_textures;
   if (d->n_materials > 0) s->mtls_host.assign(d->materials, d->materials + d->n_materials);
@@ -1609,23 +1256,25 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
     const mt_texture &t = d->textures[i];
     const size_t texel_bytes = (t.format == MT_TEX_RGB8 ? 3 : 24);
     const uint8_t *dev_texels = nullptr;
-    if ((rc = upload(s, (const uint8_t *)t.texels, (size_t)t.width * t.height * texel_bytes,
-                     &dev_texels)) != MT_OK) {
-      return rc;
-    }
+    MT_TRY(upload(s, (const uint8_t *)t.texels, (size_t)t.width * t.height * texel_bytes, &dev_texels));
     texs[i] = DevTexture{dev_texels, t.width, t.height, t.format, 0};
   }
-  if ((rc = upload(s, texs.data(), texs.size(), &s->dev.texs)) != MT_OK) return rc;
+  MT_TRY(upload(s, texs.data(), texs.size(), &s->dev.texs));
   s->texs_host = texs;
   s->tex_generation.assign(texs.size(), 0ull);
   s->dev.n_tris = d->n_tris;
-  s->dev.n_nodes = nn;
-  s->dev.tree_depth = max_depth;
+  s->dev.n_nodes = d->n_nodes;
+  s->dev.tree_depth = L.max_depth;
   s->dev.force_mode = 0;
-  s->dev.scene_regular = regular ? 1 : 0;
-  s->dev.pack_shift = pack_shift_for(d->n_tris, nn);  // (MT_TUNE_PACKED_STACK = 0 switches it off)
+  s->dev.scene_regular = L.regular ? 1 : 0;
+  s->dev.pack_shift = pack_shift_for(d->n_tris, d->n_nodes);  // (MT_TUNE_PACKED_STACK = 0 switches it off)
   s->dev.n_lights = 0;
   s->dev.lights = nullptr;
+  return MT_OK;
+}
+
+// What every launch of the scene needs besides the scene: counters, work words, queues, events, the device's DevScene.
+static int init_launch_state(mt_scene *s) {
   MT_TRY(s->d_counters.ensure(ST_COUNT * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(s->d_counters, 0, ST_COUNT * sizeof(unsigned long long)));
   MT_TRY(s->d_work.ensure((kLeanCtl + 8) * sizeof(unsigned)));  // 16 words of counters, 8 of the lean frame kernel's
@@ -1636,7 +1285,7 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
   MT_TRY(s->d_order_whist.ensure((size_t)kOrdGroupsMax * kOrdKeysMax * sizeof(unsigned)));
   HIP_TRY(hipEventCreate(&s->ev0));
   HIP_TRY(hipEventCreate(&s->ev1));
-  if ((rc = mt_scene_set_lights(s, nullptr, 0)) != MT_OK) return rc;
+  MT_TRY(mt_scene_set_lights(s, nullptr, 0));
   s->dev.hb = nullptr;
   s->dev.prof = nullptr;
   MT_TRY(s->d_dev.ensure(sizeof(DevScene)));
@@ -1663,6 +1312,18 @@ static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
     s->dev.hb = (volatile unsigned long long *)dp;
   }
   return configure_launch(s);
+}
+
+// A bad desc is refused before any HIP call (mt_layout.h: the checks and every derived array).
+static int scene_create_impl(mt_scene *s, const mt_scene_desc *d) {
+  std::vector<int> depth_of;
+  int max_depth = 0;
+  LayoutError err;
+  if (!check_scene_desc(*d, &depth_of, &max_depth, &err)) return fail(err);
+  SceneLayout L;
+  derive_layout(*d, depth_of, &L);
+  MT_TRY(upload_layout(s, d, L));
+  return init_launch_state(s);
 }
 
 mt_scene *mt_scene_create(const mt_scene_desc *d) {

@@ -2,6 +2,7 @@
 // side of libmythtracer_hip.so.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "mythtracer_hip.h"
 
@@ -69,7 +70,9 @@ struct HsRec {
   int32_t pad1[2];
 };
 static_assert(sizeof(HsRec) == 432, "HsRec must be 432 bytes");
-constexpr int kHsRecOwn = 304, kHsRecSl = 340, kHsRecLl = 344, kHsRecPlanes = 352;  // byte offsets the walk reads at (checked in mt_capi.hip)
+constexpr int kHsRecOwn = 304, kHsRecSl = 340, kHsRecLl = 344, kHsRecPlanes = 352;  // byte offsets the walk reads at
+static_assert(offsetof(HsRec, kid) == 16 && offsetof(HsRec, own) == kHsRecOwn && offsetof(HsRec, planes) == kHsRecPlanes &&
+                  offsetof(HsRec, sl_begin) == kHsRecSl && offsetof(HsRec, ll_begin) == kHsRecLl, "the walk reads the record at these offsets");
 constexpr int kHsRecLanes = 27;   // 16 bytes per lane
 #ifndef MT_HS_SHORT
 #define MT_HS_SHORT 32
