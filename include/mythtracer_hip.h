@@ -809,7 +809,8 @@ int mt_retexture_gbuffer_device(mt_scene *scene, int chunk_w, int chunk_h, const
  * that changes at least one entry bumps it and bumps the material generation too, so every ray tree of the scene
  * becomes stale exactly as after a material edit (mt_raytree_update_materials).  A set that changes nothing changes no
  * state and makes no device call.  mt_scene_get_triangle_materials returns the host copy.  Zero triangles and
- * n_tris = 0 is MT_OK and does nothing, in both.
+ * n_tris = 0 is MT_OK and does nothing, in both.  After mt_scene_set_triangle_vertices the node-stream order is the new
+ * tree's: both calls speak that order from then on (mt_scene_read_tree gives its tri_id).
  * CONTRACT: after the set, every call that renders or shades -- mt_scene_set_materials's list, both frame engines, the
  * hybrid, the lean kernel and its redo launch, supersampled and adaptive frames, tile lists and mt_render_frame_multi
  * replicas that share a device -- gives, byte for byte and plane for plane, what the same call gives on a scene newly
@@ -867,8 +868,9 @@ int mt_raytree_keeps_tri(const mt_raytree *tree);
  * look-dev session that smooths or flattens an object's shading, or tiles, offsets or rotates a texture on a surface.
  * The arrays are n_tris x 9 doubles in node-stream order, exactly as mt_scene_desc::tri_normal / tri_uvw have them.
  * Every kernel reads them at run time and nothing mt_scene_create derives from the description reads them (node
- * records, lists and boxes come from vertices alone), so the edit is one copy.  Vertex POSITIONS are out of scope: they
- * change the octree and every derived record; a moved vertex needs a new scene.
+ * records, lists and boxes come from vertices alone), so the edit is one copy.  Vertex POSITIONS change the octree and
+ * every derived record: mt_scene_set_triangle_vertices.  After such a set the node-stream order is the NEW tree's, and
+ * these four calls speak that order (mt_scene_read_tree gives its tri_id).
  * The set is synchronous, like mt_scene_set_triangle_materials: it waits until the scene's device is idle.  The scene
  * keeps NO host copy of the attributes (144 bytes per triangle): the new array goes to a staging buffer on the GPU and
  * mt::tri_attr_stamp_kernel, one thread per triangle, compares each triangle's 9 doubles BY THEIR BITS with the live
@@ -1263,9 +1265,75 @@ typedef struct mt_triangle_desc {
 } mt_triangle_desc;
 mt_scene *mt_scene_create_triangles(const mt_triangle_desc *d, mt_build_info *info);
 
-/* The same arrays from ANY scene: its node records and triangle boxes read back from the device, its tri_id mirror.
+/* The same arrays from ANY scene: its node records and triangle boxes read back from the device, its tri_id mirror
+ * (after mt_scene_set_triangle_vertices: the new tree and the new order's tri_id).
  * Checks, in this order, all MT_ERR_ARG: scene NULL; out NULL; a scene made without tri_id. */
 int mt_scene_read_tree(const mt_scene *scene, mt_octree_arrays *out);
+
+/* Triangles MOVED in place: the vertex positions of the listed triangles replaced on the uploaded scene.  (No reference
+ * counterpart.)  For a session that moves an object between frames without giving up the scene: materials, textures (no
+ * texel is uploaded again), lights, tuning, engine, traversal mode, the stats switch, the material / texture /
+ * assignment / attribute generations, cost history and forecasts all stay.
+ * add_idx holds ADD-order indices (mt_scene_desc::tri_id values), each at most once, in any order; vertices holds
+ * n_idx x 9 doubles, triangle add_idx[i] at vertices + 9 i.  mt_scene_get_triangle_vertices returns ALL vertices in add
+ * order.  Both calls are synchronous, like mt_scene_set_triangle_normals: they wait until the scene's device is idle.
+ * There is no _device form.  The scene keeps no host copy of vertices, normals or uvw, before or after.
+ * CONTRACT: after a successful set, every call that renders, shades or reads the scene -- both frame engines, the
+ * hybrid, the lean kernel and its redo launch, supersampled and adaptive frames, tiles and tile lists, the G-buffer and
+ * light-buffer calls, mt_raytree_create[_rays], mt_trace_rays, mt_intersect_rays, mt_render_frame_multi replicas,
+ * mt_scene_read_tree and every getter -- gives, byte for byte and plane for plane, what the same call gives on a scene
+ * newly made by mt_scene_create_triangles from the same triangles in add order with the new vertices, the live normals,
+ * uvw, assignment, line numbers, materials, textures and lights, and the same switches; the counters of mt_stats match
+ * too (not the times) wherever the two frames are SCHEDULED alike -- a first frame, a frame with
+ * mt_scene_set_scheduling(scene, 0), the G-buffer, light-buffer, ray-tree and ray-list calls: the wave-level counters
+ * of a frame depend on its work order, and a moved scene orders its next frame by the costs of the frames before the
+ * move (forecasts, not results: the frame's bytes do not depend on them), which a new scene does not have.
+ * STREAM ORDER: the tree is built anew, so the scene's node-stream order is the NEW tree's from then on.
+ * mt_scene_set_triangle_materials, mt_scene_set_triangle_normals, mt_scene_set_triangle_uvw and their getters speak the
+ * new order, and mt_scene_read_tree gives the new order's tri_id: read it after every set that may have changed a
+ * triangle.
+ * How, all on the scene's GPU (mt_build.h): mt::move_unscatter_kernel brings the live vertices into add order through
+ * the old tri_id and writes the inverse permutation; mt::move_overwrite_kernel writes the listed triangles over them,
+ * comparing each triangle's 9 doubles BY THEIR BITS and counting the changed triangles; the tree is built from that
+ * device array (mt_octree_build's path); mt::move_regather_kernel writes vertices, normals, uvw, material indices,
+ * line numbers, boxes and the attribute stamp planes in the new order into new allocations.  The host reads back the
+ * tree, the stream-order boxes and vertices, runs mt_scene_create's own checks and derivation (mt_layout.h) and uploads
+ * the derived arrays into new allocations.  Only then the scene's pointers and counts are swapped, the launch
+ * configuration is made again (deep layout, LDS bytes, packed stack), the host mirrors are permuted (mt_move.h) and the
+ * old allocations freed.
+ * NO-OP: a set whose listed vertices equal the live ones by their bits changes no state and bumps nothing.  n_idx = 0
+ * is MT_OK and does nothing.
+ * FAILURE before the swap leaves the scene EXACTLY as it was -- the next frame, mt_scene_read_tree and the getters are
+ * what they were: MT_ERR_NOMEM; MT_ERR_UNSUPPORTED with the build's message for a tree deeper than MT_MAX_TREE_DEPTH or
+ * of more nodes than an int32 indexes; MT_ERR_HIP.
+ * RAY TREES: the scene has a GEOMETRY generation, 0 at creation, bumped by every set that changed a triangle.  A tree
+ * snapshots it at creation.  A tree's tri plane and hit points belong to the geometry it was traced in, so a tree of an
+ * older geometry generation is refused for good with MT_ERR_ARG by mt_raytree_shade[_colors][_device],
+ * mt_raytree_update_lights[_device], mt_raytree_update_materials and mt_raytree_regrow_materials; the message says to
+ * destroy the tree.  The check stands directly before the stale-materials check and leaves the tree untouched.
+ * mt_raytree_destroy, mt_raytree_info and the mt_raytree_read_* calls keep working.  G-buffer and light-buffer planes
+ * are the caller's and describe the old geometry; the `prim` plane holds add indices, which a move does not change.
+ * Argument checks come before any device call, in this order, all MT_ERR_ARG: scene NULL; a scene made without tri_id;
+ * n_idx negative or greater than n_tris; add_idx or vertices NULL with n_idx > 0; an index outside 0 .. n_tris - 1; an
+ * index listed twice.  (Then, for a scene from mt_scene_create: a tri_id that is no permutation of 0 .. n_tris - 1.)
+ * Values are not checked: NaN and +-inf are legal, as for the build.  The getter: scene NULL; no tri_id; n_tris unequal
+ * to the scene's; out NULL with n_tris > 0.
+ * info (nullable): the build's, as mt_octree_build reports it, with total_ms = the wall time of the whole set; all zero
+ * after a no-op.  mt_scene_move_times_last, a diagnostic in the manner of mt_scene_kernel_times: the wall times in ms of
+ * the parts of the scene's last set that changed a triangle, out_ms[MT_MOVE_TIMES], all zero before the first such set
+ * (MT_ERR_ARG: scene or out_ms NULL).  mt_build_info cannot carry them without a change of the ABI's structs. */
+enum {
+  MT_MOVE_MS_BUILD = 0,  /* the tree */
+  MT_MOVE_MS_REGATHER,   /* the per-triangle arrays in the new order */
+  MT_MOVE_MS_READBACK,   /* tree, boxes and vertices to the host */
+  MT_MOVE_MS_LAYOUT,     /* mirrors, checks, derived arrays (host) */
+  MT_MOVE_MS_UPLOAD,     /* the derived arrays to the device */
+  MT_MOVE_TIMES
+};
+int mt_scene_set_triangle_vertices(mt_scene *scene, const int32_t *add_idx, int n_idx,
+                                   const double *vertices /* n_idx x 9 */, mt_build_info *info /* nullable */);
+int mt_scene_get_triangle_vertices(mt_scene *scene, double *out /* n_tris x 9 */, int n_tris);
+int mt_scene_move_times_last(const mt_scene *scene, double *out_ms /* MT_MOVE_TIMES */);
 
 #ifdef __cplusplus
 }

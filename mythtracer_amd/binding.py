@@ -46,6 +46,7 @@ HIP_SYMBOLS = [
     "mt_scene_get_triangle_uvw", "mt_raytree_attr_info_last",
     "mt_octree_build", "mt_octree_info", "mt_octree_read", "mt_octree_destroy", "mt_scene_create_triangles",
     "mt_scene_read_tree",
+    "mt_scene_set_triangle_vertices", "mt_scene_get_triangle_vertices", "mt_scene_move_times_last",
 ]
 MT_MAX_RECURSION = 16
 
@@ -369,6 +370,9 @@ class HipAbi:
         L.mt_scene_create_triangles.restype = vp
         L.mt_scene_create_triangles.argtypes = [C.POINTER(mt_triangle_desc), C.POINTER(mt_build_info)]
         L.mt_scene_read_tree.argtypes = [vp, C.POINTER(mt_octree_arrays)]
+        L.mt_scene_set_triangle_vertices.argtypes = [vp, vp, ci, vp, C.POINTER(mt_build_info)]
+        L.mt_scene_get_triangle_vertices.argtypes = [vp, vp, ci]
+        L.mt_scene_move_times_last.argtypes = [vp, vp]
         L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
@@ -560,6 +564,33 @@ class HipAbi:
     def scene_read_tree(self, h) -> dict:
         """mt_scene_read_tree: the same arrays from any scene made with tri_id."""
         return self._read_tree(self.lib.mt_scene_read_tree, h)
+
+    def scene_set_triangle_vertices(self, h, add_idx, vertices) -> dict:
+        """mt_scene_set_triangle_vertices: the triangles `add_idx` (ADD-order indices, each at most once) of the uploaded
+        scene moved to `vertices` ((len(add_idx), 3, 3) or (len(add_idx), 9) doubles).  The scene's node-stream order is
+        the new tree's afterwards (scene_read_tree).  Returns the build's info, all zero when no listed triangle
+        changed by its bits.  RuntimeError with the library's message on a refusal: the scene is then as it was."""
+        idx = np.ascontiguousarray(add_idx, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        if v.size != idx.size * 9:
+            raise ValueError("%d triangles listed, %d doubles of vertices (9 per triangle)" % (idx.size, v.size))
+        info = mt_build_info()
+        self.check(self.lib.mt_scene_set_triangle_vertices(h, idx.ctypes.data if idx.size else None, int(idx.size),
+                                                           v.ctypes.data if v.size else None, C.byref(info)))
+        return info.as_dict()
+
+    def scene_get_triangle_vertices(self, h, n_tris) -> np.ndarray:
+        """mt_scene_get_triangle_vertices: all vertices of the scene in ADD order, (n_tris, 3, 3) float64."""
+        out = np.zeros((max(n_tris, 0), 3, 3), dtype=np.float64)
+        self.check(self.lib.mt_scene_get_triangle_vertices(h, out.ctypes.data if out.size else None, n_tris))
+        return out
+
+    def scene_move_times(self, h) -> dict:
+        """mt_scene_move_times_last: wall times in ms of the parts of the scene's last set_triangle_vertices that
+        changed a triangle: build, regather, readback, layout, upload."""
+        out = np.zeros(5, dtype=np.float64)
+        self.check(self.lib.mt_scene_move_times_last(h, out.ctypes.data))
+        return dict(zip(("build", "regather", "readback", "layout", "upload"), (float(x) for x in out)))
 
     def scene_create_triangles(self, tris: dict, device: int = 0):
         """mt_scene_create_triangles.  tris: tri_vertex, tri_normal, tri_uvw ((n, 9) doubles), tri_material, tri_line_no
@@ -1317,6 +1348,7 @@ def host_lib():
     L.mth_set_triangle_vertices.argtypes = [vp, vp, ci, vp]
     L.mth_update_geometry.argtypes = [vp]
     L.mth_update_geometry.restype = None
+    L.mth_update_geometry_in_place.argtypes = [vp]
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1716,6 +1748,21 @@ class MythTracer:
                 t.close()
         self._trees = []
         self.L.mth_update_geometry(self.h)
+
+    def update_geometry_in_place(self):
+        """MythTracer::UpdateGeometryInPlace: after set_triangle_vertices, the uploaded scenes take the moved triangles
+        in place (mt_scene_set_triangle_vertices): the tree is built again on the GPU, the device arrays are
+        re-ordered, and materials, textures, lights, tuning and cost history stay.  update_triangle_materials,
+        update_triangle_attributes and flatten() speak the new order afterwards.  With nothing uploaded yet it is
+        update_geometry() and prepare().  The RayTrees of this object belong to the old geometry: they are closed
+        first.  RuntimeError with the library's message when a device refuses; its scene is then as it was."""
+        for ref in getattr(self, "_trees", []):
+            t = ref()
+            if t is not None:
+                t.close()
+        self._trees = []
+        if not self.L.mth_update_geometry_in_place(self.h):
+            raise RuntimeError("update_geometry_in_place failed: " + self.last_error())
 
     def set_raytree_keep_triangles(self, keep: bool):
         """MythTracer::SetRayTreeKeepTriangles: RayTrees built from now on keep the triangle each ray hit."""

@@ -209,4 +209,84 @@ __global__ __launch_bounds__(kBuildThreads) void build_finish_kernel(BuildTree T
   atomicAdd(&T.prim_count[node], 1);
 }
 
+// ---- triangles moved in place (mt_scene_set_triangle_vertices): the scene's per-triangle arrays live in node-stream
+// order and the scene keeps no host copy of them, so the new tree's input is made, and the arrays are re-ordered, here.
+//   move_unscatter_kernel  a thread per OLD stream position q: the live vertices to an ADD-order staging array through
+//                          the old tri_id, and the inverse permutation old_pos[add index] = q
+//   move_overwrite_kernel  a thread per listed triangle: its 9 doubles compared BY BITS with the staged ones, written
+//                          where they differ; the changed triangles counted (one integer atomicAdd per wave)
+//   [the build above, from the staging array]
+//   move_regather_kernel   a thread per NEW stream position p: everything of triangle a = new_tri_id[p] into new arrays
+// Every index read from memory is checked against n before it is used: a thread whose index is out of range writes
+// nothing (the host has checked that both tri_id are permutations; the kernels do not rely on it).
+
+__global__ __launch_bounds__(kBuildThreads) void move_unscatter_kernel(const double *__restrict__ live_vertex,
+                                                                        const int32_t *__restrict__ old_tri_id, uint32_t n,
+                                                                        double *__restrict__ staged,
+                                                                        int32_t *__restrict__ old_pos) {
+  const uint32_t q = blockIdx.x * kBuildThreads + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t a = (uint32_t)old_tri_id[q];
+  if (a >= n) return;
+  for (int k = 0; k < 9; k++) staged[(size_t)a * 9 + k] = live_vertex[(size_t)q * 9 + k];
+  old_pos[a] = (int32_t)q;
+}
+
+__global__ __launch_bounds__(kBuildThreads) void move_overwrite_kernel(const int32_t *__restrict__ add_idx,
+                                                                        const double *__restrict__ vertices, uint32_t n_idx,
+                                                                        uint32_t n_tris, double *__restrict__ staged,
+                                                                        unsigned int *__restrict__ changed) {
+  const uint32_t i = blockIdx.x * kBuildThreads + threadIdx.x;
+  bool differs = false;
+  if (i < n_idx) {
+    const uint32_t a = (uint32_t)add_idx[i];
+    if (a < n_tris) {
+      double v[9];
+      for (int k = 0; k < 9; k++) {
+        v[k] = vertices[(size_t)i * 9 + k];
+        differs = differs || __double_as_longlong(v[k]) != __double_as_longlong(staged[(size_t)a * 9 + k]);
+      }
+      if (differs) {
+        for (int k = 0; k < 9; k++) staged[(size_t)a * 9 + k] = v[k];
+      }
+    }
+  }
+  // (every lane of the wave gets here)
+  const unsigned long long any = __ballot(differs);
+  if (any != 0ull && (int)(threadIdx.x & 63u) == __ffsll((long long)any) - 1) atomicAdd(changed, (unsigned int)__popcll(any));
+}
+
+// the per-triangle arrays of a scene in stream order; a stamp plane that does not exist is nullptr on both sides
+struct MoveArrays {
+  double *vertex, *normal, *uvw, *aabb;  // 9, 9, 9, 6 per triangle
+  int32_t *mtl, *line;
+  uint32_t *stamp[2];
+};
+
+// was: the old arrays (read), now: the new ones (written; now.aabb has room for n boxes).  staged: the vertices in add
+// order; box_add: the build's tri_aabb, add order.
+__global__ __launch_bounds__(kBuildThreads) void move_regather_kernel(MoveArrays was, MoveArrays now,
+                                                                       const double *__restrict__ staged,
+                                                                       const double *__restrict__ box_add,
+                                                                       const int32_t *__restrict__ new_tri_id,
+                                                                       const int32_t *__restrict__ old_pos, uint32_t n) {
+  const uint32_t p = blockIdx.x * kBuildThreads + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t a = (uint32_t)new_tri_id[p];
+  if (a >= n) return;
+  const uint32_t q = (uint32_t)old_pos[a];
+  if (q >= n) return;
+  for (int k = 0; k < 9; k++) {
+    now.vertex[(size_t)p * 9 + k] = staged[(size_t)a * 9 + k];
+    now.normal[(size_t)p * 9 + k] = was.normal[(size_t)q * 9 + k];
+    now.uvw[(size_t)p * 9 + k] = was.uvw[(size_t)q * 9 + k];
+  }
+  for (int k = 0; k < 6; k++) now.aabb[(size_t)p * 6 + k] = box_add[(size_t)a * 6 + k];
+  now.mtl[p] = was.mtl[q];
+  now.line[p] = was.line[q];
+  for (int w = 0; w < 2; w++) {
+    if (now.stamp[w] != nullptr) now.stamp[w][p] = was.stamp[w][q];
+  }
+}
+
 }  // namespace mt

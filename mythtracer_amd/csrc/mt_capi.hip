@@ -33,6 +33,7 @@
 #include "mt_raytree.h"
 #include "mt_build.h"
 #include "mt_layout.h"
+#include "mt_move.h"
 
 using namespace mt;
 
@@ -49,6 +50,7 @@ int fail(int code, const char *fmt, ...) {
 }
 
 int fail(const LayoutError &err) { return fail(err.code, "%s", err.msg.c_str()); }
+int fail(const MoveError &err) { return fail(err.code, "%s", err.msg.c_str()); }
 
 #define HIP_TRY(expr)                                                                   \
   do {                                                                                  \
@@ -313,6 +315,11 @@ struct mt_scene {
   Buf<uint32_t> d_attr_stamp[2];
   std::vector<uint32_t> attr_stamp_host[2];
   uint32_t attr_generation[2] = {0, 0};
+  // mt_scene_set_triangle_vertices: how often the geometry has changed since mt_scene_create (a ray tree of an older
+  // geometry is refused for good), and the wall times of the last set's parts (mt_scene_move_times_last)
+  unsigned long long geo_generation = 0;
+  bool tri_id_checked = false;  // tri_id_host was found to be a permutation (the first set; a move keeps it one)
+  double move_ms[MT_MOVE_TIMES] = {};
   // mt_order_tiles_device: summed block costs per tile
   Buf<unsigned long long> d_tile_cost;
   // mt_render_frame_multi, cost-balanced ownership: this replica's order and list; on the first replica every replica's list
@@ -2699,6 +2706,7 @@ struct mt_raytree {
   // the scene's two attribute generations then (mt_scene_set_triangle_normals / _uvw), the kernels' kRayTreeAttrWords
   // counts (first use) and what the last update or regrow made of them (mt_raytree_attr_info_last)
   uint32_t attr_generation[2] = {0, 0};
+  unsigned long long geo_generation = 0;  // the scene's geometry generation at creation (mt_scene_set_triangle_vertices)
   unsigned long long *d_attr_count = nullptr;
   mt_raytree_attr_info attr_last{};
   unsigned long long *d_mismatch = nullptr;
@@ -2806,9 +2814,20 @@ int check_raytree_rays_args(const mt_scene *s, const mt_ray_list *rays, int max_
   return MT_OK;
 }
 
+// a tree made before the scene's triangles were moved is refused for good: its tri plane and hit points belong to the
+// old geometry (checked directly before the stale-materials check; the tree is left untouched)
+int check_raytree_geometry(const mt_raytree *t) {
+  if (t->geo_generation != t->scene->geo_generation) {
+    return fail(MT_ERR_ARG, "the scene's triangles were moved after the ray tree was made (mt_scene_set_triangle_vertices): "
+                            "its hits belong to the old geometry; destroy the tree and make a new one");
+  }
+  return MT_OK;
+}
+
 // a tree whose scene's materials were edited since it was made or last updated is stale (the last check of every
 // call that shades or re-traces it)
 int check_raytree_fresh(const mt_raytree *t) {
+  MT_TRY(check_raytree_geometry(t));
   if (t->mtl_generation != t->scene->mtl_generation) {
     return fail(MT_ERR_ARG, "the scene's materials were edited after the ray tree was made: mt_raytree_update_materials "
                             "or a new tree is needed");
@@ -2967,6 +2986,7 @@ mt_raytree *raytree_new(mt_scene *s) {
   t->keep_uvw = s->raytree_uvw != 0;
   t->keep_tri = s->raytree_tri != 0;
   t->info.n_lights = s->dev.n_lights;
+  t->geo_generation = s->geo_generation;
   return t;
 }
 
@@ -3773,6 +3793,7 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     memset(info, 0, sizeof *info);
     info->n_layers_before = info->n_layers_after = I.n_layers;
   }
+  MT_TRY(check_raytree_geometry(t));
   t->attr_last = mt_raytree_attr_info{};
   if (t->mtl_generation == s->mtl_generation) return MT_OK;
   // ---- 1. the edit, and the edits this tree cannot take
@@ -4191,8 +4212,10 @@ int build_scan(Buf<char> &temp, In in, int32_t *out, size_t n, hipStream_t strea
 
 }  // extern "C++"
 
-// The build of t->n_tris triangles on t->device: mt_build.h's kernels level by level, one round trip per level.
-int octree_build(mt_octree *t, const double *tri_vertex) {
+// The build of t->n_tris triangles on t->device: mt_build.h's kernels level by level, one round trip per level.  The
+// vertices are d_vertex_in, a device array in add order (mt_scene_set_triangle_vertices' staging array), or, where
+// that is NULL, the host array tri_vertex, copied to the device first (mt_octree_build).
+int octree_build(mt_octree *t, const double *tri_vertex, const double *d_vertex_in = nullptr) {
   const auto w0 = std::chrono::steady_clock::now();
   const int32_t n = t->n_tris;
   const size_t nt = (size_t)n;
@@ -4202,13 +4225,14 @@ int octree_build(mt_octree *t, const double *tri_vertex) {
   HostCall call(nullptr, nullptr, t->ev0, t->ev1);
   const hipStream_t stream = call.stream;
   // ---- everything whose size is known: the triangles' arrays, the first nodes
-  Buf<double> d_vertex;
+  Buf<double> d_vertex_own;
   Buf<int32_t> d_cur, d_reached, d_split_before, d_value;
   Buf<uint32_t> d_key, d_key_sorted;
   Buf<unsigned long long> d_root_key;
   Buf<char> d_temp;
   size_t cap = nt / 2 + 1024;  // nodes the arrays hold; doubled when a level does not fit
-  MT_TRY(build_room(d_vertex, nt * 9, "the triangles' vertices"));
+  if (!d_vertex_in) MT_TRY(build_room(d_vertex_own, nt * 9, "the triangles' vertices"));
+  const double *const d_vertex = d_vertex_in ? d_vertex_in : d_vertex_own.p;
   MT_TRY(build_room(t->d_tri_aabb, nt * 6, "the triangles' boxes"));
   MT_TRY(build_room(d_cur, nt, "the triangles' nodes"));
   MT_TRY(build_room(d_key, nt, "the sort's keys"));
@@ -4224,7 +4248,7 @@ int octree_build(mt_octree *t, const double *tri_vertex) {
   const unsigned long long zero_keys[6] = {kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero, kBuildKeyZero};
   HIP_TRY(hipMemcpy(d_root_key, zero_keys, sizeof zero_keys, hipMemcpyHostToDevice));
   if (n > 0) {
-    HIP_TRY(hipMemcpy(d_vertex, tri_vertex, nt * 72, hipMemcpyHostToDevice));
+    if (!d_vertex_in) HIP_TRY(hipMemcpy(d_vertex_own, tri_vertex, nt * 72, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(d_cur, 0, nt * sizeof(int32_t), stream));  // every triangle starts at the root
   }
   auto tree = [&]() {
@@ -4237,7 +4261,7 @@ int octree_build(mt_octree *t, const double *tri_vertex) {
     return T;
   };
   MT_TRY(call.begin(false));
-  if (n > 0) HIP_TRY(launch_flat(build_tri_box_kernel, nt, stream, d_vertex.p, (uint32_t)n, t->d_tri_aabb.p, d_root_key.p));
+  if (n > 0) HIP_TRY(launch_flat(build_tri_box_kernel, nt, stream, d_vertex, (uint32_t)n, t->d_tri_aabb.p, d_root_key.p));
   hipLaunchKernelGGL(build_root_kernel, dim3(1), dim3(64), 0, stream, tree(), d_root_key.p, n);
   HIP_TRY(hipGetLastError());
   // ---- level by level: a level is the contiguous range [level_begin, level_begin + level_n) of node indices
@@ -4486,6 +4510,330 @@ int mt_scene_read_tree(const mt_scene *s, mt_octree_arrays *out) {
     HIP_TRY(hipMemcpy(box.data(), s->dev.tri_aabb, nt * 48, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < nt; p++) memcpy(out->tri_aabb + (size_t)s->tri_id_host[p] * 6, &box[p * 6], 48);
   }
+  return MT_OK;
+}
+
+// ---- triangles moved in place (mt_build.h's move_* kernels, mt_move.h's bookkeeping) ---------------------------------
+namespace {
+
+// Device allocations made aside while a move is under way: freed with this object unless the scene has taken them.
+struct MoveAllocs {
+  std::vector<void *> p;
+  MoveAllocs() = default;
+  MoveAllocs(const MoveAllocs &) = delete;
+  MoveAllocs &operator=(const MoveAllocs &) = delete;
+  ~MoveAllocs() {
+    for (void *q : p) (void)hipFree(q);
+  }
+};
+
+extern "C++" {
+
+// `count` elements of new device memory (at least one byte), owned by `A`; what does not fit is MT_ERR_NOMEM
+template <typename T>
+int move_alloc(MoveAllocs &A, size_t count, const char *what, T **out) {
+  const size_t bytes = (count ? count : 1) * sizeof(T);
+  void *d = nullptr;
+  const hipError_t e = hipMalloc(&d, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s", bytes, what);
+    return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
+  }
+  A.p.push_back(d);
+  *out = (T *)d;
+  return MT_OK;
+}
+
+// upload() into an allocation of `A` instead of the scene's
+template <typename T>
+int move_upload(MoveAllocs &A, const std::vector<T> &host, const char *what, const T **out) {
+  T *d = nullptr;
+  MT_TRY(move_alloc(A, host.size(), what, &d));
+  if (!host.empty()) HIP_TRY(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = d;
+  return MT_OK;
+}
+
+}  // extern "C++"
+
+double ms_since(const std::chrono::steady_clock::time_point &t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Steps 1 .. 6 of mt_scene_set_triangle_vertices for a checked list of n_idx >= 1 triangles.  Until the swap at the end
+// everything is built aside (locals that free themselves): a return before it leaves the scene exactly as it was.
+int move_triangles(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, mt_build_info *info) {
+  const auto w0 = std::chrono::steady_clock::now();
+  const int32_t n = s->dev.n_tris;
+  const size_t nt = (size_t)n, ni = (size_t)n_idx;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the scene while it is taken apart
+  const hipStream_t stream = nullptr;
+  // ---- 1. + 2. the live vertices in add order, the listed triangles written over them
+  Buf<double> d_stage, d_listed;
+  Buf<int32_t> d_old_id, d_old_pos, d_idx;
+  Buf<unsigned int> d_changed;
+  MT_TRY(build_room(d_stage, nt * 9, "the staged vertices"));
+  MT_TRY(build_room(d_listed, ni * 9, "the listed vertices"));
+  MT_TRY(build_room(d_old_id, nt, "the old tri_id"));
+  MT_TRY(build_room(d_old_pos, nt, "the old stream positions"));
+  MT_TRY(build_room(d_idx, ni, "the index list"));
+  MT_TRY(build_room(d_changed, 1, "the changed count"));
+  HIP_TRY(hipMemcpyAsync(d_old_id, s->tri_id_host.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_idx, add_idx, ni * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_listed, vertices, ni * 72, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(d_old_pos, 0xff, nt * sizeof(int32_t), stream));
+  HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), stream));
+  HIP_TRY(launch_flat(move_unscatter_kernel, nt, stream, s->dev.tri_vertex, (const int32_t *)d_old_id.p, (uint32_t)n, d_stage.p,
+                      d_old_pos.p));
+  HIP_TRY(launch_flat(move_overwrite_kernel, ni, stream, (const int32_t *)d_idx.p, (const double *)d_listed.p, (uint32_t)n_idx,
+                      (uint32_t)n, d_stage.p, d_changed.p));
+  unsigned int changed = 0;
+  HIP_TRY(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (changed == 0) return MT_OK;  // the listed vertices are the live ones, bit for bit
+  // ---- 3. the tree, from the staging array
+  auto t0 = std::chrono::steady_clock::now();
+  double part_ms[MT_MOVE_TIMES] = {};
+  std::unique_ptr<mt_octree, void (*)(mt_octree *)> tree(new mt_octree(), mt_octree_destroy);
+  tree->device = s->device;
+  tree->n_tris = n;
+  {
+    const int rc = octree_build(tree.get(), nullptr, d_stage.p);
+    if (rc != MT_OK) {
+      const std::string why = g_err;  // (the text survives the clean-up)
+      (void)hipGetLastError();
+      return fail(rc, "%s", why.c_str());
+    }
+  }
+  part_ms[MT_MOVE_MS_BUILD] = ms_since(t0);
+  // ---- 4. the per-triangle arrays in the new order, in new allocations
+  t0 = std::chrono::steady_clock::now();
+  MoveAllocs fresh;
+  Buf<uint32_t> d_stamp_new[2];
+  Buf<double> d_box_stream;
+  Buf<int32_t> d_tri_id_new;
+  MoveArrays was{}, now{};
+  was.vertex = const_cast<double *>(s->dev.tri_vertex);
+  was.normal = const_cast<double *>(s->dev.tri_normal);
+  was.uvw = const_cast<double *>(s->dev.tri_uvw);
+  was.aabb = const_cast<double *>(s->dev.tri_aabb);
+  was.mtl = const_cast<int32_t *>(s->dev.tri_mtl);
+  was.line = const_cast<int32_t *>(s->dev.tri_line);
+  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' vertices", &now.vertex));
+  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' normals", &now.normal));
+  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' uvw", &now.uvw));
+  MT_TRY(move_alloc(fresh, nt, "the triangles' materials", &now.mtl));
+  MT_TRY(move_alloc(fresh, nt, "the triangles' line numbers", &now.line));
+  MT_TRY(build_room(d_box_stream, nt * 6, "the triangles' boxes"));
+  now.aabb = d_box_stream;
+  for (int w = 0; w < 2; w++) {
+    if (s->d_attr_stamp[w].p == nullptr) continue;
+    MT_TRY(build_room(d_stamp_new[w], nt, "the triangles' stamp plane"));
+    was.stamp[w] = s->d_attr_stamp[w];
+    now.stamp[w] = d_stamp_new[w];
+  }
+  if (s->d_tri_id.p != nullptr) {  // (the G-buffer's `prim` plane reads it)
+    MT_TRY(build_room(d_tri_id_new, nt, "the scene's tri_id"));
+    HIP_TRY(hipMemcpyAsync(d_tri_id_new, tree->d_tri_id, nt * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+  }
+  HIP_TRY(launch_flat(move_regather_kernel, nt, stream, was, now, (const double *)d_stage.p, (const double *)tree->d_tri_aabb.p,
+                      (const int32_t *)tree->d_tri_id.p, (const int32_t *)d_old_pos.p, (uint32_t)n));
+  HIP_TRY(hipStreamSynchronize(stream));
+  part_ms[MT_MOVE_MS_REGATHER] = ms_since(t0);
+  // ---- 5. the tree, the stream-order boxes and vertices on the host; the checks and the derived arrays of a new scene
+  t0 = std::chrono::steady_clock::now();
+  const size_t nn = (size_t)tree->n_nodes;
+  std::vector<double> node_aabb(nn * 6), node_center(nn * 3), box(nt * 6), vertex(nt * 9);
+  std::vector<int32_t> first_child(nn), prim_begin(nn), prim_count(nn), new_tri_id(nt);
+  mt_octree_arrays a{};
+  a.node_aabb = node_aabb.data();
+  a.node_center = node_center.data();
+  a.first_child = first_child.data();
+  a.prim_begin = prim_begin.data();
+  a.prim_count = prim_count.data();
+  a.tri_id = new_tri_id.data();
+  MT_TRY(octree_read_arrays(tree->n_nodes, n, tree->depth, tree->d_aabb, tree->d_center, tree->d_first_child, tree->d_prim_begin,
+                            tree->d_prim_count, tree->d_tri_id, tree->d_tri_aabb, &a));
+  HIP_TRY(hipMemcpy(box.data(), d_box_stream, nt * 48, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(vertex.data(), now.vertex, nt * 72, hipMemcpyDeviceToHost));
+  part_ms[MT_MOVE_MS_READBACK] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  MovedMirrors mirrors;
+  std::vector<int32_t> from;
+  MoveError merr;
+  if (!move_mirrors(s->tri_id_host, new_tri_id.data(), *s->tri_mtl_host, s->attr_stamp_host, &mirrors, &from, &merr)) return fail(merr);
+  auto tri_mtl_new = std::make_shared<const std::vector<int32_t>>(std::move(mirrors.tri_mtl));  // (trees hold the old one)
+  // The description of the new scene as mt_scene_create would get it.  check_scene_desc and derive_layout read the node
+  // arrays, tri_vertex, tri_aabb, tri_material and the material / texture tables; of tri_normal, tri_uvw, tri_line_no
+  // and the textures' texels they only ask that they are there (the scene keeps no host copy of them: stand-ins).
+  std::vector<mt_texture> texs((size_t)s->n_textures);
+  for (size_t i = 0; i < texs.size(); i++) {
+    const DevTexture &t = s->texs_host[i];
+    texs[i].width = t.width;
+    texs[i].height = t.height;
+    texs[i].format = t.format;
+    texs[i].texels = t.texels;
+  }
+  mt_scene_desc sd;
+  memset(&sd, 0, sizeof sd);
+  sd.struct_size = sizeof sd;
+  sd.abi_version = MT_ABI_VERSION;
+  sd.device = s->device;
+  sd.n_nodes = tree->n_nodes;
+  sd.n_tris = n;
+  sd.n_materials = s->n_materials;
+  sd.n_textures = s->n_textures;
+  sd.tree_depth = tree->depth;
+  sd.node_aabb = node_aabb.data();
+  sd.node_center = node_center.data();
+  sd.node_first_child = first_child.data();
+  sd.node_prim_begin = prim_begin.data();
+  sd.node_prim_count = prim_count.data();
+  sd.tri_vertex = vertex.data();
+  sd.tri_normal = vertex.data();  // (stand-in)
+  sd.tri_uvw = vertex.data();     // (stand-in)
+  sd.tri_aabb = box.data();
+  sd.tri_material = tri_mtl_new->data();
+  sd.tri_line_no = new_tri_id.data();  // (stand-in)
+  sd.tri_id = new_tri_id.data();
+  sd.materials = s->mtls_host.data();
+  sd.textures = texs.data();
+  std::vector<int> depth_of;
+  int max_depth = 0;
+  LayoutError lerr;
+  if (!check_scene_desc(sd, &depth_of, &max_depth, &lerr)) return fail(lerr);
+  SceneLayout L;
+  derive_layout(sd, depth_of, &L);
+  part_ms[MT_MOVE_MS_LAYOUT] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  DevScene dev = s->dev;
+  MT_TRY(move_upload(fresh, L.groups, "the block boxes", &dev.grp_aabb32));
+  MT_TRY(move_upload(fresh, L.supers, "the super boxes", &dev.sup_aabb32));
+  MT_TRY(move_upload(fresh, L.subs, "the subtree boxes", &dev.sub_aabb32));
+  MT_TRY(move_upload(fresh, L.hsr, "the walk's records", &dev.hs_rec));
+  MT_TRY(move_upload(fresh, L.ll_tri, "the long lists", &dev.ll_tri));
+  MT_TRY(move_upload(fresh, L.ll_exact, "the long lists", &dev.ll_exact));
+  MT_TRY(move_upload(fresh, L.ll_box_q, "the long lists' boxes", &dev.ll_box_q));
+  MT_TRY(move_upload(fresh, L.ll_grp_q, "the long lists' boxes", &dev.ll_grp_q));
+  MT_TRY(move_upload(fresh, L.ll_sup_q, "the long lists' boxes", &dev.ll_sup_q));
+  MT_TRY(move_upload(fresh, L.sl_box, "the short lists' boxes", &dev.sl_box32));
+  MT_TRY(move_upload(fresh, L.recs, "the node records", &dev.nodes));
+  MT_TRY(move_upload(fresh, L.tri_aabb, "the triangles' boxes", &dev.tri_aabb));
+  MT_TRY(move_upload(fresh, L.tri_aabb32, "the triangles' boxes", &dev.tri_aabb32));
+  part_ms[MT_MOVE_MS_UPLOAD] = ms_since(t0);
+  for (int k = 0; k < 3; k++) dev.bmax[k] = L.bmax[k];
+  dev.tri_vertex = now.vertex;
+  dev.tri_normal = now.normal;
+  dev.tri_uvw = now.uvw;
+  dev.tri_mtl = now.mtl;
+  dev.tri_line = now.line;
+  dev.n_nodes = tree->n_nodes;
+  dev.tree_depth = L.max_depth;
+  dev.scene_regular = L.regular ? 1 : 0;
+  dev.pack_shift = s->tune.v[MT_TUNE_PACKED_STACK] != 0.0 ? pack_shift_for(n, tree->n_nodes) : 0;
+  // what the scene gives up once the swap stands (as many as `fresh` brings: s->allocs keeps its size)
+  const void *const old_allocs[] = {s->dev.grp_aabb32, s->dev.sup_aabb32, s->dev.sub_aabb32, s->dev.hs_rec, s->dev.ll_tri,
+                                    s->dev.ll_exact, s->dev.ll_box_q, s->dev.ll_grp_q, s->dev.ll_sup_q, s->dev.sl_box32,
+                                    s->dev.nodes, s->dev.tri_aabb, s->dev.tri_aabb32, s->dev.tri_vertex, s->dev.tri_normal,
+                                    s->dev.tri_uvw, s->dev.tri_mtl, s->dev.tri_line};
+  std::vector<void *> allocs_new;
+  allocs_new.reserve(s->allocs.size());
+  for (void *p : s->allocs) {
+    if (std::find(std::begin(old_allocs), std::end(old_allocs), (const void *)p) == std::end(old_allocs)) allocs_new.push_back(p);
+  }
+  if (allocs_new.size() + fresh.p.size() != s->allocs.size()) {
+    return fail(MT_ERR_HIP, "the scene's allocations are not the %zu its arrays name", fresh.p.size());
+  }
+  allocs_new.insert(allocs_new.end(), fresh.p.begin(), fresh.p.end());
+  // ---- 6. the swap.  The launch configuration depends on the tree (deep layout, LDS bytes, packed stack): if it cannot
+  // be made, the old scene and its configuration come back.  After it nothing fails.
+  const DevScene dev_was = s->dev;
+  s->dev = dev;
+  {
+    const int rc = configure_launch(s);
+    if (rc != MT_OK) {
+      const std::string why = g_err;
+      (void)hipGetLastError();
+      s->dev = dev_was;
+      (void)configure_launch(s);
+      return fail(rc, "%s", why.c_str());
+    }
+  }
+  s->dev_uploaded_valid = false;
+  s->allocs.swap(allocs_new);
+  for (const void *p : old_allocs) (void)hipFree(const_cast<void *>(p));
+  fresh.p.clear();  // (the scene's now)
+  s->tri_id_host.swap(mirrors.tri_id);
+  s->tri_mtl_host = tri_mtl_new;
+  for (int w = 0; w < 2; w++) {
+    s->attr_stamp_host[w].swap(mirrors.stamp[w]);
+    if (d_stamp_new[w].p != nullptr) {
+      std::swap(s->d_attr_stamp[w].p, d_stamp_new[w].p);
+      std::swap(s->d_attr_stamp[w].bytes, d_stamp_new[w].bytes);
+    }
+  }
+  if (d_tri_id_new.p != nullptr) {
+    std::swap(s->d_tri_id.p, d_tri_id_new.p);
+    std::swap(s->d_tri_id.bytes, d_tri_id_new.bytes);
+  }
+  s->geo_generation++;
+  for (int k = 0; k < MT_MOVE_TIMES; k++) s->move_ms[k] = part_ms[k];
+  if (info) {
+    *info = tree->info;
+    info->total_ms = ms_since(w0);
+  }
+  return MT_OK;
+}
+
+}  // namespace
+
+int mt_scene_set_triangle_vertices(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, mt_build_info *info) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  MoveError err;
+  if (!check_move_list(s->have_tri_id, s->dev.n_tris, add_idx, n_idx, vertices, &err)) return fail(err);
+  if (info) memset(info, 0, sizeof *info);
+  if (n_idx == 0) return MT_OK;
+  if (!s->tri_id_checked) {  // (a tri_id is the caller's at mt_scene_create: the kernels scatter through it; checked once)
+    std::vector<int32_t> from;
+    if (!compose_move(s->tri_id_host.data(), s->tri_id_host.data(), s->tri_id_host.size(), &from, &err)) {
+      return fail(MT_ERR_ARG, "the scene's tri_id is no permutation of its triangles: %s", err.msg.c_str());
+    }
+    s->tri_id_checked = true;
+  }
+  try {
+    return move_triangles(s, add_idx, n_idx, vertices, info);
+  } catch (const std::bad_alloc &) {
+    return fail(MT_ERR_NOMEM, "no host memory for the moved scene's arrays");
+  }
+}
+
+int mt_scene_get_triangle_vertices(mt_scene *s, double *out, int n_tris) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  MoveError err;
+  if (!check_move_get(s->have_tri_id, s->dev.n_tris, out, n_tris, &err)) return fail(err);
+  if (n_tris == 0) return MT_OK;
+  const size_t nt = (size_t)n_tris;
+  try {
+    std::vector<double> stream_order(nt * 9);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(stream_order.data(), s->dev.tri_vertex, nt * 72, hipMemcpyDeviceToHost));  // (waits for the device)
+    for (size_t p = 0; p < nt; p++) {
+      const int32_t a = s->tri_id_host[p];
+      if (a < 0 || a >= n_tris) return fail(MT_ERR_ARG, "the scene's tri_id is no permutation of its triangles");
+      memcpy(out + (size_t)a * 9, &stream_order[p * 9], 72);
+    }
+  } catch (const std::bad_alloc &) {
+    return fail(MT_ERR_NOMEM, "no host memory for %d triangles' vertices", n_tris);
+  }
+  return MT_OK;
+}
+
+int mt_scene_move_times_last(const mt_scene *s, double *out_ms) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  if (!out_ms) return fail(MT_ERR_ARG, "the output array is NULL");
+  for (int k = 0; k < MT_MOVE_TIMES; k++) out_ms[k] = s->move_ms[k];
   return MT_OK;
 }
 

@@ -235,7 +235,7 @@ class MythTracer {
   // After triangles' per-vertex NORMALS or texture coordinates were edited (GetScene()->tree.MutableTriangle(i)->normal
   // / ->uvw): flattens them again in the uploaded order and replaces them on every device replica
   // (mt_scene_set_triangle_normals, mt_scene_set_triangle_uvw), without uploading a triangle again.  Vertex positions
-  // are not covered: a moved vertex needs a new upload.  Before the first upload it is Prepare.  RayTrees built before
+  // are not covered: a moved vertex needs UpdateGeometryInPlace or a new upload.  Before the first upload it is Prepare.  RayTrees built before
   // the edit are stale until UpdateRayTreeMaterials / RegrowRayTree, which need a tree that keeps triangles for it.
   bool UpdateTriangleAttributes();
   // The octree of the next Prepare is built on the GPU (OctTree::SetDeviceBuild, mt_octree_build on the facade's first
@@ -256,6 +256,22 @@ class MythTracer {
   // scene that no longer exists and must have been destroyed or Reset BEFORE the call (see RayTree); there is no way
   // to bring such a tree to the moved geometry, and none to ask it whether it is fresh: build a new one.
   void UpdateGeometry();
+  // The same IN PLACE (mt_scene_set_triangle_vertices): the device scenes stay alive and keep their materials, textures
+  // (nothing of them is uploaded again), lights, tuning, engine and cost history.  The root box is recomputed on the
+  // host, the triangles moved by SetTriangleVertices since the last upload or update (all triangles when none were
+  // moved through it) go to every device replica, which builds the tree again on its GPU and re-orders its arrays, and
+  // the host tree adopts the new flat tree from the first replica.  UpdateTriangleMaterials, UpdateTriangleAttributes
+  // and flatten() speak the new order afterwards; the scene stays finalized and uploaded.  With nothing uploaded yet it
+  // is UpdateGeometry() followed by Prepare().  False with LastError() set when a device refuses (no memory, a tree
+  // deeper than MT_MAX_TREE_DEPTH): that device's scene is as it was, and neither the host builder nor a new upload
+  // is used instead.  With one device the facade is then exactly as before the call.  With several, the first device
+  // moves first and the host tree adopts its tree at once, so the host's stream order is always the first device's; a
+  // LATER replica that refuses stays on the old geometry, and the only legal calls then are a repeated
+  // UpdateGeometryInPlace() (the moved triangles are remembered; the set is a no-op where it already happened) or
+  // UpdateGeometry().  RayTree objects follow
+  // UpdateGeometry's rule: destroy or Reset them BEFORE the call (a tree of the old geometry is refused by every call
+  // that shades or updates it).
+  bool UpdateGeometryInPlace();
   // RayTrees built from now on also keep the triangle each ray hit (mt_scene_set_raytree_tri): 4 bytes more per ray,
   // and UpdateRayTreeMaterials / RegrowRayTree then take an UpdateTriangleMaterials, which they refuse for a tree
   // without.  Off by default; independent of SetRayTreeKeepUVW (a reassignment TO a textured material needs both).
@@ -317,6 +333,7 @@ class MythTracer {
   std::vector<const Material*> uploaded_materials_;        // UpdateTriangleMaterials: the dense table's sources
   bool keep_uvw_ = false;                                  // SetRayTreeKeepUVW
   bool keep_tri_ = false;                                  // SetRayTreeKeepTriangles
+  std::vector<int> moved_;                                 // SetTriangleVertices' indices since the last upload or update
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
   int adaptive_ss_ = 1, adaptive_threshold_ = 16;

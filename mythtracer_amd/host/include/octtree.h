@@ -9,12 +9,14 @@
 // traversal results depend on them.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <vector>
 #include "math3d.h"
 #include "primitive.h"
 
 struct mt_scene;
+struct mt_octree_arrays;
 
 namespace raytracer {
 using math3d::V3D;
@@ -56,6 +58,14 @@ class OctTree {
   // {0,0,0}-{0,0,0} over all triangles in add order -- it can shrink --, and the tree is unfinalized: the next
   // Finalize() builds it again.  The standalone IntersectRay's upload is dropped.
   void Refit();
+  // extension, for a tree that was rebuilt elsewhere after triangles were moved (mt_scene_set_triangle_vertices on the
+  // uploaded scene): RefitRoot recomputes the root box like Refit and drops the standalone IntersectRay's upload, but
+  // leaves the tree as it is; Adopt takes `flat` as the finalized tree, as Finalize does under SetDeviceBuild.
+  void RefitRoot();
+  void Adopt(FlatTree flat);
+  // A flat tree through `read` (mt_octree_read of a tree, mt_scene_read_tree of a scene: MT_OK or an error code): a
+  // first read with no array wanted gives the counts, a second fills the arrays.  The code of a failed read, else 0.
+  static int ReadFlat(const std::function<int(mt_octree_arrays*)>& read, FlatTree* out);
   // extension: no "Triangles: N" line on stdout
   void SetQuiet(bool quiet) { quiet_ = quiet; }
   // extension: HIP device of the standalone IntersectRay(s) (MythTracer::SetDevice forwards to it)

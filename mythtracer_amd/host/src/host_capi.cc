@@ -678,6 +678,9 @@ int mth_set_triangle_vertices(void* p, const int32_t* add_indices, int n, const 
 // MythTracer::UpdateGeometry
 void mth_update_geometry(void* p) { static_cast<Handle*>(p)->mt.UpdateGeometry(); }
 
+// MythTracer::UpdateGeometryInPlace; 0 with the facade's message when a device refuses
+int mth_update_geometry_in_place(void* p) { return static_cast<Handle*>(p)->mt.UpdateGeometryInPlace() ? 1 : 0; }
+
 // MythTracer::SetRayTreeKeepTriangles
 void mth_set_raytree_keep_triangles(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepTriangles(keep != 0); }
 

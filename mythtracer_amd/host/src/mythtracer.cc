@@ -226,6 +226,7 @@ bool MythTracer::Prepare() {
   }
   uploaded_textures_ = flat.texture_of;
   uploaded_materials_ = flat.material_of;
+  moved_.clear();  // (the upload took every vertex as it is)
   return true;
 }
 
@@ -250,13 +251,63 @@ bool MythTracer::SetTriangleVertices(const std::vector<int>& add_indices, const 
     for (int v = 0; v < 3; v++) t->vertex[v] = vertices[k * 3 + (size_t)v];
     t->CacheAABB();
   }
+  moved_.insert(moved_.end(), add_indices.begin(), add_indices.end());
   return true;
 }
 
 void MythTracer::UpdateGeometry() {
   scene.tree.Refit();
   was_scene_finalized = false;
+  moved_.clear();
   DropDeviceScenes();
+}
+
+bool MythTracer::UpdateGeometryInPlace() {
+  if (!was_scene_finalized || dev_ == nullptr) {  // nothing uploaded yet: the upload takes the vertices as they are
+    UpdateGeometry();
+    return Prepare();
+  }
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  scene.tree.RefitRoot();
+  // the moved triangles, each once (all of them when the caller edited MutableTriangle(i)->vertex itself)
+  const size_t nt = scene.tree.PrimitiveCount();
+  std::vector<int32_t> idx;
+  if (moved_.empty()) {
+    idx.resize(nt);
+    for (size_t i = 0; i < nt; i++) idx[i] = (int32_t)i;
+  } else {
+    std::vector<bool> seen(nt, false);
+    for (int i : moved_) {
+      if (!seen[(size_t)i]) idx.push_back((int32_t)i);
+      seen[(size_t)i] = true;
+    }
+  }
+  std::vector<double> vtx(idx.size() * 9);
+  for (size_t k = 0; k < idx.size(); k++) memcpy(&vtx[k * 9], scene.tree.GetTriangle((size_t)idx[k])->vertex, 72);
+  // The first replica, and at once its new tree: from here on the host tree speaks the order dev_ speaks, whatever a
+  // later replica answers.
+  if (mt_scene_set_triangle_vertices(dev_, idx.data(), (int)idx.size(), vtx.data(), nullptr) != MT_OK) {
+    return refuse(std::string("moving the triangles in place failed: ") + mt_last_error());
+  }
+  FlatTree f;
+  mt_scene* const first = dev_;
+  if (OctTree::ReadFlat([first](mt_octree_arrays* a) { return mt_scene_read_tree(first, a); }, &f) != MT_OK) {
+    return refuse(std::string("reading the moved tree failed: ") + mt_last_error());
+  }
+  scene.tree.Adopt(std::move(f));
+  // The other replicas.  One that refuses keeps its old geometry while dev_ has moved: moved_ is kept, so a repeated
+  // call moves the replicas that are behind (the set is a no-op on those that are not); UpdateGeometry() uploads anew.
+  for (mt_scene* s : replicas_) {
+    if (mt_scene_set_triangle_vertices(s, idx.data(), (int)idx.size(), vtx.data(), nullptr) != MT_OK) {
+      return refuse(std::string("moving the triangles in place failed on a replica: ") + mt_last_error());
+    }
+  }
+  moved_.clear();
+  return true;
 }
 
 bool MythTracer::UpdateTriangleMaterials() {

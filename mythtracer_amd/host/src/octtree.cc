@@ -75,6 +75,18 @@ void OctTree::Refit() {
   geometry_only_ = nullptr;
 }
 
+void OctTree::RefitRoot() {
+  root_aabb_ = AABB();
+  for (const auto& p : prims_) root_aabb_.Extend(p->GetAABB());
+  if (geometry_only_) mt_scene_destroy(geometry_only_);
+  geometry_only_ = nullptr;
+}
+
+void OctTree::Adopt(FlatTree flat) {
+  flat_ = std::move(flat);
+  finalized_ = true;
+}
+
 // flat_ from mt_octree_build + mt_octree_read on device_; false with error_ set, and flat_ empty, when the build fails
 bool OctTree::FinalizeOnDevice() {
   const size_t nt = prims_.size();
@@ -91,30 +103,40 @@ bool OctTree::FinalizeOnDevice() {
     return false;
   }
   FlatTree f;
-  const size_t n = (size_t)info.n_nodes;
+  const int rc = ReadFlat([t](mt_octree_arrays* a) { return mt_octree_read(t, a); }, &f);
+  mt_octree_destroy(t);
+  if (rc != MT_OK) {
+    error_ = std::string("device tree build failed: ") + mt_last_error();
+    return false;
+  }
+  flat_ = std::move(f);
+  return true;
+}
+
+int OctTree::ReadFlat(const std::function<int(mt_octree_arrays*)>& read, FlatTree* out) {
+  mt_octree_arrays a;
+  memset(&a, 0, sizeof a);
+  int rc = read(&a);  // (the counts)
+  if (rc != MT_OK) return rc;
+  FlatTree f;
+  const size_t n = (size_t)a.n_nodes;
   f.node_aabb.resize(n * 6);
   f.node_center.resize(n * 3);
   f.first_child.resize(n);
   f.prim_begin.resize(n);
   f.prim_count.resize(n);
-  f.tri_id.resize(nt);
-  mt_octree_arrays a;
-  memset(&a, 0, sizeof a);
+  f.tri_id.resize((size_t)a.n_tris);
   a.node_aabb = f.node_aabb.data();
   a.node_center = f.node_center.data();
   a.first_child = f.first_child.data();
   a.prim_begin = f.prim_begin.data();
   a.prim_count = f.prim_count.data();
   a.tri_id = f.tri_id.data();
-  const int rc = mt_octree_read(t, &a);
-  mt_octree_destroy(t);
-  if (rc != MT_OK) {
-    error_ = std::string("device tree build failed: ") + mt_last_error();
-    return false;
-  }
+  rc = read(&a);
+  if (rc != MT_OK) return rc;
   f.depth = a.depth;
-  flat_ = std::move(f);
-  return true;
+  *out = std::move(f);
+  return MT_OK;
 }
 
 void OctTree::Finalize() {
