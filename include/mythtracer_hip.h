@@ -150,7 +150,9 @@ int mt_abi_version(void);
 int mt_device_count(void);
 
 /* Uploads the flattened scene to HBM.  Replaces: the in-memory Scene the
- * reference keeps after LoadObj + Finalize (mythtracer.cc:247-256,281-285). */
+ * reference keeps after LoadObj + Finalize (mythtracer.cc:247-256,281-285).
+ * NULL on failure, with mt_last_error: an upload that does not fit on the device
+ * is MT_ERR_NOMEM, as for every other call here that allocates. */
 mt_scene *mt_scene_create(const mt_scene_desc *desc);
 void mt_scene_destroy(mt_scene *scene);
 

@@ -33,6 +33,7 @@
 #include "mt_raytree.h"
 #include "mt_build.h"
 #include "mt_layout.h"
+#include "mt_host_tree.h"
 #include "mt_move.h"
 
 using namespace mt;
@@ -68,6 +69,67 @@ int fail(const MoveError &err) { return fail(err.code, "%s", err.msg.c_str()); }
     if (rc_ != MT_OK) return rc_;                                                       \
   } while (0)
 
+// The text g_err holds now, to fail with again after a clean-up that may overwrite it (a destroy, a configure, a fail
+// that quotes it)
+struct KeptError {
+  const std::string text = g_err;
+  int fail_again(int rc) const { return fail(rc, "%s", text.c_str()); }
+};
+
+// hipMalloc of `bytes` (at least one) for `what`: an allocation that does not fit is MT_ERR_NOMEM, *p is NULL then
+int device_malloc(void **p, size_t bytes, const char *what) {
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+  if (e == hipSuccess) return MT_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s", bytes, what);
+  return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
+}
+
+// A move-only list of device allocations, freed with it.  Whatever alloc() and upload() hand out belongs to the list;
+// ownership changes hands by swapping whole lists or single slots (the k-th allocation made is slot k), never by
+// copying a pointer.
+class DeviceAllocs {
+  std::vector<void *> p_;
+
+ public:
+  DeviceAllocs() = default;
+  DeviceAllocs(const DeviceAllocs &) = delete;
+  DeviceAllocs &operator=(const DeviceAllocs &) = delete;
+  DeviceAllocs(DeviceAllocs &&o) noexcept { p_.swap(o.p_); }
+  ~DeviceAllocs() { free_all(); }
+  void free_all() {
+    for (void *q : p_) (void)hipFree(q);
+    p_.clear();
+  }
+  void swap(DeviceAllocs &o) noexcept { p_.swap(o.p_); }
+  void swap_slot(size_t slot, DeviceAllocs &o, size_t o_slot) { std::swap(p_.at(slot), o.p_.at(o_slot)); }
+  // `count` elements (at least one) of new device memory; *out is const T * where only kernels read it, T * where its
+  // owner writes it
+  template <typename T, typename P>
+  int alloc(size_t count, const char *what, P *out) {
+    p_.reserve(p_.size() + 1);  // (no push_back that throws with the allocation in hand)
+    void *d = nullptr;
+    MT_TRY(device_malloc(&d, (count ? count : 1) * sizeof(T), what));
+    p_.push_back(d);
+    *out = (T *)d;
+    return MT_OK;
+  }
+  // ... filled from `count` elements of `host`
+  template <typename T, typename P>
+  int upload(const T *host, size_t count, const char *what, P *out) {
+    T *d = nullptr;
+    MT_TRY(alloc<T>(count, what, &d));
+    if (count) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    *out = d;
+    return MT_OK;
+  }
+  template <typename T, typename P>
+  int upload(const std::vector<T> &host, const char *what, P *out) {
+    return upload(host.data(), host.size(), what, out);
+  }
+};
+
 constexpr size_t kLdsBudget = 160 * 1024;
 
 // A growable scratch buffer that owns its allocation: device memory, or page-locked host memory (HOST).  It only grows
@@ -83,6 +145,10 @@ struct Buf {
     if (p) (void)(HOST ? hipHostFree(p) : hipFree(p));
   }
   operator T *() const { return p; }
+  void swap(Buf &o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
   int ensure(size_t need, unsigned host_flags = hipHostMallocDefault) {
     if (bytes >= need && p) return MT_OK;
     void **ptr = (void **)&p;
@@ -188,12 +254,25 @@ struct ForecastBank {
   bool irr_sensor_valid = false;
 };
 
+// The scene's own, writable view of the per-triangle arrays that DevScene shows the kernels as const (the edit calls
+// write them, a move regathers them)
+struct TriArrays {
+  double *vertex = nullptr, *normal = nullptr, *uvw = nullptr;  // DevScene::tri_vertex, tri_normal, tri_uvw
+  int32_t *mtl = nullptr, *line = nullptr;                      // DevScene::tri_mtl, tri_line
+};
+
 }  // namespace
 
 struct mt_scene {
   int device = 0;
   DevScene dev{};
-  std::vector<void *> allocs;  // the scene's uploads (scene_create_impl)
+  // The scene's uploads.  geo: the 13 arrays derived from the geometry (upload_derived) and the five of `tri`; a move
+  // builds a new one aside and swaps it in whole.  tables: texture i's texels in slot i, then the materials and the
+  // texture table; mt_scene_set_texture swaps slot i.
+  DeviceAllocs geo, tables;
+  TriArrays tri;
+  mt_material *mtls = nullptr;  // dev.mtls and dev.texs for the scene's own writes
+  DevTexture *texs = nullptr;
   Buf<mt_light> d_lights;
   Buf<unsigned long long> d_counters;
   Buf<unsigned int> d_work;
@@ -335,17 +414,6 @@ struct mt_scene {
 };
 
 namespace {
-
-template <typename T>
-int upload(mt_scene *s, const T *host, size_t count, const T **dev_out) {
-  T *d = nullptr;
-  const size_t bytes = (count ? count : 1) * sizeof(T);
-  HIP_TRY(hipMalloc((void **)&d, bytes));
-  s->allocs.push_back(d);
-  if (count) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-  *dev_out = d;
-  return MT_OK;
-}
 
 // `kernel` over a flat range of n elements, one thread each in workgroups of 256; returns the launch's status
 template <typename... Params, typename... Args>
@@ -1095,8 +1163,7 @@ int check_ss(int ss, int image_w, int image_h) {
 int ensure_samples(mt_scene *s, size_t bytes) {
   if (s->d_samples.ensure(bytes) == MT_OK) return MT_OK;
   (void)hipGetLastError();
-  const std::string why = g_err;
-  return fail(MT_ERR_NOMEM, "no room for the %zu-byte sample buffer: %s", bytes, why.c_str());
+  return fail(MT_ERR_NOMEM, "no room for the %zu-byte sample buffer: %s", bytes, KeptError().text.c_str());
 }
 
 // resolve_kernel over n_tiles slots of the OUTPUT image's tile grid (a chunk: its one tile)
@@ -1193,8 +1260,7 @@ int mt_device_count(void) {
 
 void mt_scene_destroy(mt_scene *s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);  // (the buffers are freed with the scene)
-  for (void *p : s->allocs) (void)hipFree(p);
+  (void)hipSetDevice(s->device);  // (the uploads and the buffers are freed with the scene)
   for (hipEvent_t e : s->ev_stage) {
     if (e) (void)hipEventDestroy(e);
   }
@@ -1221,6 +1287,37 @@ static int check_texture(const mt_texture &t, int i) {
   return mt::check_texture(t, i, &err) ? MT_OK : fail(err);
 }
 
+// The arrays of a SceneLayout (mt_layout.h) in new allocations of `geo`, and what else of *dev the layout decides.  The
+// one place that knows which arrays a layout has: scene creation and a move both come through here.
+static int upload_derived(const SceneLayout &L, DeviceAllocs &geo, DevScene *dev) {
+  MT_TRY(geo.upload(L.groups, "the block boxes", &dev->grp_aabb32));
+  MT_TRY(geo.upload(L.supers, "the super boxes", &dev->sup_aabb32));
+  MT_TRY(geo.upload(L.subs, "the subtree boxes", &dev->sub_aabb32));
+  MT_TRY(geo.upload(L.hsr, "the walk's records", &dev->hs_rec));
+  MT_TRY(geo.upload(L.ll_tri, "the long lists", &dev->ll_tri));
+  MT_TRY(geo.upload(L.ll_exact, "the long lists", &dev->ll_exact));
+  MT_TRY(geo.upload(L.ll_box_q, "the long lists' boxes", &dev->ll_box_q));
+  MT_TRY(geo.upload(L.ll_grp_q, "the long lists' boxes", &dev->ll_grp_q));
+  MT_TRY(geo.upload(L.ll_sup_q, "the long lists' boxes", &dev->ll_sup_q));
+  MT_TRY(geo.upload(L.sl_box, "the short lists' boxes", &dev->sl_box32));
+  MT_TRY(geo.upload(L.recs, "the node records", &dev->nodes));
+  MT_TRY(geo.upload(L.tri_aabb, "the triangles' boxes", &dev->tri_aabb));
+  MT_TRY(geo.upload(L.tri_aabb32, "the triangles' boxes", &dev->tri_aabb32));
+  for (int k = 0; k < 3; k++) dev->bmax[k] = L.bmax[k];
+  dev->tree_depth = L.max_depth;
+  dev->scene_regular = L.regular ? 1 : 0;
+  return MT_OK;
+}
+
+// dev's per-triangle pointers are the scene's own `tri`
+static void show_tri_arrays(const TriArrays &tri, DevScene *dev) {
+  dev->tri_vertex = tri.vertex;
+  dev->tri_normal = tri.normal;
+  dev->tri_uvw = tri.uvw;
+  dev->tri_mtl = tri.mtl;
+  dev->tri_line = tri.line;
+}
+
 // The derived arrays (mt_layout.h) and the caller's own reach the device; the host keeps what the edit calls mirror.
 static int upload_layout(mt_scene *s, const mt_scene_desc *d, const SceneLayout &L) {
   HIP_TRY(hipSetDevice(d->device));
@@ -1229,51 +1326,40 @@ static int upload_layout(mt_scene *s, const mt_scene_desc *d, const SceneLayout 
   HIP_TRY(hipGetDeviceProperties(&prop, d->device));
   s->n_cu = prop.multiProcessorCount;
 
-  MT_TRY(upload(s, L.groups.data(), L.groups.size(), &s->dev.grp_aabb32));
-  MT_TRY(upload(s, L.supers.data(), L.supers.size(), &s->dev.sup_aabb32));
-  MT_TRY(upload(s, L.subs.data(), L.subs.size(), &s->dev.sub_aabb32));
-  MT_TRY(upload(s, L.hsr.data(), L.hsr.size(), &s->dev.hs_rec));
-  MT_TRY(upload(s, L.ll_tri.data(), L.ll_tri.size(), &s->dev.ll_tri));
-  MT_TRY(upload(s, L.ll_exact.data(), L.ll_exact.size(), &s->dev.ll_exact));
-  MT_TRY(upload(s, L.ll_box_q.data(), L.ll_box_q.size(), &s->dev.ll_box_q));
-  MT_TRY(upload(s, L.ll_grp_q.data(), L.ll_grp_q.size(), &s->dev.ll_grp_q));
-  MT_TRY(upload(s, L.ll_sup_q.data(), L.ll_sup_q.size(), &s->dev.ll_sup_q));
-  MT_TRY(upload(s, L.sl_box.data(), L.sl_box.size(), &s->dev.sl_box32));
-  MT_TRY(upload(s, L.recs.data(), L.recs.size(), &s->dev.nodes));
-  MT_TRY(upload(s, L.tri_aabb.data(), L.tri_aabb.size(), &s->dev.tri_aabb));
-  MT_TRY(upload(s, L.tri_aabb32.data(), L.tri_aabb32.size(), &s->dev.tri_aabb32));
-  for (int k = 0; k < 3; k++) s->dev.bmax[k] = L.bmax[k];
+  MT_TRY(upload_derived(L, s->geo, &s->dev));
   const size_t nt = (size_t)d->n_tris;
-  MT_TRY(upload(s, d->tri_vertex, nt * 9, &s->dev.tri_vertex));
-  MT_TRY(upload(s, d->tri_normal, nt * 9, &s->dev.tri_normal));
-  MT_TRY(upload(s, d->tri_uvw, nt * 9, &s->dev.tri_uvw));
-  MT_TRY(upload(s, d->tri_material, nt, &s->dev.tri_mtl));
+  MT_TRY(s->geo.upload(d->tri_vertex, nt * 9, "the triangles' vertices", &s->tri.vertex));
+  MT_TRY(s->geo.upload(d->tri_normal, nt * 9, "the triangles' normals", &s->tri.normal));
+  MT_TRY(s->geo.upload(d->tri_uvw, nt * 9, "the triangles' uvw", &s->tri.uvw));
+  MT_TRY(s->geo.upload(d->tri_material, nt, "the triangles' materials", &s->tri.mtl));
   s->tri_mtl_host = std::make_shared<const std::vector<int32_t>>(d->tri_material, d->tri_material + nt);
-  MT_TRY(upload(s, d->tri_line_no, nt, &s->dev.tri_line));
+  MT_TRY(s->geo.upload(d->tri_line_no, nt, "the triangles' line numbers", &s->tri.line));
+  show_tri_arrays(s->tri, &s->dev);
   if (d->tri_id != nullptr) {  // (mt_render_gbuffer's `prim` plane; not part of DevScene)
     s->tri_id_host.assign(d->tri_id, d->tri_id + nt);
     s->have_tri_id = true;
   }
-  MT_TRY(upload(s, d->materials, (size_t)d->n_materials, &s->dev.mtls));
-  s->n_materials = d->n_materials;
-  s->n_textures = d->n_textures;
-  if (d->n_materials > 0) s->mtls_host.assign(d->materials, d->materials + d->n_materials);
   std::vector<DevTexture> texs((size_t)d->n_textures);
-  for (int i = 0; i < d->n_textures; i++) {
+  for (int i = 0; i < d->n_textures; i++) {  // (first: texture i's texels are slot i of `tables`)
     const mt_texture &t = d->textures[i];
     const size_t texel_bytes = (t.format == MT_TEX_RGB8 ? 3 : 24);
     const uint8_t *dev_texels = nullptr;
-    MT_TRY(upload(s, (const uint8_t *)t.texels, (size_t)t.width * t.height * texel_bytes, &dev_texels));
+    MT_TRY(s->tables.upload((const uint8_t *)t.texels, (size_t)t.width * t.height * texel_bytes,
+                            ("texture " + std::to_string(i)).c_str(), &dev_texels));
     texs[i] = DevTexture{dev_texels, t.width, t.height, t.format, 0};
   }
-  MT_TRY(upload(s, texs.data(), texs.size(), &s->dev.texs));
+  MT_TRY(s->tables.upload(d->materials, (size_t)d->n_materials, "the materials", &s->mtls));
+  s->dev.mtls = s->mtls;
+  s->n_materials = d->n_materials;
+  s->n_textures = d->n_textures;
+  if (d->n_materials > 0) s->mtls_host.assign(d->materials, d->materials + d->n_materials);
+  MT_TRY(s->tables.upload(texs, "the texture table", &s->texs));
+  s->dev.texs = s->texs;
   s->texs_host = texs;
   s->tex_generation.assign(texs.size(), 0ull);
   s->dev.n_tris = d->n_tris;
   s->dev.n_nodes = d->n_nodes;
-  s->dev.tree_depth = L.max_depth;
   s->dev.force_mode = 0;
-  s->dev.scene_regular = L.regular ? 1 : 0;
   s->dev.pack_shift = pack_shift_for(d->n_tris, d->n_nodes);  // (MT_TUNE_PACKED_STACK = 0 switches it off)
   s->dev.n_lights = 0;
   s->dev.lights = nullptr;
@@ -1385,7 +1471,7 @@ int mt_scene_set_materials(mt_scene *s, const mt_material *materials, int n) {
   if (n == 0 || memcmp(s->mtls_host.data(), materials, (size_t)n * sizeof(mt_material)) == 0) return MT_OK;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the table while it changes
-  HIP_TRY(hipMemcpy(const_cast<mt_material *>(s->dev.mtls), materials, (size_t)n * sizeof(mt_material), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->mtls, materials, (size_t)n * sizeof(mt_material), hipMemcpyHostToDevice));
   s->mtls_host.assign(materials, materials + n);
   s->mtl_generation++;
   return MT_OK;
@@ -1412,28 +1498,17 @@ int mt_scene_set_texture(mt_scene *s, int index, const mt_texture *tex) {
   MT_TRY(check_texture(*tex, index));
   HIP_TRY(hipSetDevice(s->device));
   const size_t bytes = (size_t)tex->width * (size_t)tex->height * (tex->format == MT_TEX_RGB8 ? 3 : 24);
-  // the new texels next to the old ones: until the entry is patched the scene is what it was
-  void *fresh = nullptr;
-  const hipError_t e = hipMalloc(&fresh, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of texture %d", bytes, index);
-    return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for texture %d failed: %s", bytes, index, hipGetErrorString(e));
-  }
+  // the new texels next to the old ones, in a list of their own: until the entry is patched the scene is what it was
+  DeviceAllocs aside;
+  uint8_t *fresh = nullptr;
+  MT_TRY(aside.alloc<uint8_t>(bytes, ("texture " + std::to_string(index)).c_str(), &fresh));
   const DevTexture entry{fresh, tex->width, tex->height, tex->format, 0};
-  DevTexture *slot = const_cast<DevTexture *>(s->dev.texs) + index;
   // (hipDeviceSynchronize: no kernel of an earlier call reads the entry or the old texels while they change)
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(fresh, tex->texels, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(slot, &entry, sizeof entry, hipMemcpyHostToDevice) != hipSuccess) {
-    const hipError_t why = hipGetLastError();
-    (void)hipFree(fresh);
-    return fail(MT_ERR_HIP, "uploading texture %d failed: %s", index, hipGetErrorString(why));
+      hipMemcpy(s->texs + index, &entry, sizeof entry, hipMemcpyHostToDevice) != hipSuccess) {
+    return fail(MT_ERR_HIP, "uploading texture %d failed: %s", index, hipGetErrorString(hipGetLastError()));
   }
-  void *old = const_cast<void *>(s->texs_host[(size_t)index].texels);
-  for (void *&a : s->allocs) {
-    if (a == old) a = fresh;  // (the scene's uploads are freed with it)
-  }
-  (void)hipFree(old);
+  s->tables.swap_slot((size_t)index, aside, 0);  // (the old texels are freed with `aside`)
   s->texs_host[(size_t)index] = entry;
   s->tex_generation[(size_t)index]++;
   s->mtl_generation++;  // every ray tree of the scene is stale, as after a material edit
@@ -1477,7 +1552,7 @@ int mt_scene_set_triangle_materials(mt_scene *s, const int32_t *tri_material, in
   if (n == 0 || memcmp(s->tri_mtl_host->data(), tri_material, (size_t)n * sizeof(int32_t)) == 0) return MT_OK;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the array while it changes
-  HIP_TRY(hipMemcpy(const_cast<int32_t *>(s->dev.tri_mtl), tri_material, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->tri.mtl, tri_material, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
   s->tri_mtl_host = std::make_shared<const std::vector<int32_t>>(tri_material, tri_material + n);
   s->asg_generation++;
   s->mtl_generation++;  // every ray tree of the scene is stale, as after a material edit
@@ -1507,8 +1582,7 @@ int check_triangle_attr_args(const mt_scene *s, const void *attr, int n, int whi
 int attr_nomem(int rc, size_t bytes, const char *what) {
   if (rc == MT_OK) return MT_OK;
   (void)hipGetLastError();
-  const std::string why = g_err;
-  return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s: %s", bytes, what, why.c_str());
+  return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s: %s", bytes, what, KeptError().text.c_str());
 }
 
 // mt_scene_set_triangle_normals (which = 0) / _uvw (1): the array staged on the device, tri_attr_stamp_kernel, and --
@@ -1542,7 +1616,7 @@ int set_triangle_attr(mt_scene *s, const double *attr, int n, int which) {
   MT_TRY(call.begin(false));
   TriAttrStampArgs A{};
   A.staged = s->d_attr_stage;
-  A.live = const_cast<double *>(which == 0 ? s->dev.tri_normal : s->dev.tri_uvw);
+  A.live = which == 0 ? s->tri.normal : s->tri.uvw;
   A.stamp = s->d_attr_stamp[which];
   A.n_tris = (uint32_t)n;
   A.generation = s->attr_generation[which] + 1u;
@@ -2722,16 +2796,6 @@ struct mt_raytree {
 
 namespace {
 
-// hipMalloc for a tree: what does not fit is MT_ERR_NOMEM
-int raytree_malloc(void **p, size_t bytes, const char *what) {
-  const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-  if (e == hipSuccess) return MT_OK;
-  (void)hipGetLastError();
-  *p = nullptr;
-  if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s", bytes, what);
-  return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
-}
-
 // One allocation holds a layer's planes, each at a multiple of 256 bytes: the planes of layer k with n rays and n_l
 // lights laid out from `base` (nullptr: only the size is wanted).  Returns the bytes.  The uvw plane of a tree that
 // keeps one comes last, [n][3] doubles at a multiple of 256 bytes: without it a layer is laid out as it always was.
@@ -2766,7 +2830,7 @@ int raytree_alloc_layer(mt_raytree *t, int k, size_t n) {
   const size_t total = raytree_carve_layer(nullptr, n_l, k, n, t->keep_uvw, t->keep_tri, &L);
   char what[64];
   snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k, n);
-  MT_TRY(raytree_malloc(&t->alloc[k], total, what));
+  MT_TRY(device_malloc(&t->alloc[k], total, what));
   (void)raytree_carve_layer(t->alloc[k], n_l, k, n, t->keep_uvw, t->keep_tri, &L);
   t->info.bytes += total;
   t->info.n_rays[k] = (int64_t)n;
@@ -2915,12 +2979,12 @@ int raytree_read_counters(mt_scene *s, hipStream_t stream) {
 // Synchronises: no tracing kernel is launched before the kernel's count of refused rays has been read.
 int raytree_import_rays(mt_raytree *t, const mt_ray_list *rays, bool on_device, hipStream_t stream) {
   const size_t n = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
-  MT_TRY(raytree_malloc((void **)&t->d_bad, 2 * sizeof(unsigned int), "the ray tree's count of refused rays"));
+  MT_TRY(device_malloc((void **)&t->d_bad, 2 * sizeof(unsigned int), "the ray tree's count of refused rays"));
   RayTreeRaysArgs A{};
   A.ray = rays->ray; A.in_object = rays->in_object; A.coef = rays->coef;
   void *staged = nullptr;
   if (!on_device) {  // one allocation: the rays, the coefficients, the in_object bytes
-    MT_TRY(raytree_malloc(&staged, n * 48 + n * 8 + n, "the caller's ray list"));
+    MT_TRY(device_malloc(&staged, n * 48 + n * 8 + n, "the caller's ray list"));
     char *at = (char *)staged;
     A.ray = (const double *)at;
     A.coef = rays->coef ? (const double *)(at + n * 48) : nullptr;
@@ -3011,7 +3075,7 @@ int raytree_build(mt_raytree *t, const mt_ray_list *rays, bool on_device, mt_sta
   if (npx >= 0x80000000ull) return fail(MT_ERR_UNSUPPORTED, "layer 0 of the ray tree would have %zu rays (2^31 or more)", npx);
   HIP_TRY(hipEventCreate(&t->ev0));
   HIP_TRY(hipEventCreate(&t->ev1));
-  MT_TRY(raytree_malloc((void **)&t->d_count, sizeof(unsigned long long), "the ray tree's child count"));
+  MT_TRY(device_malloc((void **)&t->d_count, sizeof(unsigned long long), "the ray tree's child count"));
   MT_TRY(raytree_alloc_layer(t, 0, npx));
   MT_TRY(call.begin(true));
   if (rays) {
@@ -3143,9 +3207,9 @@ mt_raytree *mt_raytree_create(mt_scene *s, const mt_sensor *sensor, int image_w,
   t->info.max_depth = max_depth;
   const int rc = raytree_build(t, nullptr, false, stats);
   if (rc != MT_OK) {
-    const std::string why = g_err;  // (the text survives the clean-up)
+    const KeptError why;
     mt_raytree_destroy(t);
-    (void)fail(rc, "%s", why.c_str());
+    (void)why.fail_again(rc);
     return nullptr;
   }
   return t;
@@ -3166,9 +3230,9 @@ int raytree_create_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, mt_
   t->info.from_rays = 1;
   const int rc = raytree_build(t, rays, on_device, stats);
   if (rc != MT_OK) {
-    const std::string why = g_err;  // (the text survives the clean-up)
+    const KeptError why;
     mt_raytree_destroy(t);
-    return fail(rc, "%s", why.c_str());
+    return why.fail_again(rc);
   }
   *out = t;
   return MT_OK;
@@ -3277,8 +3341,8 @@ int raytree_shade_host(mt_raytree *t, const mt_light *lights, int n_lights, uint
   HIP_TRY(hipSetDevice(t->scene->device));
   const size_t npx = (size_t)t->info.chunk_w * (size_t)t->info.chunk_h;
   const hipStream_t stream = call.stream;
-  if (out_rgb && !t->d_rgb) MT_TRY(raytree_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
-  if (out_color && !t->d_out_color) MT_TRY(raytree_malloc((void **)&t->d_out_color, npx * 24, "the ray tree's colours"));
+  if (out_rgb && !t->d_rgb) MT_TRY(device_malloc((void **)&t->d_rgb, npx * 3, "the ray tree's bitmap"));
+  if (out_color && !t->d_out_color) MT_TRY(device_malloc((void **)&t->d_out_color, npx * 24, "the ray tree's colours"));
   MT_TRY(call.begin(false));  // (no ray, no traversal: every work counter is zero)
   MT_TRY(launch_raytree_shade(t, lights, n_lights, out_rgb ? t->d_rgb : nullptr, out_color ? t->d_out_color : nullptr, stream));
   MT_TRY(call.mark_end());
@@ -3309,9 +3373,9 @@ int mt_trace_rays(mt_scene *s, const mt_ray_list *rays, int max_depth, double *o
   const std::vector<mt_light> lights = s->lights_host;  // the scene's current lights
   mt_stats shaded{};
   const int rc = raytree_shade_host(t, lights.data(), (int)lights.size(), out_rgb, out_color, stats ? &shaded : nullptr);
-  const std::string why = rc != MT_OK ? g_err : std::string();
+  const KeptError why;
   mt_raytree_destroy(t);
-  if (rc != MT_OK) return fail(rc, "%s", why.c_str());
+  if (rc != MT_OK) return why.fail_again(rc);
   if (stats) {
     *stats = made;
     stats->kernel_ms = made.kernel_ms + shaded.kernel_ms;
@@ -3439,7 +3503,7 @@ int raytree_scratch(void **p, size_t *cap, size_t bytes, const char *what) {
     *p = nullptr;
     *cap = 0;
   }
-  MT_TRY(raytree_malloc(p, bytes, what));
+  MT_TRY(device_malloc(p, bytes, what));
   *cap = bytes;
   return MT_OK;
 }
@@ -3448,7 +3512,7 @@ int raytree_scratch(void **p, size_t *cap, size_t bytes, const char *what) {
 int raytree_upload_albedo_changed(mt_raytree *t, const MaterialDiff &D, hipStream_t stream) {
   const size_t n_mtl = (size_t)t->scene->n_materials;
   if (!t->d_albedo_changed) {
-    MT_TRY(raytree_malloc((void **)&t->d_albedo_changed, n_mtl, "the ray tree's material flags"));
+    MT_TRY(device_malloc((void **)&t->d_albedo_changed, n_mtl, "the ray tree's material flags"));
   }
   HIP_TRY(hipMemcpyAsync(t->d_albedo_changed, D.albedo_changed.data(), n_mtl, hipMemcpyHostToDevice, stream));
   return MT_OK;
@@ -3548,7 +3612,7 @@ int raytree_regrow(mt_raytree *t, const MaterialDiff &D, mt_raytree_regrow_info 
     const size_t total = raytree_carve_layer(nullptr, n_l, k + 1, n1, t->keep_uvw, t->keep_tri, &NL[k + 1]);
     char what[64];
     snprintf(what, sizeof what, "layer %d of the ray tree (%zu rays)", k + 1, n1);
-    if (const int rc = raytree_malloc(&alloc[k + 1], total, what)) return release(rc);
+    if (const int rc = device_malloc(&alloc[k + 1], total, what)) return release(rc);
     (void)raytree_carve_layer(alloc[k + 1], n_l, k + 1, n1, t->keep_uvw, t->keep_tri, &NL[k + 1]);
     const int to = (k + 1) & 1;
     if (const int rc = raytree_scratch((void **)&t->d_src[to], &t->src_cap[to], n1 * 4, "the ray tree's regrow indices")) {
@@ -3738,7 +3802,7 @@ int raytree_check_pass(mt_raytree *t, const MaterialDiff &D, hipStream_t stream,
   const mt_scene *s = t->scene;
   const mt_raytree_desc &I = t->info;
   if (!t->d_mismatch) {
-    MT_TRY(raytree_malloc((void **)&t->d_mismatch, 2 * sizeof(unsigned long long), "the ray tree's mismatch count"));
+    MT_TRY(device_malloc((void **)&t->d_mismatch, 2 * sizeof(unsigned long long), "the ray tree's mismatch count"));
   }
   HIP_TRY(hipMemsetAsync(t->d_mismatch, 0, sizeof(unsigned long long), stream));
   HIP_TRY(hipMemsetAsync(t->d_mismatch + 1, 0xff, sizeof(unsigned long long), stream));
@@ -3814,7 +3878,7 @@ int raytree_take_materials(mt_raytree *t, mt_stats *stats, bool regrow, mt_raytr
     const hipStream_t stream = call.stream;
     if (attrs) {
       if (!t->d_attr_count) {
-        MT_TRY(raytree_malloc((void **)&t->d_attr_count, sizeof attr_count, "the ray tree's attribute counts"));
+        MT_TRY(device_malloc((void **)&t->d_attr_count, sizeof attr_count, "the ray tree's attribute counts"));
       }
       HIP_TRY(hipMemsetAsync(t->d_attr_count, 0, sizeof attr_count, stream));
       HIP_TRY(hipMemsetAsync(t->d_attr_count + kRayTreeAttrFirst, 0xff, sizeof(unsigned long long), stream));
@@ -4190,8 +4254,7 @@ int build_grow(Buf<T> &b, size_t keep, size_t want, const char *what, hipStream_
   MT_TRY(attr_nomem(grown.ensure(want * sizeof(T)), want * sizeof(T), what));
   if (keep) HIP_TRY(hipMemcpyAsync(grown.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  std::swap(b.p, grown.p);
-  std::swap(b.bytes, grown.bytes);
+  b.swap(grown);
   return MT_OK;
 }
 
@@ -4358,6 +4421,18 @@ int octree_read_arrays(int32_t n_nodes, int32_t n_tris, int32_t depth, const dou
   return MT_OK;
 }
 
+// *out = the tree of t (mt_host_tree.h); *box_add, where wanted, the build's boxes of the triangles in add order
+int read_host_tree(const mt_octree *t, HostTree *out, std::vector<double> *box_add) {
+  mt_octree_arrays a = out->room_for(t->n_nodes, t->n_tris, box_add);
+  HIP_TRY(hipSetDevice(t->device));
+  MT_TRY(octree_read_arrays(t->n_nodes, t->n_tris, t->depth, t->d_aabb, t->d_center, t->d_first_child, t->d_prim_begin,
+                            t->d_prim_count, t->d_tri_id, t->d_tri_aabb, &a));
+  out->n_nodes = a.n_nodes;
+  out->n_tris = a.n_tris;
+  out->depth = a.depth;
+  return MT_OK;
+}
+
 }  // namespace
 
 void mt_octree_destroy(mt_octree *t) {
@@ -4375,10 +4450,10 @@ mt_octree *mt_octree_build(int device, int n_tris, const double *tri_vertex, mt_
   t->n_tris = n_tris;
   const int rc = octree_build(t, tri_vertex);
   if (rc != MT_OK) {
-    const std::string why = g_err;  // (the text survives the clean-up)
+    const KeptError why;
     (void)hipGetLastError();
     mt_octree_destroy(t);
-    (void)fail(rc, "%s", why.c_str());
+    (void)why.fail_again(rc);
     return nullptr;
   }
   if (info) *info = t->info;
@@ -4426,24 +4501,16 @@ mt_scene *mt_scene_create_triangles(const mt_triangle_desc *d, mt_build_info *in
   mt_octree *t = mt_octree_build(d->device, d->n_tris, d->tri_vertex, &built);
   if (!t) return nullptr;
   // the tree on the host, and the triangles gathered into its stream order
-  const size_t nn = (size_t)t->n_nodes, nt = (size_t)d->n_tris;
-  std::vector<double> node_aabb(nn * 6), node_center(nn * 3), box_add(nt * 6);
-  std::vector<int32_t> first_child(nn), prim_begin(nn), prim_count(nn), tri_id(nt ? nt : 1);  // (never NULL: the scene has a tri_id)
-  mt_octree_arrays a{};
-  a.node_aabb = node_aabb.data();
-  a.node_center = node_center.data();
-  a.first_child = first_child.data();
-  a.prim_begin = prim_begin.data();
-  a.prim_count = prim_count.data();
-  a.tri_id = tri_id.data();
-  a.tri_aabb = box_add.data();
-  const int rc = mt_octree_read(t, &a);
+  const size_t nt = (size_t)d->n_tris;
+  HostTree tree;
+  std::vector<double> box_add;
+  const int rc = read_host_tree(t, &tree, &box_add);
   mt_octree_destroy(t);
   if (rc != MT_OK) return nullptr;
   std::vector<double> vertex(nt * 9), normal(nt * 9), uvw(nt * 9), box(nt * 6);
   std::vector<int32_t> material(nt), line_no(nt);
   for (size_t s = 0; s < nt; s++) {
-    const size_t i = (size_t)tri_id[s];
+    const size_t i = (size_t)tree.tri_id[s];
     memcpy(&vertex[s * 9], d->tri_vertex + i * 9, 72);
     memcpy(&normal[s * 9], d->tri_normal + i * 9, 72);
     memcpy(&uvw[s * 9], d->tri_uvw + i * 9, 72);
@@ -4451,28 +4518,14 @@ mt_scene *mt_scene_create_triangles(const mt_triangle_desc *d, mt_build_info *in
     material[s] = d->tri_material[i];
     line_no[s] = d->tri_line_no[i];
   }
-  mt_scene_desc sd;
-  memset(&sd, 0, sizeof sd);
-  sd.struct_size = sizeof sd;
-  sd.abi_version = MT_ABI_VERSION;
-  sd.device = d->device;
-  sd.n_nodes = a.n_nodes;
-  sd.n_tris = d->n_tris;
-  sd.n_materials = d->n_materials;
-  sd.n_textures = d->n_textures;
-  sd.tree_depth = a.depth;
-  sd.node_aabb = node_aabb.data();
-  sd.node_center = node_center.data();
-  sd.node_first_child = first_child.data();
-  sd.node_prim_begin = prim_begin.data();
-  sd.node_prim_count = prim_count.data();
+  mt_scene_desc sd = new_scene_desc(d->device, d->n_tris, d->n_materials, d->n_textures);
+  describe_tree(tree, &sd);
   sd.tri_vertex = vertex.data();
   sd.tri_normal = normal.data();
   sd.tri_uvw = uvw.data();
   sd.tri_aabb = box.data();
   sd.tri_material = material.data();
   sd.tri_line_no = line_no.data();
-  sd.tri_id = tri_id.data();
   sd.materials = d->materials;
   sd.textures = d->textures;
   mt_scene *s = mt_scene_create(&sd);
@@ -4516,272 +4569,215 @@ int mt_scene_read_tree(const mt_scene *s, mt_octree_arrays *out) {
 // ---- triangles moved in place (mt_build.h's move_* kernels, mt_move.h's bookkeeping) ---------------------------------
 namespace {
 
-// Device allocations made aside while a move is under way: freed with this object unless the scene has taken them.
-struct MoveAllocs {
-  std::vector<void *> p;
-  MoveAllocs() = default;
-  MoveAllocs(const MoveAllocs &) = delete;
-  MoveAllocs &operator=(const MoveAllocs &) = delete;
-  ~MoveAllocs() {
-    for (void *q : p) (void)hipFree(q);
-  }
-};
-
-extern "C++" {
-
-// `count` elements of new device memory (at least one byte), owned by `A`; what does not fit is MT_ERR_NOMEM
-template <typename T>
-int move_alloc(MoveAllocs &A, size_t count, const char *what, T **out) {
-  const size_t bytes = (count ? count : 1) * sizeof(T);
-  void *d = nullptr;
-  const hipError_t e = hipMalloc(&d, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(MT_ERR_NOMEM, "no room for the %zu bytes of %s", bytes, what);
-    return fail(MT_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
-  }
-  A.p.push_back(d);
-  *out = (T *)d;
-  return MT_OK;
-}
-
-// upload() into an allocation of `A` instead of the scene's
-template <typename T>
-int move_upload(MoveAllocs &A, const std::vector<T> &host, const char *what, const T **out) {
-  T *d = nullptr;
-  MT_TRY(move_alloc(A, host.size(), what, &d));
-  if (!host.empty()) HIP_TRY(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = d;
-  return MT_OK;
-}
-
-}  // extern "C++"
-
 double ms_since(const std::chrono::steady_clock::time_point &t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// Steps 1 .. 6 of mt_scene_set_triangle_vertices for a checked list of n_idx >= 1 triangles.  Until the swap at the end
-// everything is built aside (locals that free themselves): a return before it leaves the scene exactly as it was.
-int move_triangles(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, mt_build_info *info) {
-  const auto w0 = std::chrono::steady_clock::now();
-  const int32_t n = s->dev.n_tris;
-  const size_t nt = (size_t)n, ni = (size_t)n_idx;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the scene while it is taken apart
-  const hipStream_t stream = nullptr;
-  // ---- 1. + 2. the live vertices in add order, the listed triangles written over them
+// What the steps of a move hand on to one another.  Everything in it is built aside and frees itself: until move_swap
+// nothing of the scene is written, and a return leaves the scene exactly as it was.
+struct Move {
+  int32_t n = 0;  // the scene's triangles
+  // 1. + 2. the vertices in add order with the listed ones written over them; add index -> old stream position; and the
+  // step's own inputs
   Buf<double> d_stage, d_listed;
-  Buf<int32_t> d_old_id, d_old_pos, d_idx;
+  Buf<int32_t> d_old_pos, d_old_id, d_idx;
   Buf<unsigned int> d_changed;
-  MT_TRY(build_room(d_stage, nt * 9, "the staged vertices"));
-  MT_TRY(build_room(d_listed, ni * 9, "the listed vertices"));
-  MT_TRY(build_room(d_old_id, nt, "the old tri_id"));
-  MT_TRY(build_room(d_old_pos, nt, "the old stream positions"));
-  MT_TRY(build_room(d_idx, ni, "the index list"));
-  MT_TRY(build_room(d_changed, 1, "the changed count"));
-  HIP_TRY(hipMemcpyAsync(d_old_id, s->tri_id_host.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_idx, add_idx, ni * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_listed, vertices, ni * 72, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemsetAsync(d_old_pos, 0xff, nt * sizeof(int32_t), stream));
-  HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), stream));
-  HIP_TRY(launch_flat(move_unscatter_kernel, nt, stream, s->dev.tri_vertex, (const int32_t *)d_old_id.p, (uint32_t)n, d_stage.p,
-                      d_old_pos.p));
-  HIP_TRY(launch_flat(move_overwrite_kernel, ni, stream, (const int32_t *)d_idx.p, (const double *)d_listed.p, (uint32_t)n_idx,
-                      (uint32_t)n, d_stage.p, d_changed.p));
-  unsigned int changed = 0;
-  HIP_TRY(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (changed == 0) return MT_OK;  // the listed vertices are the live ones, bit for bit
-  // ---- 3. the tree, from the staging array
-  auto t0 = std::chrono::steady_clock::now();
-  double part_ms[MT_MOVE_TIMES] = {};
-  std::unique_ptr<mt_octree, void (*)(mt_octree *)> tree(new mt_octree(), mt_octree_destroy);
-  tree->device = s->device;
-  tree->n_tris = n;
-  {
-    const int rc = octree_build(tree.get(), nullptr, d_stage.p);
-    if (rc != MT_OK) {
-      const std::string why = g_err;  // (the text survives the clean-up)
-      (void)hipGetLastError();
-      return fail(rc, "%s", why.c_str());
-    }
-  }
-  part_ms[MT_MOVE_MS_BUILD] = ms_since(t0);
-  // ---- 4. the per-triangle arrays in the new order, in new allocations
-  t0 = std::chrono::steady_clock::now();
-  MoveAllocs fresh;
-  Buf<uint32_t> d_stamp_new[2];
+  // 3.
+  std::unique_ptr<mt_octree, void (*)(mt_octree *)> tree{nullptr, mt_octree_destroy};
+  // 4. the scene's next `geo` and `tri`, the boxes in stream order, the scene's next stamp planes and tri_id
+  DeviceAllocs geo;
+  TriArrays tri;
   Buf<double> d_box_stream;
-  Buf<int32_t> d_tri_id_new;
+  Buf<uint32_t> d_stamp[2];
+  Buf<int32_t> d_tri_id;
+  // 5. the tree, the stream-order boxes and vertices on the host; the next mirrors, layout and DevScene
+  HostTree host;
+  std::vector<double> box, vertex;
+  MovedMirrors mirrors;
+  std::shared_ptr<const std::vector<int32_t>> tri_mtl;
+  SceneLayout L;
+  DevScene dev{};
+};
+
+// 1. + 2.: the live vertices in add order, the listed triangles written over them.  *changed: the triangles of the list
+// whose vertices are not the live ones, bit for bit.
+int move_stage(const mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, Move &M, unsigned int *changed) {
+  const size_t nt = (size_t)M.n, ni = (size_t)n_idx;
+  const hipStream_t stream = nullptr;
+  MT_TRY(build_room(M.d_stage, nt * 9, "the staged vertices"));
+  MT_TRY(build_room(M.d_listed, ni * 9, "the listed vertices"));
+  MT_TRY(build_room(M.d_old_id, nt, "the old tri_id"));
+  MT_TRY(build_room(M.d_old_pos, nt, "the old stream positions"));
+  MT_TRY(build_room(M.d_idx, ni, "the index list"));
+  MT_TRY(build_room(M.d_changed, 1, "the changed count"));
+  HIP_TRY(hipMemcpyAsync(M.d_old_id, s->tri_id_host.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(M.d_idx, add_idx, ni * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(M.d_listed, vertices, ni * 72, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(M.d_old_pos, 0xff, nt * sizeof(int32_t), stream));
+  HIP_TRY(hipMemsetAsync(M.d_changed, 0, sizeof(unsigned int), stream));
+  HIP_TRY(launch_flat(move_unscatter_kernel, nt, stream, s->dev.tri_vertex, (const int32_t *)M.d_old_id.p, (uint32_t)M.n,
+                      M.d_stage.p, M.d_old_pos.p));
+  HIP_TRY(launch_flat(move_overwrite_kernel, ni, stream, (const int32_t *)M.d_idx.p, (const double *)M.d_listed.p, (uint32_t)n_idx,
+                      (uint32_t)M.n, M.d_stage.p, M.d_changed.p));
+  HIP_TRY(hipMemcpyAsync(changed, M.d_changed, sizeof *changed, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return MT_OK;
+}
+
+// 3.: the tree, from the staging array
+int move_build(const mt_scene *s, Move &M) {
+  M.tree.reset(new mt_octree());
+  M.tree->device = s->device;
+  M.tree->n_tris = M.n;
+  const int rc = octree_build(M.tree.get(), nullptr, M.d_stage.p);
+  if (rc != MT_OK) (void)hipGetLastError();  // (the refusal's text stands: nothing here writes g_err)
+  return rc;
+}
+
+// 4.: the per-triangle arrays in the new order, in new allocations
+int move_regather(const mt_scene *s, Move &M) {
+  const size_t nt = (size_t)M.n;
+  const hipStream_t stream = nullptr;
+  const mt_octree *tree = M.tree.get();
   MoveArrays was{}, now{};
-  was.vertex = const_cast<double *>(s->dev.tri_vertex);
-  was.normal = const_cast<double *>(s->dev.tri_normal);
-  was.uvw = const_cast<double *>(s->dev.tri_uvw);
-  was.aabb = const_cast<double *>(s->dev.tri_aabb);
-  was.mtl = const_cast<int32_t *>(s->dev.tri_mtl);
-  was.line = const_cast<int32_t *>(s->dev.tri_line);
-  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' vertices", &now.vertex));
-  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' normals", &now.normal));
-  MT_TRY(move_alloc(fresh, nt * 9, "the triangles' uvw", &now.uvw));
-  MT_TRY(move_alloc(fresh, nt, "the triangles' materials", &now.mtl));
-  MT_TRY(move_alloc(fresh, nt, "the triangles' line numbers", &now.line));
-  MT_TRY(build_room(d_box_stream, nt * 6, "the triangles' boxes"));
-  now.aabb = d_box_stream;
+  was.vertex = s->tri.vertex;
+  was.normal = s->tri.normal;
+  was.uvw = s->tri.uvw;
+  was.mtl = s->tri.mtl;
+  was.line = s->tri.line;  // (was.aabb stays NULL: the boxes come from the build, not from the old scene)
+  MT_TRY(M.geo.alloc<double>(nt * 9, "the triangles' vertices", &now.vertex));
+  MT_TRY(M.geo.alloc<double>(nt * 9, "the triangles' normals", &now.normal));
+  MT_TRY(M.geo.alloc<double>(nt * 9, "the triangles' uvw", &now.uvw));
+  MT_TRY(M.geo.alloc<int32_t>(nt, "the triangles' materials", &now.mtl));
+  MT_TRY(M.geo.alloc<int32_t>(nt, "the triangles' line numbers", &now.line));
+  M.tri = TriArrays{now.vertex, now.normal, now.uvw, now.mtl, now.line};
+  MT_TRY(build_room(M.d_box_stream, nt * 6, "the triangles' boxes"));
+  now.aabb = M.d_box_stream;
   for (int w = 0; w < 2; w++) {
     if (s->d_attr_stamp[w].p == nullptr) continue;
-    MT_TRY(build_room(d_stamp_new[w], nt, "the triangles' stamp plane"));
+    MT_TRY(build_room(M.d_stamp[w], nt, "the triangles' stamp plane"));
     was.stamp[w] = s->d_attr_stamp[w];
-    now.stamp[w] = d_stamp_new[w];
+    now.stamp[w] = M.d_stamp[w];
   }
   if (s->d_tri_id.p != nullptr) {  // (the G-buffer's `prim` plane reads it)
-    MT_TRY(build_room(d_tri_id_new, nt, "the scene's tri_id"));
-    HIP_TRY(hipMemcpyAsync(d_tri_id_new, tree->d_tri_id, nt * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    MT_TRY(build_room(M.d_tri_id, nt, "the scene's tri_id"));
+    HIP_TRY(hipMemcpyAsync(M.d_tri_id, tree->d_tri_id, nt * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
   }
-  HIP_TRY(launch_flat(move_regather_kernel, nt, stream, was, now, (const double *)d_stage.p, (const double *)tree->d_tri_aabb.p,
-                      (const int32_t *)tree->d_tri_id.p, (const int32_t *)d_old_pos.p, (uint32_t)n));
+  HIP_TRY(launch_flat(move_regather_kernel, nt, stream, was, now, (const double *)M.d_stage.p, (const double *)tree->d_tri_aabb.p,
+                      (const int32_t *)tree->d_tri_id.p, (const int32_t *)M.d_old_pos.p, (uint32_t)M.n));
   HIP_TRY(hipStreamSynchronize(stream));
-  part_ms[MT_MOVE_MS_REGATHER] = ms_since(t0);
-  // ---- 5. the tree, the stream-order boxes and vertices on the host; the checks and the derived arrays of a new scene
-  t0 = std::chrono::steady_clock::now();
-  const size_t nn = (size_t)tree->n_nodes;
-  std::vector<double> node_aabb(nn * 6), node_center(nn * 3), box(nt * 6), vertex(nt * 9);
-  std::vector<int32_t> first_child(nn), prim_begin(nn), prim_count(nn), new_tri_id(nt);
-  mt_octree_arrays a{};
-  a.node_aabb = node_aabb.data();
-  a.node_center = node_center.data();
-  a.first_child = first_child.data();
-  a.prim_begin = prim_begin.data();
-  a.prim_count = prim_count.data();
-  a.tri_id = new_tri_id.data();
-  MT_TRY(octree_read_arrays(tree->n_nodes, n, tree->depth, tree->d_aabb, tree->d_center, tree->d_first_child, tree->d_prim_begin,
-                            tree->d_prim_count, tree->d_tri_id, tree->d_tri_aabb, &a));
-  HIP_TRY(hipMemcpy(box.data(), d_box_stream, nt * 48, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(vertex.data(), now.vertex, nt * 72, hipMemcpyDeviceToHost));
-  part_ms[MT_MOVE_MS_READBACK] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-  MovedMirrors mirrors;
+  return MT_OK;
+}
+
+// 5., the device's half: the tree, the stream-order boxes and vertices on the host
+int move_readback(Move &M) {
+  const size_t nt = (size_t)M.n;
+  M.box.resize(nt * 6);
+  M.vertex.resize(nt * 9);
+  MT_TRY(read_host_tree(M.tree.get(), &M.host, nullptr));
+  HIP_TRY(hipMemcpy(M.box.data(), M.d_box_stream, nt * 48, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(M.vertex.data(), M.tri.vertex, nt * 72, hipMemcpyDeviceToHost));
+  return MT_OK;
+}
+
+// 5., the host's half: the mirrors in the new order, then the checks and the derived arrays of a new scene
+int move_derive(const mt_scene *s, Move &M) {
   std::vector<int32_t> from;
   MoveError merr;
-  if (!move_mirrors(s->tri_id_host, new_tri_id.data(), *s->tri_mtl_host, s->attr_stamp_host, &mirrors, &from, &merr)) return fail(merr);
-  auto tri_mtl_new = std::make_shared<const std::vector<int32_t>>(std::move(mirrors.tri_mtl));  // (trees hold the old one)
+  if (!move_mirrors(s->tri_id_host, M.host.tri_id.data(), *s->tri_mtl_host, s->attr_stamp_host, &M.mirrors, &from, &merr)) {
+    return fail(merr);
+  }
+  M.tri_mtl = std::make_shared<const std::vector<int32_t>>(std::move(M.mirrors.tri_mtl));  // (trees hold the old one)
   // The description of the new scene as mt_scene_create would get it.  check_scene_desc and derive_layout read the node
   // arrays, tri_vertex, tri_aabb, tri_material and the material / texture tables; of tri_normal, tri_uvw, tri_line_no
   // and the textures' texels they only ask that they are there (the scene keeps no host copy of them: stand-ins).
   std::vector<mt_texture> texs((size_t)s->n_textures);
   for (size_t i = 0; i < texs.size(); i++) {
     const DevTexture &t = s->texs_host[i];
-    texs[i].width = t.width;
-    texs[i].height = t.height;
-    texs[i].format = t.format;
-    texs[i].texels = t.texels;
+    texs[i] = mt_texture{t.width, t.height, t.format, 0, t.texels};
   }
-  mt_scene_desc sd;
-  memset(&sd, 0, sizeof sd);
-  sd.struct_size = sizeof sd;
-  sd.abi_version = MT_ABI_VERSION;
-  sd.device = s->device;
-  sd.n_nodes = tree->n_nodes;
-  sd.n_tris = n;
-  sd.n_materials = s->n_materials;
-  sd.n_textures = s->n_textures;
-  sd.tree_depth = tree->depth;
-  sd.node_aabb = node_aabb.data();
-  sd.node_center = node_center.data();
-  sd.node_first_child = first_child.data();
-  sd.node_prim_begin = prim_begin.data();
-  sd.node_prim_count = prim_count.data();
-  sd.tri_vertex = vertex.data();
-  sd.tri_normal = vertex.data();  // (stand-in)
-  sd.tri_uvw = vertex.data();     // (stand-in)
-  sd.tri_aabb = box.data();
-  sd.tri_material = tri_mtl_new->data();
-  sd.tri_line_no = new_tri_id.data();  // (stand-in)
-  sd.tri_id = new_tri_id.data();
+  mt_scene_desc sd = new_scene_desc(s->device, M.n, s->n_materials, s->n_textures);
+  describe_tree(M.host, &sd);
+  sd.tri_vertex = M.vertex.data();
+  sd.tri_normal = M.vertex.data();  // (stand-in)
+  sd.tri_uvw = M.vertex.data();     // (stand-in)
+  sd.tri_aabb = M.box.data();
+  sd.tri_material = M.tri_mtl->data();
+  sd.tri_line_no = M.host.tri_id.data();  // (stand-in)
   sd.materials = s->mtls_host.data();
   sd.textures = texs.data();
   std::vector<int> depth_of;
   int max_depth = 0;
   LayoutError lerr;
   if (!check_scene_desc(sd, &depth_of, &max_depth, &lerr)) return fail(lerr);
-  SceneLayout L;
-  derive_layout(sd, depth_of, &L);
-  part_ms[MT_MOVE_MS_LAYOUT] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-  DevScene dev = s->dev;
-  MT_TRY(move_upload(fresh, L.groups, "the block boxes", &dev.grp_aabb32));
-  MT_TRY(move_upload(fresh, L.supers, "the super boxes", &dev.sup_aabb32));
-  MT_TRY(move_upload(fresh, L.subs, "the subtree boxes", &dev.sub_aabb32));
-  MT_TRY(move_upload(fresh, L.hsr, "the walk's records", &dev.hs_rec));
-  MT_TRY(move_upload(fresh, L.ll_tri, "the long lists", &dev.ll_tri));
-  MT_TRY(move_upload(fresh, L.ll_exact, "the long lists", &dev.ll_exact));
-  MT_TRY(move_upload(fresh, L.ll_box_q, "the long lists' boxes", &dev.ll_box_q));
-  MT_TRY(move_upload(fresh, L.ll_grp_q, "the long lists' boxes", &dev.ll_grp_q));
-  MT_TRY(move_upload(fresh, L.ll_sup_q, "the long lists' boxes", &dev.ll_sup_q));
-  MT_TRY(move_upload(fresh, L.sl_box, "the short lists' boxes", &dev.sl_box32));
-  MT_TRY(move_upload(fresh, L.recs, "the node records", &dev.nodes));
-  MT_TRY(move_upload(fresh, L.tri_aabb, "the triangles' boxes", &dev.tri_aabb));
-  MT_TRY(move_upload(fresh, L.tri_aabb32, "the triangles' boxes", &dev.tri_aabb32));
-  part_ms[MT_MOVE_MS_UPLOAD] = ms_since(t0);
-  for (int k = 0; k < 3; k++) dev.bmax[k] = L.bmax[k];
-  dev.tri_vertex = now.vertex;
-  dev.tri_normal = now.normal;
-  dev.tri_uvw = now.uvw;
-  dev.tri_mtl = now.mtl;
-  dev.tri_line = now.line;
-  dev.n_nodes = tree->n_nodes;
-  dev.tree_depth = L.max_depth;
-  dev.scene_regular = L.regular ? 1 : 0;
-  dev.pack_shift = s->tune.v[MT_TUNE_PACKED_STACK] != 0.0 ? pack_shift_for(n, tree->n_nodes) : 0;
-  // what the scene gives up once the swap stands (as many as `fresh` brings: s->allocs keeps its size)
-  const void *const old_allocs[] = {s->dev.grp_aabb32, s->dev.sup_aabb32, s->dev.sub_aabb32, s->dev.hs_rec, s->dev.ll_tri,
-                                    s->dev.ll_exact, s->dev.ll_box_q, s->dev.ll_grp_q, s->dev.ll_sup_q, s->dev.sl_box32,
-                                    s->dev.nodes, s->dev.tri_aabb, s->dev.tri_aabb32, s->dev.tri_vertex, s->dev.tri_normal,
-                                    s->dev.tri_uvw, s->dev.tri_mtl, s->dev.tri_line};
-  std::vector<void *> allocs_new;
-  allocs_new.reserve(s->allocs.size());
-  for (void *p : s->allocs) {
-    if (std::find(std::begin(old_allocs), std::end(old_allocs), (const void *)p) == std::end(old_allocs)) allocs_new.push_back(p);
-  }
-  if (allocs_new.size() + fresh.p.size() != s->allocs.size()) {
-    return fail(MT_ERR_HIP, "the scene's allocations are not the %zu its arrays name", fresh.p.size());
-  }
-  allocs_new.insert(allocs_new.end(), fresh.p.begin(), fresh.p.end());
-  // ---- 6. the swap.  The launch configuration depends on the tree (deep layout, LDS bytes, packed stack): if it cannot
-  // be made, the old scene and its configuration come back.  After it nothing fails.
+  derive_layout(sd, depth_of, &M.L);
+  return MT_OK;
+}
+
+// 6.: the swap.  M.dev, the live DevScene with the derived arrays of M.geo, gets the rest of the moved scene.  The
+// launch configuration depends on the tree (deep layout, LDS bytes, packed stack): if it cannot be made, the old scene
+// and its configuration come back.  After it nothing fails, and the scene takes what was built aside: M keeps what the
+// scene gives up.
+int move_swap(mt_scene *s, Move &M) {
+  show_tri_arrays(M.tri, &M.dev);
+  M.dev.n_nodes = M.host.n_nodes;
+  M.dev.pack_shift = s->tune.v[MT_TUNE_PACKED_STACK] != 0.0 ? pack_shift_for(M.n, M.host.n_nodes) : 0;
   const DevScene dev_was = s->dev;
-  s->dev = dev;
-  {
-    const int rc = configure_launch(s);
-    if (rc != MT_OK) {
-      const std::string why = g_err;
-      (void)hipGetLastError();
-      s->dev = dev_was;
-      (void)configure_launch(s);
-      return fail(rc, "%s", why.c_str());
-    }
+  s->dev = M.dev;
+  const int rc = configure_launch(s);
+  if (rc != MT_OK) {
+    const KeptError why;
+    (void)hipGetLastError();
+    s->dev = dev_was;
+    (void)configure_launch(s);
+    return why.fail_again(rc);
   }
   s->dev_uploaded_valid = false;
-  s->allocs.swap(allocs_new);
-  for (const void *p : old_allocs) (void)hipFree(const_cast<void *>(p));
-  fresh.p.clear();  // (the scene's now)
-  s->tri_id_host.swap(mirrors.tri_id);
-  s->tri_mtl_host = tri_mtl_new;
+  s->geo.swap(M.geo);
+  M.geo.free_all();  // (the old arrays, within the call's total_ms)
+  s->tri = M.tri;
+  s->tri_id_host.swap(M.mirrors.tri_id);
+  s->tri_mtl_host = M.tri_mtl;
   for (int w = 0; w < 2; w++) {
-    s->attr_stamp_host[w].swap(mirrors.stamp[w]);
-    if (d_stamp_new[w].p != nullptr) {
-      std::swap(s->d_attr_stamp[w].p, d_stamp_new[w].p);
-      std::swap(s->d_attr_stamp[w].bytes, d_stamp_new[w].bytes);
-    }
+    s->attr_stamp_host[w].swap(M.mirrors.stamp[w]);
+    if (M.d_stamp[w].p != nullptr) s->d_attr_stamp[w].swap(M.d_stamp[w]);
   }
-  if (d_tri_id_new.p != nullptr) {
-    std::swap(s->d_tri_id.p, d_tri_id_new.p);
-    std::swap(s->d_tri_id.bytes, d_tri_id_new.bytes);
-  }
+  if (M.d_tri_id.p != nullptr) s->d_tri_id.swap(M.d_tri_id);
   s->geo_generation++;
+  return MT_OK;
+}
+
+// Steps 1 .. 6 of mt_scene_set_triangle_vertices for a checked list of n_idx >= 1 triangles
+int move_triangles(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, mt_build_info *info) {
+  const auto w0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the scene while it is taken apart
+  Move M;
+  M.n = s->dev.n_tris;
+  unsigned int changed = 0;
+  MT_TRY(move_stage(s, add_idx, n_idx, vertices, M, &changed));
+  if (changed == 0) return MT_OK;  // the listed vertices are the live ones, bit for bit
+  double part_ms[MT_MOVE_TIMES] = {};
+  auto t0 = std::chrono::steady_clock::now();
+  const auto lap = [&](int part) {
+    part_ms[part] = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+  };
+  MT_TRY(move_build(s, M));
+  lap(MT_MOVE_MS_BUILD);
+  MT_TRY(move_regather(s, M));
+  lap(MT_MOVE_MS_REGATHER);
+  MT_TRY(move_readback(M));
+  lap(MT_MOVE_MS_READBACK);
+  MT_TRY(move_derive(s, M));
+  lap(MT_MOVE_MS_LAYOUT);
+  M.dev = s->dev;
+  MT_TRY(upload_derived(M.L, M.geo, &M.dev));
+  lap(MT_MOVE_MS_UPLOAD);
+  MT_TRY(move_swap(s, M));
   for (int k = 0; k < MT_MOVE_TIMES; k++) s->move_ms[k] = part_ms[k];
   if (info) {
-    *info = tree->info;
+    *info = M.tree->info;
     info->total_ms = ms_since(w0);
   }
   return MT_OK;

@@ -285,6 +285,53 @@ def test_move_after_other_edits_and_a_regrow_in_the_new_order():
         abi.scene_destroy(h)
 
 
+def texels_of(seed, shape):
+    return np.random.RandomState(seed).randint(0, 256, shape).astype(np.uint8)
+
+
+def with_texture0(tris, texels0, texels1=None):
+    """tris with texture 0, and texture 1 where given, replaced"""
+    t1 = tris["textures"][1] if texels1 is None else dict(texels=texels1)
+    return dict(tris, textures=[dict(texels=texels0), t1])
+
+
+def test_textures_set_between_and_after_moves():
+    """A texture set patches the scene's table allocations, a move replaces its geometry allocations: texture 0 is
+    replaced on both sides of a move, texture 1 between two moves, and every state is the newly made scene's."""
+    abi = M.hip_abi()
+    v, steps = MOVES["leaf_15_to_16"]
+    (idx, listed), (_, back) = steps
+    tris = mv.scene_of(v)
+    assert {m["tex"] for m in tris["materials"]} >= {0, 1}  # a material names each texture
+    original = [t["texels"] for t in tris["textures"]]
+    a, b, c = texels_of(21, (3, 5, 3)), texels_of(22, (2, 2, 3)), texels_of(23, (7, 1, 3))
+    assert len({a.shape, c.shape, original[0].shape}) == 3 and b.shape != original[1].shape
+    moved = v.copy()
+    moved[idx] = listed
+    view = view_of(v)
+    sens = binding.sensor(view[0], W, H)
+    h, _ = abi.scene_create_triangles(tris)
+    try:
+        first = look(abi, h, view)
+        abi.set_texture(h, 0, a)
+        abi.scene_set_triangle_vertices(h, idx, listed)
+        assert differences(look(abi, h, view), new_scene_look(abi, with_texture0(tris, a), moved, view)) == []
+        abi.set_texture(h, 1, b)
+        albedo_a = abi.render_gbuffer(h, sens, W, H, channels=("albedo",))["albedo"]
+        abi.set_texture(h, 0, c)
+        albedo_c = abi.render_gbuffer(h, sens, W, H, channels=("albedo",))["albedo"]
+        assert not same(albedo_a, albedo_c), "no texel of texture 0 shows"
+        abi.scene_set_triangle_vertices(h, idx, back)
+        assert differences(look(abi, h, view), new_scene_look(abi, with_texture0(tris, c, b), v, view)) == []
+        abi.set_texture(h, 0, original[0])
+        abi.set_texture(h, 1, original[1])
+        last = look(abi, h, view)
+        assert differences(last, new_scene_look(abi, tris, v, view)) == []
+        assert differences(last, first) == []
+    finally:
+        abi.scene_destroy(h)
+
+
 # ---- (e) no-op sets, old trees
 
 def test_noop_set_bumps_nothing_and_a_real_move_retires_old_trees():
@@ -377,6 +424,32 @@ def test_depth_refusal_leaves_the_scene_as_it_was():
         cur = v.copy()
         cur[idx] = legal
         assert differences(look(abi, h, view), new_scene_look(abi, tris, cur, view)) == []
+    finally:
+        abi.scene_destroy(h)
+
+
+def test_a_refused_move_after_a_texture_set_keeps_both():
+    abi = M.hip_abi()
+    v, idx, listed = mv.never_separate_move()
+    tris = mv.scene_of(v)
+    view = view_of(v)
+    a, c = texels_of(21, (3, 5, 3)), texels_of(23, (7, 1, 3))
+    h, _ = abi.scene_create_triangles(tris)
+    try:
+        abi.set_texture(h, 0, a)
+        before = look(abi, h, view)
+        assert differences(before, new_scene_look(abi, with_texture0(tris, a), v, view)) == []
+        info = binding.mt_build_info()
+        rc = abi.lib.mt_scene_set_triangle_vertices(h, idx.ctypes.data, len(idx), listed.ctypes.data, C.byref(info))
+        assert rc == MT_ERR_UNSUPPORTED and abi.last_error() == DEPTH_MESSAGE
+        assert differences(look(abi, h, view), before) == []  # the geometry and the new texture, both as they were
+        legal = v[idx] + np.array([0.0, 0.0, 0.125])
+        abi.scene_set_triangle_vertices(h, idx, legal)
+        cur = v.copy()
+        cur[idx] = legal
+        assert differences(look(abi, h, view), new_scene_look(abi, with_texture0(tris, a), cur, view)) == []
+        abi.set_texture(h, 0, c)
+        assert differences(look(abi, h, view), new_scene_look(abi, with_texture0(tris, c), cur, view)) == []
     finally:
         abi.scene_destroy(h)
 
