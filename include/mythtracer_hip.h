@@ -1141,6 +1141,14 @@ enum {
                                  = unless a primary ray of the frame has a zero direction component; 2 = even then (tests) */
   MT_TUNE_COUNT
 };
+/* One more knob, outside the dense range above: those are constants of a launch's scheduling, this one is a property of
+ * the traversal.  Frame kernels (the state machine of engines 1 and 3, lean and full; the ray pool's own shadow records
+ * are never bounded): an iteration of the shadow loop does not walk into subtrees that its ray enters beyond the light
+ * (mt_shadow_bound.h; a scene that is not eligible traces as before).  The picture is the same; the WORK COUNTERS are
+ * not -- the far wall's triangle is no longer tested.  0 = never; 1 (default) = launches with the counters off
+ * (mt_scene_set_stats(scene, 0)), so that the counters always describe the unbounded traversal, whose work is never
+ * below the reference's; 2 = counting launches too (tests, measurements). */
+#define MT_TUNE_SHADOW_BOUND 1000
 int mt_scene_set_tuning(mt_scene *scene, int knob, double value);
 
 /* Device durations of the launches made since the previous call (at most the

@@ -58,6 +58,8 @@ TUNE = {name: i for i, name in enumerate([
     "POOL_SCRATCH_MB", "HYBRID_POOL_SHARE", "HYBRID_QUAD_SHARE", "HYBRID_WORK1", "HYBRID_WORK2", "FORECAST_STEP",
     "HYBRID_STARTER_SHARE", "DEEP_LAYOUT", "MULTI_FORCE_PEER_COPY", "MULTI_BALANCE", "XCD_QUEUES",
     "ORDER_GROUPS", "SM_CELL_SHARE", "SM_CELL_TIME", "SM_CELL_WORK", "HYBRID_CELL_FACTOR", "LEAN_KERNEL"])}
+# knob ids outside the enum's dense range (include/mythtracer_hip.h: ids from 1000 on); set_tuning looks a name up in TUNE, then here
+TUNE_EXTRA = {"SHADOW_BOUND": 1000}  # MT_TUNE_SHADOW_BOUND: 0 | 1 | 2
 
 STAT_NAMES = ["rays_primary", "rays_secondary", "rays_shadow", "box_tests",
               "node_visits", "tri_tests", "mt_tests", "shaded_hits"]
@@ -1202,8 +1204,8 @@ class HipAbi:
         self.check(self.lib.mt_set_default_engine(int(engine)))
 
     def set_tuning(self, h, knob: str, value: float):
-        """mt_scene_set_tuning; knob = a key of TUNE (e.g. "POOL_CAP")."""
-        self.check(self.lib.mt_scene_set_tuning(h, TUNE[knob], float(value)))
+        """mt_scene_set_tuning; knob = a key of TUNE (e.g. "POOL_CAP") or of TUNE_EXTRA ("SHADOW_BOUND")."""
+        self.check(self.lib.mt_scene_set_tuning(h, TUNE[knob] if knob in TUNE else TUNE_EXTRA[knob], float(value)))
 
     def render_frame_multi(self, handles, sensor12, image_w, image_h, tile_w=64, tile_h=64, max_depth=5,
                            want_stats=True):

@@ -281,6 +281,7 @@ struct mt_scene {
   Buf<unsigned int> d_order_whist; // [kOrdGroupsMax][kOrdKeysMax]
   unsigned order_epoch = 0;             // work orders of this scene so far (order_forecast_kernel, order_count_kernel, order_scatter_kernel)
   DevScene dev_uploaded;                // what d_dev holds
+  int32_t shadow_bound_knob = 1;        // MT_TUNE_SHADOW_BOUND (DevScene::sb_knob)
   bool dev_uploaded_valid = false;
   Buf<double> d_frames;            // throughput engine: recursion frames
   Buf<int32_t> d_hit_prim;         // launch 1 -> launch 2 hand-off (per pixel)
@@ -1306,6 +1307,7 @@ static int upload_derived(const SceneLayout &L, DeviceAllocs &geo, DevScene *dev
   for (int k = 0; k < 3; k++) dev->bmax[k] = L.bmax[k];
   dev->tree_depth = L.max_depth;
   dev->scene_regular = L.regular ? 1 : 0;
+  dev->sb = L.shadow;  // (sb_knob stays the scene's)
   return MT_OK;
 }
 
@@ -1361,6 +1363,7 @@ static int upload_layout(mt_scene *s, const mt_scene_desc *d, const SceneLayout 
   s->dev.n_nodes = d->n_nodes;
   s->dev.force_mode = 0;
   s->dev.pack_shift = pack_shift_for(d->n_tris, d->n_nodes);  // (MT_TUNE_PACKED_STACK = 0 switches it off)
+  s->dev.sb_knob = s->shadow_bound_knob;
   s->dev.n_lights = 0;
   s->dev.lights = nullptr;
   return MT_OK;
@@ -1688,6 +1691,12 @@ int mt_set_default_engine(int engine) {
 }
 
 int mt_scene_set_tuning(mt_scene *s, int knob, double value) {
+  if (s && knob == MT_TUNE_SHADOW_BOUND) {  // (not one of the launch constants in tune.v: a word of the scene description)
+    if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(MT_ERR_ARG, "shadow bound: 0 (never), 1 (launches without work counters) or 2 (always)");
+    s->shadow_bound_knob = s->dev.sb_knob = (int32_t)value;
+    s->forget_histories();  // other block costs: start from a first frame
+    return MT_OK;
+  }
   if (!s || knob < 0 || knob >= MT_TUNE_COUNT || !std::isfinite(value)) return fail(MT_ERR_ARG, "bad tuning argument");
   // The kernels divide by the work factors and scale an even share by the shares: those must be positive (and small
   // enough for their products to stay finite in float); counts and budgets must not be negative or beyond what the

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "mythtracer_hip.h"
+#include "mt_shadow_bound.h"
 
 // Waves per SIMD the frame kernels are compiled for (register budget 512 / n per lane: 2 -> 256 VGPRs, nothing of
 // the frame engines' context spilled).  The hit-set walk hides its latencies itself and wants the registers and the
@@ -137,6 +138,10 @@ struct DevScene {
   int32_t force_mode;  // mt_scene_set_traversal_mode (include/mythtracer_hip.h)
   int32_t scene_regular;  // 1: all coordinates finite and boxes ordered
   int32_t pack_shift;     // 0: 20-byte stack frames; else bits of the (triangle index + 1) field of a packed frame
+  // Shadow rays' distance bound (mt_shadow_bound.h).  sb.on: the scene is eligible.  sb_knob = MT_TUNE_SHADOW_BOUND: the
+  // frame kernels bound their shadow iterations when it exceeds 0 (launches without work counters) or 1 (with them).
+  ShadowBound sb;
+  int32_t sb_knob;
   // Debug heartbeat (normally NULL): host-visible words the kernel updates so
   // that a stuck launch can be diagnosed from the host (MT_DEBUG_HEARTBEAT=1).
   volatile unsigned long long *hb;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mt_device.h"
+#include "mt_shadow_bound.h"
 
 namespace mt {
 
@@ -128,6 +129,7 @@ struct SceneLayout {
   std::vector<float> tri_aabb32;
   double bmax[3] = {0.0, 0.0, 0.0};
   bool regular = false;             // scene_regular
+  ShadowBound shadow{1.0f, 0.0f, 0.0f, 0};  // sb (mt_shadow_bound.h): on = 0 unless the scene is eligible
   int max_depth = 0;                // tree_depth
 };
 
@@ -444,6 +446,11 @@ inline void derive_layout(const mt_scene_desc &d, const std::vector<int> &depth_
   derive_long_lists(d, &L.hsr, &L.ll_tri, &L.ll_exact, &ll_box);
   derive_long_list_quads(ll_box, &L);
   derive_triangle_boxes(d, &L);
+  if (L.regular) {
+    const ShadowBoundInput in{d.n_nodes, d.n_tris, d.node_aabb, d.node_center, d.node_first_child, d.node_prim_begin,
+                              d.node_prim_count, d.tri_vertex, d.tri_aabb};
+    L.shadow = shadow_bound_for(in);
+  }
 }
 
 }  // namespace mt

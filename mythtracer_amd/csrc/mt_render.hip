@@ -489,7 +489,8 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     const int role = quad ? (lane & 3) : 0;
     const bool owner = role == 0;
     const unsigned long long my_group = quad ? (0xFull << (lane & ~3)) : (1ull << lane);
-    enum { MODE_IDLE = 2 };
+    // MODE_SHADOW_AGAIN: a shadow iteration whose bounded traversal answered kTraceRedo -- the same ray once more, without a bound
+    enum { MODE_IDLE = 2, MODE_SHADOW_AGAIN = 3 };
     int mode = owner ? MODE_RADIANCE : MODE_IDLE;
     int level = 0;
     bool in_object = false;
@@ -512,11 +513,11 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
     bool traversing = false;
     bool want_round = false, waiting_round = false;
 
-    // Bound on traversals per item: every ray of a pixel is at most one pass; a
-    // pixel needs at most 2^(max_depth+1) radiance rays, each with one shadow
+    // Bound on traversals per item: every ray of a pixel is at most one pass (a bounded shadow iteration that has to be
+    // repeated: two); a pixel needs at most 2^(max_depth+1) radiance rays, each with one shadow
     // loop per light whose iterations each cross a different surface.
     const long long pass_bound =
-        (2ll << P.max_depth) * (1 + (long long)S.n_lights * ((long long)S.n_tris + 2)) + 16;
+        (2ll << P.max_depth) * (1 + 2 * (long long)S.n_lights * ((long long)S.n_tris + 2)) + 16;
     long long passes = 0;
     while (__ballot(alive) != 0ull) {
       int prim = -1;
@@ -539,7 +540,14 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
 #ifdef MT_DIAG
         const unsigned long long diag_tt0 = __builtin_amdgcn_s_memtime();
 #endif
-        const TraceOut to = trace_wave<STATS, DEEP, LEAN>(S.self, stk.base, lane, tracing, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z);
+        // a shadow iteration looks no farther than its light (mt_shadow_bound.h; the distance from the ray's origin)
+        // (MT_TUNE_SHADOW_BOUND is data, not a code variant: the walk turns l32 into +inf where the bound is off)
+        float l32 = __builtin_inff();
+        if (tracing && mode == MODE_SHADOW) {
+          const MT_CONST mt_light *lt = lights + li;
+          l32 = shadow_l32(sqr_distance(ro, v3(lt->position[0], lt->position[1], lt->position[2])));
+        }
+        const TraceOut to = trace_wave<STATS, DEEP, LEAN, true>(S.self, stk.base, lane, tracing, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, l32);
 #ifdef MT_DIAG
         asm volatile("" :: "v"(to.prim));
         diag_trace_ticks += __builtin_amdgcn_s_memtime() - diag_tt0;
@@ -567,7 +575,9 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
       bool after_lights = false, do_return = false;
       V3 retval = v3(0, 0, 0);
       V3 add1 = retval, add2 = retval, add3 = retval;  // this role's contributions to `color`, in the order they are added
-      if (tracing) {
+      const bool again = tracing && prim == kTraceRedo;  // (nothing consumed: the lane's state is the iteration's still)
+      if (again) mode = MODE_SHADOW_AGAIN;
+      if (tracing && !again) {
         if (mode == MODE_RADIANCE) {
           if (STATS) {  // with launch 1, level 0 was counted there
             if (level > 0) st.v[ST_RAYS_SECONDARY]++;
@@ -614,6 +624,7 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
             }
           }
         } else {  // ---- one iteration of the shadow loop, mythtracer.cc:94-156
+          mode = MODE_SHADOW;  // (it may have been MODE_SHADOW_AGAIN)
           if (STATS) {
             st.v[ST_RAYS_SHADOW]++;
             st.v[ST_BYTES_VECTOR] += 96u + 4u + 32u;  // light, occluder's material index and transparency
@@ -700,7 +711,7 @@ __device__ __forceinline__ unsigned sm_engine(const DevScene &S, const RenderPar
       // (a) a round is complete when no role of the pixel is still in a shadow
       //     loop: the owner adds the roles' terms in light order.
       {
-        const unsigned long long busy = __ballot(alive && mode == MODE_SHADOW);
+        const unsigned long long busy = __ballot(alive && (mode & 1) != 0);  // MODE_SHADOW, MODE_SHADOW_AGAIN
         const bool round_done = owner && waiting_round && ((busy & my_group) == 0ull);
         const int hl0 = has_light ? 1 : 0, h30 = has_add3 ? 1 : 0;
         if (quad && has_light) {  // possibly computed in an earlier pass

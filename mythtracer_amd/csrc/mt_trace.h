@@ -314,7 +314,7 @@ struct RayRegs {
 #define MT_F32_FROM_PARAMS(f) \
   Filter32 f;                 \
   f.ix = fix_; f.iy = fiy_; f.iz = fiz_; f.cnx = fcnx_; f.cny = fcny_; f.cnz = fcnz_; \
-  f.cfx = fcfx_; f.cfy = fcfy_; f.cfz = fcfz_
+  f.cfx = fcfx_; f.cfy = fcfy_; f.cfz = fcfz_; f.tmax = __builtin_inff()
 #define MT_RAY_FROM_PARAMS(r) \
   RayRegs r;                  \
   r.ox = ox_; r.oy = oy_; r.oz = oz_; r.dx = dx_; r.dy = dy_; r.dz = dz_; r.ix = ix_; r.iy = iy_; r.iz = iz_
@@ -502,6 +502,11 @@ struct Filter32 {
   float ix, iy, iz;
   float cnx, cny, cnz;
   float cfx, cfy, cfz;
+  // The hit-set walk's distance bound (mt_shadow_bound.h; the BOUNDED instantiations of trace_wave only): a subtree or
+  // an own list whose conservative entry distance exceeds it is skipped.  +inf for every ray that is not an iteration
+  // of a shadow loop; NaN compares false, so it skips nothing; -inf marks a lane whose walk met a tie it must not decide
+  // with a bound (trace_wave answers kTraceRedo for it) and skips everything that is left.
+  float tmax;
 };
 
 // next representable fp32 below / above a finite value
@@ -639,6 +644,15 @@ __device__ __forceinline__ bool near_far_may_hit(float nx, float fx, float ny, f
   const float lo0 = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.0f));
   const float hi = __builtin_fminf(__builtin_fminf(tfx, tfy), tfz);
   return !(lo0 > hi);  // NaN: keep
+}
+// ... and not beyond the lane's distance bound: one minimum more (a NaN bound leaves hi as it is)
+__device__ __forceinline__ bool near_far_may_hit_within(float nx, float fx, float ny, float fy, float nz, float fz, const Filter32 &f) {
+  const float tnx = __builtin_fmaf(nx, f.ix, f.cnx), tfx = __builtin_fmaf(fx, f.ix, f.cfx);
+  const float tny = __builtin_fmaf(ny, f.iy, f.cny), tfy = __builtin_fmaf(fy, f.iy, f.cfy);
+  const float tnz = __builtin_fmaf(nz, f.iz, f.cnz), tfz = __builtin_fmaf(fz, f.iz, f.cfz);
+  const float lo0 = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.0f));
+  const float hi = __builtin_fminf(__builtin_fminf(__builtin_fminf(tfx, tfy), tfz), f.tmax);
+  return !(lo0 > hi);
 }
 
 // keep mask of the eight subtree boxes `sub` (children fc .. fc + 7) for a ray with one zero direction component:
@@ -1829,10 +1843,15 @@ struct TraceOut {
 // mode (force_mode is 0 by construction), no second round for a wave that mixes regular and irregular rays.  The
 // walk's preconditions are checked once per call; a wave that fails them gets the wave-uniform status DEV_NEEDS_FULL
 // and no result.  For a wave that passes, the same instructions run on the same data as in the full instantiation.
-template <bool STATS, int DEEP = 0, bool LEAN = false>
+// BOUNDED (the frame kernels' state machine): l32 = shadow_l32 of a shadow iteration's lane, +inf for every other ray;
+// where the scene is eligible and MT_TUNE_SHADOW_BOUND allows it the walk skips what lies beyond shadow_tmax32
+// (Filter32::tmax; the scene's constants are read here, where they live for three instructions).  A lane that met a tie gets
+// prim = kTraceRedo and no result: the caller traces the same ray again with +inf.  The ordered descent knows no bound.
+constexpr int kTraceRedo = -2;
+template <bool STATS, int DEEP = 0, bool LEAN = false, bool BOUNDED = false>
 __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned stack_base, int lane,
                                                          bool want_all, double ox, double oy, double oz,
-                                                         double dx, double dy, double dz) {
+                                                         double dx, double dy, double dz, float l32 = __builtin_inff()) {
   constexpr bool WIDE = DEEP >= 2;  // DEEP 2: child bytes for 24 levels (mt_device.h, deep_layout)
   const MT_CONST DevScene *G = as_const(uniform_ptr(scene));
   DevScene S;
@@ -1926,6 +1945,14 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
                            (__ballot(want && !fin) == 0ull);
   Filter32 f32;
   const bool f32_ok = make_filter32(S, r, f32);
+  f32.tmax = __builtin_inff();
+  if constexpr (BOUNDED) {
+    ShadowBound sb;
+    sb.rho1 = G->sb.rho1; sb.mu = G->sb.mu; sb.kappa = G->sb.kappa;
+    const bool sb_on = G->sb.on != 0 && G->sb_knob > (STATS ? 1 : 0);  // (wave-uniform)
+    const float imax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(f32.ix), __builtin_fabsf(f32.iy)), __builtin_fabsf(f32.iz));
+    if (sb_on) f32.tmax = shadow_tmax32(sb, l32, imax);
+  }
   const bool use_filter = all_regular && (S.force_mode != 4) && (S.force_mode != 2) &&
                           (__ballot(want && !f32_ok) == 0ull);
 
@@ -2381,6 +2408,12 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
       const double tmax = mn3<false>(xh ? amax[0][1] : amax[0][0], yh ? amax[1][1] : amax[1][0], zh ? amax[2][1] : amax[2][0]);
       const double tmin = mx3<false>(xh ? amin[0][1] : amin[0][0], yh ? amin[1][1] : amin[1][0], zh ? amin[2][1] : amin[2][0]);
       const bool entered = (tmax >= 0.0) & (tmin <= tmax);
+      // Bounded lanes, DESIGN 3.1.3: the proof orders the children's parameter intervals like their sort keys, which
+      // holds unless a child that brings a hit is entered and left at ONE parameter (then it may tie with a sibling of
+      // smaller index that the bound emptied).  Such a lane gives up its bound: kTraceRedo.  So that no such child goes
+      // unseen, a bounded lane keeps the children AT its candidate's key (below); offering them changes nothing.
+      const bool bounded_lane = BOUNDED && f32.tmax < __builtin_inff();
+      const bool tie = bounded_lane && rp_ >= 0 && entered && tmin == tmax;
       const int own_p = HS_LD(h_own_p, g_own_p, lev);
       const double own_t = HS_LD(h_own_t, g_own_t, lev);
       if (rp_ >= 0 && entered && !(own_p >= 0 && rt_ > own_t)) {
@@ -2413,13 +2446,16 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
             rest &= rest - 1u;
             const bool cxh = (c2 & 1) != 0, czh = (c2 & 2) != 0, cyh = (c2 & 4) != 0;  // wave-uniform
             const double cmin = mx3<false>(cxh ? amin[0][1] : amin[0][0], cyh ? amin[1][1] : amin[1][0], czh ? amin[2][1] : amin[2][0]);
-            const bool behind = wp >= 0 && !((cmin < wmin) || (cmin == wmin && c2 < kw));
+            const bool behind = wp >= 0 && !((cmin < wmin) || (cmin == wmin && (c2 < kw || bounded_lane)));
             if (behind) my &= ~(1u << c2);
             if (__ballot(((my >> c2) & 1u) != 0u) != 0ull) still |= 1u << c2;
           }
           set8(wantA, wantB, wantC, lev, my);
           set8(pendA, pendB, pendC, lev, still);
         }
+      }
+      if constexpr (BOUNDED) {
+        if (tie) f32.tmax = -__builtin_inff();
       }
     };
     if (m != 0ull) {
@@ -2506,7 +2542,8 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
           }
 #pragma unroll
           for (int c = 0; c < 8; c++) {
-            const bool pass = near_far_may_hit(pnx[c], pfx[c], pny[c], pfy[c], pnz[c], pfz[c], f32);
+            const bool pass = BOUNDED ? near_far_may_hit_within(pnx[c], pfx[c], pny[c], pfy[c], pnz[c], pfz[c], f32)
+                                      : near_far_may_hit(pnx[c], pfx[c], pny[c], pfy[c], pnz[c], pfz[c], f32);
             if (pass) bits |= 1u << c;
             // (the compare's lane mask IS the ballot: which children some entering lane lets through costs no vector code)
             if ((__ballot(pass) & m) != 0ull) any |= 1u << c;
@@ -2521,7 +2558,8 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
           const MT_LDS float *wx = (const MT_LDS float *)(uintptr_t)(rec + (unsigned)kHsRecOwn + (sxl != 0 ? 4u : 0u));
           const MT_LDS float *wy = (const MT_LDS float *)(uintptr_t)(rec + (unsigned)kHsRecOwn + 12u + (syl != 0 ? 4u : 0u));
           const MT_LDS float *wz = (const MT_LDS float *)(uintptr_t)(rec + (unsigned)kHsRecOwn + 24u + (szl != 0 ? 4u : 0u));
-          in_list = in && near_far_may_hit(wx[0], wx[1], wy[0], wy[1], wz[0], wz[1], f32);
+          in_list = in && (BOUNDED ? near_far_may_hit_within(wx[0], wx[1], wy[0], wy[1], wz[0], wz[1], f32)
+                                   : near_far_may_hit(wx[0], wx[1], wy[0], wy[1], wz[0], wz[1], f32));
         }
         const unsigned long long lm = __ballot(in_list);
 #ifdef MT_PROF
@@ -2633,6 +2671,9 @@ __device__ MT_TRACE_ATTR TraceOut trace_wave(const DevScene *scene, unsigned sta
     if (want && status == DEV_OK) {
       out_prim = ret_p;
       out_t = ret_t;
+      if constexpr (BOUNDED) {
+        if (f32.tmax == -__builtin_inff()) out_prim = kTraceRedo;
+      }
     }
     cur = -1;
   }
