@@ -1330,7 +1330,8 @@ int mt_scene_read_tree(const mt_scene *scene, mt_octree_arrays *out);
  * to the scene's; out NULL with n_tris > 0.
  * info (nullable): the build's, as mt_octree_build reports it, with total_ms = the wall time of the whole set; all zero
  * after a no-op.  mt_scene_move_times_last, a diagnostic in the manner of mt_scene_kernel_times: the wall times in ms of
- * the parts of the scene's last set that changed a triangle, out_ms[MT_MOVE_TIMES], all zero before the first such set
+ * the parts of the scene's last set that changed a triangle -- or of its last mt_scene_edit_triangles (below) that was
+ * not the no-op, whichever came later --, out_ms[MT_MOVE_TIMES], all zero before the first such call
  * (MT_ERR_ARG: scene or out_ms NULL).  mt_build_info cannot carry them without a change of the ABI's structs. */
 enum {
   MT_MOVE_MS_BUILD = 0,  /* the tree */
@@ -1344,6 +1345,61 @@ int mt_scene_set_triangle_vertices(mt_scene *scene, const int32_t *add_idx, int 
                                    const double *vertices /* n_idx x 9 */, mt_build_info *info /* nullable */);
 int mt_scene_get_triangle_vertices(mt_scene *scene, double *out /* n_tris x 9 */, int n_tris);
 int mt_scene_move_times_last(const mt_scene *scene, double *out_ms /* MT_MOVE_TIMES */);
+
+/* Triangles ADDED and REMOVED in place: the triangle set of the uploaded scene changed, n_tris with it.  (No reference
+ * counterpart.)  For a session in which an object appears or leaves without giving up the scene: everything a move keeps
+ * is kept -- materials, textures (no texel moves), lights, tuning, engine, traversal mode, the stats switch, the
+ * material / texture / assignment / attribute generations, and the forecast banks with their cost history (they are per
+ * image block and do not know n_tris).
+ * remove_idx holds ADD-order indices of the scene as it is, each at most once, in any order.  The add_* arrays are HOST
+ * arrays in mt_triangle_desc's layout: 9 / 9 / 9 doubles and 1 / 1 int32 per added triangle.  add_material indexes the
+ * scene's existing material table, or is -1: the call adds no material and no texture.
+ * NEW ADD ORDER: the surviving triangles come first, in their old relative order, numbered densely -- new index = old
+ * index - the number of removed indices below it --; the n_add new triangles follow in the order given.  (numpy.delete
+ * followed by concatenate: the caller can compute it, so no call reports it.)
+ * CONTRACT: mt_scene_set_triangle_vertices's, word for word.  After a successful edit every call that renders, shades or
+ * reads the scene -- all frame engines, the hybrid, the lean kernel and its redo launch, supersampled and adaptive
+ * frames, tiles and tile lists, the G-buffer and light-buffer calls, mt_raytree_create[_rays], mt_trace_rays,
+ * mt_intersect_rays, mt_render_frame_multi replicas, mt_scene_read_tree and every getter -- gives, byte for byte and
+ * plane for plane, what it gives on a scene newly made by mt_scene_create_triangles from the resulting add-order arrays:
+ * the survivors with their live vertices, normals, uvw, assignment and line numbers, the added triangles with theirs,
+ * and the live materials, textures, lights and switches.  The counters of mt_stats match wherever the two frames are
+ * scheduled alike (see above).
+ * COUNT AND ORDER: n_tris is the new count and the node-stream order the new tree's from then on.
+ * mt_scene_set_triangle_materials / _normals / _uvw, their getters, mt_scene_get_triangle_vertices and
+ * mt_scene_set_triangle_vertices speak the new count and the new order; a call with the old count gets their
+ * "%d triangles for a scene made with %d".
+ * STAMPS: an added triangle's attribute stamp is 0, as for a triangle no set has touched; a stamp plane that does not
+ * exist yet stays non-existent.
+ * How (mt_build.h): mt::edit_mark_kernel writes keep[a] = 0 for every listed index over a plane of ones; an exclusive
+ * integer prefix sum of it (rocPRIM) is every survivor's new add index, its total the survivor count, which is held to
+ * n_tris - n_remove (MT_ERR_INTERNAL if they differ); mt::edit_stage_kernel brings the survivors' live vertices and the
+ * added vertices into the new add order and notes every triangle's source; the tree is built from that array with the new
+ * count; mt::edit_regather_kernel writes all per-triangle arrays and the stamp planes in the new stream order into new
+ * allocations, the attributes from the old arrays or from the uploaded add arrays.  From there on the steps are a
+ * move's, with another count: read-back, mt_scene_create's checks and derivation, upload, swap -- which also sets
+ * n_tris and what is computed from it --, the mirrors in the new count (mt_edit.h), the old allocations freed.
+ * NO-OP: n_remove = 0 and n_add = 0 is MT_OK, changes no state and makes no device call.  Every other accepted edit
+ * changes the scene: removing a triangle and adding an identical one renumbers the add order.
+ * FAILURE before the swap leaves the scene EXACTLY as it was, as for a move: MT_ERR_NOMEM; MT_ERR_UNSUPPORTED with the
+ * build's message for a tree deeper than MT_MAX_TREE_DEPTH or of more nodes than an int32 indexes; MT_ERR_HIP.
+ * RAY TREES: every edit that is not the no-op bumps the geometry generation, so a tree of the old geometry is refused for
+ * good by the calls that refuse it after a move (above); no other check exists or is needed.  The `prim` plane of an
+ * older G-buffer holds add indices of the OLD numbering.
+ * Argument checks come before any device call, in this order, all MT_ERR_ARG: scene NULL; a scene made without tri_id;
+ * a scene of zero triangles; n_remove negative or greater than n_tris; n_add negative; remove_idx NULL with
+ * n_remove > 0; a missing add array with n_add > 0, named in the order vertex, normal, uvw, material, line_no; a remove
+ * index outside 0 .. n_tris - 1; a remove index listed twice; a resulting count (computed in 64 bits) below 1 or above
+ * what an int32 holds; an add_material outside -1 .. n_materials - 1 (mt_scene_create's message).  (Then, for a scene
+ * from mt_scene_create, once: a tri_id that is no permutation.)  An edit never empties a scene and never starts from an
+ * empty one, which keeps zero-sized launches and allocations out of the path.  Vertex values are not checked: NaN and
+ * +-inf are legal, as for the build.
+ * info (nullable): the build's, with total_ms = the wall time of the whole edit; all zero after the no-op.
+ * mt_scene_move_times_last reports the parts of the scene's last move OR edit, through the same five entries
+ * (MT_MOVE_MS_BUILD does not include the staging, as for a move). */
+int mt_scene_edit_triangles(mt_scene *scene, const int32_t *remove_idx, int n_remove, int n_add, const double *add_vertex,
+                            const double *add_normal, const double *add_uvw, const int32_t *add_material,
+                            const int32_t *add_line_no, mt_build_info *info /* nullable */);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ HIP_SYMBOLS = [
     "mt_octree_build", "mt_octree_info", "mt_octree_read", "mt_octree_destroy", "mt_scene_create_triangles",
     "mt_scene_read_tree",
     "mt_scene_set_triangle_vertices", "mt_scene_get_triangle_vertices", "mt_scene_move_times_last",
+    "mt_scene_edit_triangles",
 ]
 MT_MAX_RECURSION = 16
 
@@ -375,6 +376,7 @@ class HipAbi:
         L.mt_scene_set_triangle_vertices.argtypes = [vp, vp, ci, vp, C.POINTER(mt_build_info)]
         L.mt_scene_get_triangle_vertices.argtypes = [vp, vp, ci]
         L.mt_scene_move_times_last.argtypes = [vp, vp]
+        L.mt_scene_edit_triangles.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, C.POINTER(mt_build_info)]
         L.mt_retexture_gbuffer.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_retexture_gbuffer_device.argtypes = [vp, ci, ci, C.POINTER(mt_gbuffer), vp]
         L.mt_render_chunk.argtypes = [vp, C.POINTER(mt_sensor)] + [ci] * 7 + [vp, vp, vp]
@@ -581,6 +583,30 @@ class HipAbi:
                                                            v.ctypes.data if v.size else None, C.byref(info)))
         return info.as_dict()
 
+    def scene_edit_triangles(self, h, remove, add) -> dict:
+        """mt_scene_edit_triangles: the triangles `remove` (ADD-order indices of the scene as it is, each at most once)
+        taken out and the triangles of `add` appended.  add: None, or a dict of tri_vertex, tri_normal, tri_uvw
+        ((k, 9) or (k, 3, 3) doubles), tri_material and tri_line_no (k int32), as scene_create_triangles takes them;
+        tri_material indexes the scene's existing materials or is -1.  The new add order is numpy.delete followed by
+        concatenate; n_tris and the node-stream order are the new scene's afterwards.  Returns the build's info, all
+        zero when both lists are empty.  RuntimeError with the library's message on a refusal: the scene is then as it
+        was."""
+        idx = np.ascontiguousarray([] if remove is None else remove, dtype=np.int32).reshape(-1)
+        n_add, ptr = 0, [None] * 5
+        if add is not None:
+            v, nrm, uvw = (np.ascontiguousarray(add[k], dtype=np.float64) for k in ("tri_vertex", "tri_normal", "tri_uvw"))
+            mtl, line = (np.ascontiguousarray(add[k], dtype=np.int32).reshape(-1) for k in ("tri_material", "tri_line_no"))
+            n_add = int(mtl.size)
+            if not (v.size == nrm.size == uvw.size == 9 * n_add and line.size == n_add):
+                raise ValueError("%d added triangles: %d / %d / %d doubles of vertices, normals, uvw (9 per triangle), "
+                                 "%d line numbers" % (n_add, v.size, nrm.size, uvw.size, line.size))
+            if n_add:
+                ptr = [a.ctypes.data for a in (v, nrm, uvw, mtl, line)]
+        info = mt_build_info()
+        self.check(self.lib.mt_scene_edit_triangles(h, idx.ctypes.data if idx.size else None, int(idx.size), n_add, *ptr,
+                                                    C.byref(info)))
+        return info.as_dict()
+
     def scene_get_triangle_vertices(self, h, n_tris) -> np.ndarray:
         """mt_scene_get_triangle_vertices: all vertices of the scene in ADD order, (n_tris, 3, 3) float64."""
         out = np.zeros((max(n_tris, 0), 3, 3), dtype=np.float64)
@@ -589,7 +615,7 @@ class HipAbi:
 
     def scene_move_times(self, h) -> dict:
         """mt_scene_move_times_last: wall times in ms of the parts of the scene's last set_triangle_vertices that
-        changed a triangle: build, regather, readback, layout, upload."""
+        changed a triangle, or of its last edit_triangles: build, regather, readback, layout, upload."""
         out = np.zeros(5, dtype=np.float64)
         self.check(self.lib.mt_scene_move_times_last(h, out.ctypes.data))
         return dict(zip(("build", "regather", "readback", "layout", "upload"), (float(x) for x in out)))
@@ -1307,7 +1333,6 @@ def host_lib():
     L.mth_tree_info.argtypes = [vp, vp, vp, vp]
     L.mth_tree_info.restype = None
     L.mth_tree_dump.argtypes = [vp] * 7
-    L.mth_tree_dump.restype = None
     L.mth_triangles.argtypes = [vp, vp, vp, vp]
     L.mth_triangles.restype = None
     L.mth_flatten.argtypes = [vp] * 12
@@ -1351,6 +1376,9 @@ def host_lib():
     L.mth_update_geometry.argtypes = [vp]
     L.mth_update_geometry.restype = None
     L.mth_update_geometry_in_place.argtypes = [vp]
+    L.mth_add_triangles.argtypes = [vp, ci, vp, vp, vp, C.c_char_p, vp]
+    L.mth_remove_triangles.argtypes = [vp, vp, ci]
+    L.mth_update_triangles_in_place.argtypes = [vp]
     L.mth_raytree_build_rays.restype = vp
     L.mth_raytree_build_rays.argtypes = [vp, vp, C.c_longlong, ci, vp, vp]
     L.mth_raytree_shade_colors.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -1579,8 +1607,9 @@ class MythTracer:
                  first_child=np.zeros(n, dtype=np.int32), prim_begin=np.zeros(n, dtype=np.int32),
                  prim_count=np.zeros(n, dtype=np.int32),
                  prim_ids=np.zeros(max(nt.value, 1), dtype=np.int32))
-        self.L.mth_tree_dump(self.h, _ptr(t["aabb"]), _ptr(t["center"]), _ptr(t["first_child"]),
-                             _ptr(t["prim_begin"]), _ptr(t["prim_count"]), _ptr(t["prim_ids"]))
+        if not self.L.mth_tree_dump(self.h, _ptr(t["aabb"]), _ptr(t["center"]), _ptr(t["first_child"]),
+                                    _ptr(t["prim_begin"]), _ptr(t["prim_count"]), _ptr(t["prim_ids"])):
+            raise RuntimeError("tree failed: " + self.last_error())
         t["prim_ids"] = t["prim_ids"][:nt.value]
         return t
 
@@ -1765,6 +1794,49 @@ class MythTracer:
         self._trees = []
         if not self.L.mth_update_geometry_in_place(self.h):
             raise RuntimeError("update_geometry_in_place failed: " + self.last_error())
+
+    def add_triangles(self, vertices, normals=None, uvw=None, material=None, line_no=None):
+        """MythTracer::AddTriangle for every triangle of `vertices` ((n, 3, 3) or (n, 9)), with `normals` and `uvw` of the
+        same shape (None: the Triangle's defaults), all of the scene's material `material` (a name; None: no material)
+        and the line numbers `line_no` (one int for all, n ints, or None for 0).  The triangles get the last add
+        indices.  Only the host scene changes: update_triangles_in_place() pushes the batch.  RuntimeError for an
+        unknown material; no triangle is added then."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 9)
+        n = v.shape[0]
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 9)
+        tex = None if uvw is None else np.ascontiguousarray(uvw, dtype=np.float64).reshape(-1, 9)
+        for a in (nrm, tex):
+            if a is not None and a.shape[0] != n:
+                raise ValueError("%d triangles need %d doubles, not %d" % (n, n * 9, a.size))
+        line = None if line_no is None else np.ascontiguousarray(np.broadcast_to(np.asarray(line_no, dtype=np.int32), (n,)))
+        if not self.L.mth_add_triangles(self.h, n, _ptr(v) if n else None, _ptr(nrm), _ptr(tex),
+                                        material.encode() if material is not None else None, _ptr(line)):
+            raise RuntimeError("add_triangles failed: " + self.last_error())
+
+    def remove_triangles(self, add_indices):
+        """MythTracer::RemoveTriangles: the triangles `add_indices` (add_triangle / .obj order, each at most once) deleted
+        from the host scene; the survivors keep their order and are numbered densely.  At most once, and before any
+        add_triangles, since the last upload or update: the indices are the uploaded scene's.  RuntimeError with the
+        facade's message otherwise, or for a bad index; nothing is removed then."""
+        a = np.ascontiguousarray(add_indices, dtype=np.int32).reshape(-1)
+        if not self.L.mth_remove_triangles(self.h, a.ctypes.data if a.size else None, int(a.size)):
+            raise RuntimeError("remove_triangles failed: " + self.last_error())
+
+    def update_triangles_in_place(self):
+        """MythTracer::UpdateTrianglesInPlace: after remove_triangles / add_triangles, the uploaded scenes take the batch
+        in place (mt_scene_edit_triangles): the tree is built again on the GPU with the new count, the device arrays are
+        re-ordered, and materials, textures, lights, tuning and cost history stay.  update_triangle_materials,
+        update_triangle_attributes, set_triangle_vertices and flatten() speak the new count and order afterwards.  With
+        nothing uploaded yet it is update_geometry() and prepare().  The RayTrees of this object belong to the old
+        geometry: they are closed first.  RuntimeError with the message when the facade or a device refuses; after a
+        device's refusal every device scene is dropped and the next prepare uploads the host's state anew."""
+        for ref in getattr(self, "_trees", []):
+            t = ref()
+            if t is not None:
+                t.close()
+        self._trees = []
+        if not self.L.mth_update_triangles_in_place(self.h):
+            raise RuntimeError("update_triangles_in_place failed: " + self.last_error())
 
     def set_raytree_keep_triangles(self, keep: bool):
         """MythTracer::SetRayTreeKeepTriangles: RayTrees built from now on keep the triangle each ray hit."""

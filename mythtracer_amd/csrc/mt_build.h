@@ -289,4 +289,91 @@ __global__ __launch_bounds__(kBuildThreads) void move_regather_kernel(MoveArrays
   }
 }
 
+// ---- triangles added and removed in place (mt_scene_edit_triangles): the COUNT changes, so the add order is numbered
+// anew -- the survivors densely in their old relative order, then the added triangles -- and a triangle's attributes
+// come from one of two sources.
+//   edit_mark_kernel      a thread per listed remove index: keep[a] = 0 over a plane preset to 1
+//   [rocPRIM exclusive scan of keep -> new_add: integer addition; its total is the survivor count n_keep]
+//   edit_stage_kernel     a thread per OLD stream position q: a kept triangle's live vertices to staged[new_add[a]] and
+//                         src[new_add[a]] = q; a thread per added triangle j: staged[n_keep + j], src[n_keep + j] = ~j
+//   [the build above, from the staging array, with the new count]
+//   edit_regather_kernel  a thread per NEW stream position p: everything of triangle a' = new_tri_id[p] into new arrays,
+//                         the attributes from the old arrays at src[a'] or from the uploaded add arrays at ~src[a']
+// src is preset to kEditNoSource, which is neither a position nor a ~j: a thread that meets it writes nothing.  As in the
+// move kernels every index read from memory is checked against its bound before it is used, and no thread writes a place
+// that another thread writes (remove indices are listed at most once and all write the same 0).
+
+constexpr int32_t kEditNoSource = INT32_MIN;
+
+__global__ __launch_bounds__(kBuildThreads) void edit_mark_kernel(const int32_t *__restrict__ remove_idx, uint32_t n_remove,
+                                                                   uint32_t n_old, int32_t *__restrict__ keep) {
+  const uint32_t i = blockIdx.x * kBuildThreads + threadIdx.x;
+  if (i >= n_remove) return;
+  const uint32_t a = (uint32_t)remove_idx[i];
+  if (a >= n_old) return;
+  keep[a] = 0;
+}
+
+// threads 0 .. n_old - 1: the old stream positions; threads n_old .. n_old + n_add - 1: the added triangles.  staged and
+// src have room for n_keep + n_add triangles.
+__global__ __launch_bounds__(kBuildThreads) void edit_stage_kernel(const double *__restrict__ live_vertex,
+                                                                    const int32_t *__restrict__ old_tri_id,
+                                                                    const int32_t *__restrict__ keep,
+                                                                    const int32_t *__restrict__ new_add, uint32_t n_old,
+                                                                    uint32_t n_keep, const double *__restrict__ add_vertex,
+                                                                    uint32_t n_add, double *__restrict__ staged,
+                                                                    int32_t *__restrict__ src) {
+  const unsigned long long t = (unsigned long long)blockIdx.x * kBuildThreads + threadIdx.x;
+  if (t < n_old) {
+    const uint32_t q = (uint32_t)t;
+    const uint32_t a = (uint32_t)old_tri_id[q];
+    if (a >= n_old || keep[a] == 0) return;
+    const uint32_t to = (uint32_t)new_add[a];
+    if (to >= n_keep) return;
+    for (int k = 0; k < 9; k++) staged[(size_t)to * 9 + k] = live_vertex[(size_t)q * 9 + k];
+    src[to] = (int32_t)q;
+  } else if (t - n_old < n_add) {
+    const uint32_t j = (uint32_t)(t - n_old);
+    const size_t to = (size_t)n_keep + j;
+    for (int k = 0; k < 9; k++) staged[to * 9 + k] = add_vertex[(size_t)j * 9 + k];
+    src[to] = ~(int32_t)j;
+  }
+}
+
+// the added triangles' attributes as the caller gave them, on the device, in the order given
+struct EditAdds {
+  const double *normal, *uvw;  // 9, 9 per triangle
+  const int32_t *mtl, *line;
+};
+
+// was: the old arrays, n_old triangles (read); add: the added triangles' attributes, n_add of them (read); now: the new
+// arrays, n triangles (written; now.aabb has room for n boxes).  staged, box_add, src: in the NEW add order.
+__global__ __launch_bounds__(kBuildThreads) void edit_regather_kernel(MoveArrays was, EditAdds add, MoveArrays now,
+                                                                       const double *__restrict__ staged,
+                                                                       const double *__restrict__ box_add,
+                                                                       const int32_t *__restrict__ new_tri_id,
+                                                                       const int32_t *__restrict__ src, uint32_t n,
+                                                                       uint32_t n_old, uint32_t n_add) {
+  const uint32_t p = blockIdx.x * kBuildThreads + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t a = (uint32_t)new_tri_id[p];
+  if (a >= n) return;
+  const int32_t from = src[a];
+  const bool added = from < 0;
+  const uint32_t at = added ? (uint32_t)~from : (uint32_t)from;  // (kEditNoSource: 2^31 - 1, below no count)
+  if (at >= (added ? n_add : n_old)) return;
+  const double *normal = added ? add.normal : was.normal, *uvw = added ? add.uvw : was.uvw;
+  for (int k = 0; k < 9; k++) {
+    now.vertex[(size_t)p * 9 + k] = staged[(size_t)a * 9 + k];
+    now.normal[(size_t)p * 9 + k] = normal[(size_t)at * 9 + k];
+    now.uvw[(size_t)p * 9 + k] = uvw[(size_t)at * 9 + k];
+  }
+  for (int k = 0; k < 6; k++) now.aabb[(size_t)p * 6 + k] = box_add[(size_t)a * 6 + k];
+  now.mtl[p] = added ? add.mtl[at] : was.mtl[at];
+  now.line[p] = added ? add.line[at] : was.line[at];
+  for (int w = 0; w < 2; w++) {
+    if (now.stamp[w] != nullptr) now.stamp[w][p] = added ? 0u : was.stamp[w][at];
+  }
+}
+
 }  // namespace mt

@@ -35,6 +35,7 @@
 #include "mt_layout.h"
 #include "mt_host_tree.h"
 #include "mt_move.h"
+#include "mt_edit.h"
 
 using namespace mt;
 
@@ -395,8 +396,9 @@ struct mt_scene {
   Buf<uint32_t> d_attr_stamp[2];
   std::vector<uint32_t> attr_stamp_host[2];
   uint32_t attr_generation[2] = {0, 0};
-  // mt_scene_set_triangle_vertices: how often the geometry has changed since mt_scene_create (a ray tree of an older
-  // geometry is refused for good), and the wall times of the last set's parts (mt_scene_move_times_last)
+  // mt_scene_set_triangle_vertices, mt_scene_edit_triangles: how often the geometry has changed since mt_scene_create (a
+  // ray tree of an older geometry is refused for good), and the wall times of the last move's or edit's parts
+  // (mt_scene_move_times_last)
   unsigned long long geo_generation = 0;
   bool tri_id_checked = false;  // tri_id_host was found to be a permutation (the first set; a move keeps it one)
   double move_ms[MT_MOVE_TIMES] = {};
@@ -4575,22 +4577,37 @@ int mt_scene_read_tree(const mt_scene *s, mt_octree_arrays *out) {
   return MT_OK;
 }
 
-// ---- triangles moved in place (mt_build.h's move_* kernels, mt_move.h's bookkeeping) ---------------------------------
+// ---- triangles moved in place (mt_build.h's move_* kernels, mt_move.h's bookkeeping), and triangles added and removed
+// in place (its edit_* kernels, mt_edit.h's bookkeeping): one set of steps, a move being the edit that keeps the count --
 namespace {
 
 double ms_since(const std::chrono::steady_clock::time_point &t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// What the steps of a move hand on to one another.  Everything in it is built aside and frees itself: until move_swap
-// nothing of the scene is written, and a return leaves the scene exactly as it was.
+// What mt_scene_edit_triangles was given, for the steps that differ from a move's
+struct EditList {
+  const int32_t *remove_idx = nullptr;
+  int n_remove = 0, n_add = 0;
+  const double *add_vertex = nullptr, *add_normal = nullptr, *add_uvw = nullptr;
+  const int32_t *add_material = nullptr, *add_line_no = nullptr;
+};
+
+// What the steps of a move or an edit hand on to one another.  Everything in it is built aside and frees itself: until
+// move_swap nothing of the scene is written, and a return leaves the scene exactly as it was.
 struct Move {
-  int32_t n = 0;  // the scene's triangles
-  // 1. + 2. the vertices in add order with the listed ones written over them; add index -> old stream position; and the
-  // step's own inputs
+  int32_t n = 0;      // the triangles of the scene that is being built (a move: the scene's own count)
+  int32_t n_old = 0;  // the scene's triangles
+  const EditList *edit = nullptr;  // an edit's lists; NULL: a move
+  // 1. + 2. the vertices in (the new) add order; a move: add index -> old stream position, an edit: new add index -> old
+  // stream position or ~(added triangle) (d_old_pos for both); and the step's own inputs
   Buf<double> d_stage, d_listed;
   Buf<int32_t> d_old_pos, d_old_id, d_idx;
   Buf<unsigned int> d_changed;
+  // an edit's: the keep plane and its scan, the added triangles' attributes
+  Buf<int32_t> d_keep, d_new_add, d_add_mtl, d_add_line;
+  Buf<double> d_add_normal, d_add_uvw;
+  Buf<char> d_scan_temp;
   // 3.
   std::unique_ptr<mt_octree, void (*)(mt_octree *)> tree{nullptr, mt_octree_destroy};
   // 4. the scene's next `geo` and `tri`, the boxes in stream order, the scene's next stamp planes and tri_id
@@ -4629,6 +4646,53 @@ int move_stage(const mt_scene *s, const int32_t *add_idx, int n_idx, const doubl
   HIP_TRY(launch_flat(move_overwrite_kernel, ni, stream, (const int32_t *)M.d_idx.p, (const double *)M.d_listed.p, (uint32_t)n_idx,
                       (uint32_t)M.n, M.d_stage.p, M.d_changed.p));
   HIP_TRY(hipMemcpyAsync(changed, M.d_changed, sizeof *changed, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return MT_OK;
+}
+
+// 1. + 2. of an edit: the survivors' live vertices in the new add order, the added triangles behind them, and every new
+// add index's source (mt_build.h).  The scan's total is held to the host's own count.
+int edit_stage(const mt_scene *s, Move &M) {
+  const EditList &E = *M.edit;
+  const size_t n_old = (size_t)M.n_old, nt = (size_t)M.n, nr = (size_t)E.n_remove, na = (size_t)E.n_add;
+  const int32_t n_keep = M.n_old - E.n_remove;
+  const hipStream_t stream = nullptr;
+  MT_TRY(build_room(M.d_stage, nt * 9, "the staged vertices"));
+  MT_TRY(build_room(M.d_old_pos, nt, "the triangles' sources"));
+  MT_TRY(build_room(M.d_old_id, n_old, "the old tri_id"));
+  MT_TRY(build_room(M.d_keep, n_old, "the keep plane"));
+  MT_TRY(build_room(M.d_new_add, n_old, "the new add indices"));
+  HIP_TRY(hipMemcpyAsync(M.d_old_id, s->tri_id_host.data(), n_old * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)M.d_keep.p, 1, n_old, stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)M.d_old_pos.p, kEditNoSource, nt, stream));
+  if (nr > 0) {
+    MT_TRY(build_room(M.d_idx, nr, "the remove list"));
+    HIP_TRY(hipMemcpyAsync(M.d_idx, E.remove_idx, nr * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch_flat(edit_mark_kernel, nr, stream, (const int32_t *)M.d_idx.p, (uint32_t)nr, (uint32_t)n_old, M.d_keep.p));
+  }
+  if (na > 0) {
+    MT_TRY(build_room(M.d_listed, na * 9, "the added vertices"));
+    MT_TRY(build_room(M.d_add_normal, na * 9, "the added normals"));
+    MT_TRY(build_room(M.d_add_uvw, na * 9, "the added uvw"));
+    MT_TRY(build_room(M.d_add_mtl, na, "the added materials"));
+    MT_TRY(build_room(M.d_add_line, na, "the added line numbers"));
+    HIP_TRY(hipMemcpyAsync(M.d_listed, E.add_vertex, na * 72, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(M.d_add_normal, E.add_normal, na * 72, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(M.d_add_uvw, E.add_uvw, na * 72, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(M.d_add_mtl, E.add_material, na * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(M.d_add_line, E.add_line_no, na * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  }
+  MT_TRY(build_scan(M.d_scan_temp, (const int32_t *)M.d_keep.p, M.d_new_add.p, n_old, stream));
+  int32_t last[2] = {0, 0};  // the survivors before the last old add index; whether that one is kept
+  HIP_TRY(hipMemcpyAsync(&last[0], M.d_new_add.p + (n_old - 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&last[1], M.d_keep.p + (n_old - 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if ((long long)last[0] + last[1] != (long long)n_keep) {
+    return fail(MT_ERR_INTERNAL, "the keep plane sums to %lld survivors, the lists to %d", (long long)last[0] + last[1], n_keep);
+  }
+  HIP_TRY(launch_flat(edit_stage_kernel, n_old + na, stream, s->dev.tri_vertex, (const int32_t *)M.d_old_id.p,
+                      (const int32_t *)M.d_keep.p, (const int32_t *)M.d_new_add.p, (uint32_t)n_old, (uint32_t)n_keep,
+                      (const double *)M.d_listed.p, (uint32_t)na, M.d_stage.p, M.d_old_pos.p));
   HIP_TRY(hipStreamSynchronize(stream));
   return MT_OK;
 }
@@ -4672,8 +4736,15 @@ int move_regather(const mt_scene *s, Move &M) {
     MT_TRY(build_room(M.d_tri_id, nt, "the scene's tri_id"));
     HIP_TRY(hipMemcpyAsync(M.d_tri_id, tree->d_tri_id, nt * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
   }
-  HIP_TRY(launch_flat(move_regather_kernel, nt, stream, was, now, (const double *)M.d_stage.p, (const double *)tree->d_tri_aabb.p,
-                      (const int32_t *)tree->d_tri_id.p, (const int32_t *)M.d_old_pos.p, (uint32_t)M.n));
+  if (M.edit != nullptr) {
+    const EditAdds add{M.d_add_normal, M.d_add_uvw, M.d_add_mtl, M.d_add_line};
+    HIP_TRY(launch_flat(edit_regather_kernel, nt, stream, was, add, now, (const double *)M.d_stage.p,
+                        (const double *)tree->d_tri_aabb.p, (const int32_t *)tree->d_tri_id.p, (const int32_t *)M.d_old_pos.p,
+                        (uint32_t)M.n, (uint32_t)M.n_old, (uint32_t)M.edit->n_add));
+  } else {
+    HIP_TRY(launch_flat(move_regather_kernel, nt, stream, was, now, (const double *)M.d_stage.p, (const double *)tree->d_tri_aabb.p,
+                        (const int32_t *)tree->d_tri_id.p, (const int32_t *)M.d_old_pos.p, (uint32_t)M.n));
+  }
   HIP_TRY(hipStreamSynchronize(stream));
   return MT_OK;
 }
@@ -4693,9 +4764,12 @@ int move_readback(Move &M) {
 int move_derive(const mt_scene *s, Move &M) {
   std::vector<int32_t> from;
   MoveError merr;
-  if (!move_mirrors(s->tri_id_host, M.host.tri_id.data(), *s->tri_mtl_host, s->attr_stamp_host, &M.mirrors, &from, &merr)) {
-    return fail(merr);
-  }
+  const bool made =
+      M.edit != nullptr
+          ? edit_mirrors(s->tri_id_host, M.edit->remove_idx, (size_t)M.edit->n_remove, (size_t)M.edit->n_add, M.edit->add_material,
+                         M.host.tri_id.data(), (size_t)M.n, *s->tri_mtl_host, s->attr_stamp_host, &M.mirrors, &from, &merr)
+          : move_mirrors(s->tri_id_host, M.host.tri_id.data(), *s->tri_mtl_host, s->attr_stamp_host, &M.mirrors, &from, &merr);
+  if (!made) return fail(merr);
   M.tri_mtl = std::make_shared<const std::vector<int32_t>>(std::move(M.mirrors.tri_mtl));  // (trees hold the old one)
   // The description of the new scene as mt_scene_create would get it.  check_scene_desc and derive_layout read the node
   // arrays, tri_vertex, tri_aabb, tri_material and the material / texture tables; of tri_normal, tri_uvw, tri_line_no
@@ -4723,12 +4797,15 @@ int move_derive(const mt_scene *s, Move &M) {
   return MT_OK;
 }
 
-// 6.: the swap.  M.dev, the live DevScene with the derived arrays of M.geo, gets the rest of the moved scene.  The
+// 6.: the swap.  M.dev, the live DevScene with the derived arrays of M.geo, gets the rest of the moved scene: its
+// per-triangle arrays, and the counts with what is computed from them (the packed stack's shift here; the engine gate
+// reads dev.n_tris at every launch; the G-buffer's d_tri_id, where allocated, was made for the new count).  The
 // launch configuration depends on the tree (deep layout, LDS bytes, packed stack): if it cannot be made, the old scene
 // and its configuration come back.  After it nothing fails, and the scene takes what was built aside: M keeps what the
 // scene gives up.
 int move_swap(mt_scene *s, Move &M) {
   show_tri_arrays(M.tri, &M.dev);
+  M.dev.n_tris = M.n;
   M.dev.n_nodes = M.host.n_nodes;
   M.dev.pack_shift = s->tune.v[MT_TUNE_PACKED_STACK] != 0.0 ? pack_shift_for(M.n, M.host.n_nodes) : 0;
   const DevScene dev_was = s->dev;
@@ -4756,16 +4833,23 @@ int move_swap(mt_scene *s, Move &M) {
   return MT_OK;
 }
 
-// Steps 1 .. 6 of mt_scene_set_triangle_vertices for a checked list of n_idx >= 1 triangles
-int move_triangles(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, mt_build_info *info) {
+// Steps 1 .. 6 of mt_scene_set_triangle_vertices for a checked list of n_idx >= 1 triangles, and of
+// mt_scene_edit_triangles for checked lists that are not both empty (edit != NULL)
+int move_triangles(mt_scene *s, const int32_t *add_idx, int n_idx, const double *vertices, const EditList *edit, mt_build_info *info) {
   const auto w0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());  // no kernel of an earlier call reads the scene while it is taken apart
   Move M;
-  M.n = s->dev.n_tris;
-  unsigned int changed = 0;
-  MT_TRY(move_stage(s, add_idx, n_idx, vertices, M, &changed));
-  if (changed == 0) return MT_OK;  // the listed vertices are the live ones, bit for bit
+  M.n_old = s->dev.n_tris;
+  M.n = edit != nullptr ? M.n_old - edit->n_remove + edit->n_add : M.n_old;
+  M.edit = edit;
+  if (edit != nullptr) {
+    MT_TRY(edit_stage(s, M));
+  } else {
+    unsigned int changed = 0;
+    MT_TRY(move_stage(s, add_idx, n_idx, vertices, M, &changed));
+    if (changed == 0) return MT_OK;  // the listed vertices are the live ones, bit for bit
+  }
   double part_ms[MT_MOVE_TIMES] = {};
   auto t0 = std::chrono::steady_clock::now();
   const auto lap = [&](int part) {
@@ -4808,9 +4892,39 @@ int mt_scene_set_triangle_vertices(mt_scene *s, const int32_t *add_idx, int n_id
     s->tri_id_checked = true;
   }
   try {
-    return move_triangles(s, add_idx, n_idx, vertices, info);
+    return move_triangles(s, add_idx, n_idx, vertices, nullptr, info);
   } catch (const std::bad_alloc &) {
     return fail(MT_ERR_NOMEM, "no host memory for the moved scene's arrays");
+  }
+}
+
+int mt_scene_edit_triangles(mt_scene *s, const int32_t *remove_idx, int n_remove, int n_add, const double *add_vertex,
+                            const double *add_normal, const double *add_uvw, const int32_t *add_material,
+                            const int32_t *add_line_no, mt_build_info *info) {
+  if (!s) return fail(MT_ERR_ARG, "scene is NULL");
+  MoveError err;
+  EditAdd add;
+  add.n = n_add;
+  add.vertex = add_vertex;
+  add.normal = add_normal;
+  add.uvw = add_uvw;
+  add.material = add_material;
+  add.line_no = add_line_no;
+  try {
+    if (!check_edit_args(s->have_tri_id, s->dev.n_tris, remove_idx, n_remove, add, s->n_materials, &err)) return fail(err);
+    if (info) memset(info, 0, sizeof *info);
+    if (n_remove == 0 && n_add == 0) return MT_OK;
+    if (!s->tri_id_checked) {  // (as for a move: the kernels scatter through a tri_id that was the caller's)
+      std::vector<int32_t> from;
+      if (!compose_move(s->tri_id_host.data(), s->tri_id_host.data(), s->tri_id_host.size(), &from, &err)) {
+        return fail(MT_ERR_ARG, "the scene's tri_id is no permutation of its triangles: %s", err.msg.c_str());
+      }
+      s->tri_id_checked = true;
+    }
+    const EditList edit{remove_idx, n_remove, n_add, add_vertex, add_normal, add_uvw, add_material, add_line_no};
+    return move_triangles(s, nullptr, 0, nullptr, &edit, info);
+  } catch (const std::bad_alloc &) {
+    return fail(MT_ERR_NOMEM, "no host memory for the edited scene's arrays");
   }
 }
 

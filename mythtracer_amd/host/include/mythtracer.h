@@ -262,7 +262,8 @@ class MythTracer {
   // moved through it) go to every device replica, which builds the tree again on its GPU and re-orders its arrays, and
   // the host tree adopts the new flat tree from the first replica.  UpdateTriangleMaterials, UpdateTriangleAttributes
   // and flatten() speak the new order afterwards; the scene stays finalized and uploaded.  With nothing uploaded yet it
-  // is UpdateGeometry() followed by Prepare().  False with LastError() set when a device refuses (no memory, a tree
+  // is UpdateGeometry() followed by Prepare().  Refused with a message while a batch of AddTriangle / RemoveTriangles
+  // is pending (UpdateTrianglesInPlace() first).  False with LastError() set when a device refuses (no memory, a tree
   // deeper than MT_MAX_TREE_DEPTH): that device's scene is as it was, and neither the host builder nor a new upload
   // is used instead.  With one device the facade is then exactly as before the call.  With several, the first device
   // moves first and the host tree adopts its tree at once, so the host's stream order is always the first device's; a
@@ -272,6 +273,34 @@ class MythTracer {
   // UpdateGeometry's rule: destroy or Reset them BEFORE the call (a tree of the old geometry is refused by every call
   // that shades or updates it).
   bool UpdateGeometryInPlace();
+  // ADDING and REMOVING triangles of an uploaded scene, in place (mt_scene_edit_triangles): an object that appears in
+  // a session or leaves it.  AddTriangle takes ownership and appends the triangle (Triangle::CacheAABB is the
+  // caller's, as for AddPrimitive): it gets the last add index.  RemoveTriangles deletes the listed triangles (LoadObj /
+  // AddPrimitive indices, each at most once); the survivors keep their relative order and are numbered densely.  Only
+  // the host scene changes: UpdateTrianglesInPlace() must follow before the scene is used again.  ONE pending batch at a
+  // time: since the last upload or update RemoveTriangles may be called at most once and only before any AddTriangle,
+  // so that its indices are the uploaded scene's; anything else is refused with a message that says to update first.
+  // SetTriangleVertices is refused while a batch is pending, and so are UpdateGeometryInPlace, UpdateTriangleMaterials
+  // and UpdateTriangleAttributes, whose numbering and stream order the batch has left behind; AddTriangle (the triangle
+  // is deleted then) and RemoveTriangles are refused while triangles moved by SetTriangleVertices await
+  // UpdateGeometryInPlace(), whose indices a batch would renumber.  So moves and a batch are never pending together.
+  // While a batch is pending on an uploaded scene the flat tree describes the old triangles: flatten() and the tree's
+  // dump refuse too.
+  bool AddTriangle(Triangle* triangle);
+  bool RemoveTriangles(const std::vector<int>& add_indices);
+  // The pending batch to every device replica: the root box is recomputed on the host, the first replica removes and
+  // adds the triangles in place -- it keeps its materials, textures (nothing of them is uploaded again), lights, tuning,
+  // engine and cost history --, the host tree adopts that replica's new flat tree, and the other replicas follow.
+  // UpdateTriangleMaterials, UpdateTriangleAttributes, SetTriangleVertices and flatten() speak the new count and order
+  // afterwards.  With nothing uploaded yet it is UpdateGeometry() followed by Prepare(), whatever is pending, moved
+  // vertices included; with nothing pending it does nothing.  Refused with a message, before any device call and with the batch still pending, when triangles moved by
+  // SetTriangleVertices await UpdateGeometryInPlace(), or when an added triangle points at a material that was not
+  // uploaded (the call adds no material: UpdateGeometry() uploads such a batch).  An edit is not idempotent and the host
+  // scene cannot go back, so a device that refuses (no memory, a tree deeper than MT_MAX_TREE_DEPTH, an edit that
+  // leaves no triangle) must not leave host and replicas in a mixed state: ALL device scenes are dropped and the
+  // scene is marked unfinalized, as by UpdateGeometry(); false with LastError() set, and the next Prepare() uploads the
+  // host's state anew.  RayTree objects follow UpdateGeometry's rule: destroy or Reset them BEFORE the call.
+  bool UpdateTrianglesInPlace();
   // RayTrees built from now on also keep the triangle each ray hit (mt_scene_set_raytree_tri): 4 bytes more per ray,
   // and UpdateRayTreeMaterials / RegrowRayTree then take an UpdateTriangleMaterials, which they refuse for a tree
   // without.  Off by default; independent of SetRayTreeKeepUVW (a reassignment TO a textured material needs both).
@@ -334,6 +363,14 @@ class MythTracer {
   bool keep_uvw_ = false;                                  // SetRayTreeKeepUVW
   bool keep_tri_ = false;                                  // SetRayTreeKeepTriangles
   std::vector<int> moved_;                                 // SetTriangleVertices' indices since the last upload or update
+  // the pending batch of AddTriangle / RemoveTriangles: the removed indices (of the uploaded scene), whether
+  // RemoveTriangles was called, the number of triangles appended since (they are the host tree's last ones)
+  std::vector<int32_t> removed_;
+  bool removal_pending_ = false;
+  size_t added_ = 0;
+  bool EditPending() const { return removal_pending_ || added_ > 0; }
+  void ForgetEdit();
+  void HostOnlyEdit();
   int max_level_ = MAX_RECURSION_LEVEL;
   int supersampling_ = 1;
   int adaptive_ss_ = 1, adaptive_threshold_ = 16;

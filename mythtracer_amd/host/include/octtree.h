@@ -48,6 +48,9 @@ class OctTree {
   // Builds the tree.  Prints "Triangles: N" like the reference.
   void Finalize();
   bool IsFinalized() const { return finalized_; }
+  // extension: AppendPrimitive / RemovePrimitives changed the triangle set of a finalized tree, and Flat() still
+  // describes the old one (its tri_id may name triangles that are gone): nothing may read it until Adopt() or Refit()
+  bool FlatIsStale() const { return flat_is_stale_; }
   // extension: Finalize() builds the tree on the GPU (mt_octree_build on the device of SetDevice) instead of on the
   // host: the same FlatTree, bit for bit.  Off by default.  When it is on and the build fails -- no GPU, no memory, a
   // tree deeper than MT_MAX_TREE_DEPTH -- Finalize() leaves the tree unfinalized with the reason in LastError(): it
@@ -63,6 +66,15 @@ class OctTree {
   // leaves the tree as it is; Adopt takes `flat` as the finalized tree, as Finalize does under SetDeviceBuild.
   void RefitRoot();
   void Adopt(FlatTree flat);
+  // extension, for a triangle SET that changes after Finalize() while the tree is rebuilt elsewhere
+  // (mt_scene_edit_triangles on the uploaded scene).  AppendPrimitive is AddPrimitive -- it takes ownership, Triangle
+  // only, the root box extended -- but allowed after Finalize(); the triangle gets the last add index.
+  // RemovePrimitives deletes the listed triangles (add indices, each at most once; false with LastError() and nothing
+  // removed otherwise); the survivors keep their relative order and are numbered densely, and the root box is
+  // recomputed.  Both leave the flat tree as it is, in the manner of RefitRoot: on a finalized tree it then describes
+  // the OLD triangle set, and IntersectRay(s) refuses, until Adopt() or Refit() + Finalize().
+  void AppendPrimitive(Primitive* p);
+  bool RemovePrimitives(const std::vector<int>& add_indices);
   // A flat tree through `read` (mt_octree_read of a tree, mt_scene_read_tree of a scene: MT_OK or an error code): a
   // first read with no array wanted gives the counts, a second fills the arrays.  The code of a failed read, else 0.
   static int ReadFlat(const std::function<int(mt_octree_arrays*)>& read, FlatTree* out);
@@ -99,9 +111,11 @@ class OctTree {
   std::vector<std::unique_ptr<Primitive>> prims_;
   FlatTree flat_;
   bool finalized_ = false;
+  bool flat_is_stale_ = false;  // AppendPrimitive / RemovePrimitives after Finalize(): flat_ awaits Adopt() or Refit()
   bool quiet_ = false;
   bool device_build_ = false;
   bool FinalizeOnDevice();
+  void DropGeometryOnly();
   int device_ = 0;
   mutable mt_scene* geometry_only_ = nullptr;  // for standalone IntersectRay
   mutable std::string error_;

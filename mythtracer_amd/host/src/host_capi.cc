@@ -149,15 +149,24 @@ void mth_tree_info(void* p, int* n_nodes, int* n_tris, int* depth) {
   *depth = tree.Flat().depth;
 }
 
-void mth_tree_dump(void* p, double* aabb, double* center, int32_t* first_child, int32_t* prim_begin,
-                   int32_t* prim_count, int32_t* prim_ids) {
-  const raytracer::FlatTree& f = static_cast<Handle*>(p)->mt.GetScene()->tree.Flat();
+// 0, with a message and nothing written, while the flat tree describes another triangle set than the scene holds
+// (MythTracer::AddTriangle / RemoveTriangles before UpdateTrianglesInPlace): the arrays were sized by mth_tree_info
+int mth_tree_dump(void* p, double* aabb, double* center, int32_t* first_child, int32_t* prim_begin,
+                  int32_t* prim_count, int32_t* prim_ids) {
+  Handle* h = static_cast<Handle*>(p);
+  if (h->mt.GetScene()->tree.FlatIsStale()) {
+    h->shim_error = "triangles were added or removed and the tree still describes the old ones: "
+                    "UpdateTrianglesInPlace() first";
+    return 0;
+  }
+  const raytracer::FlatTree& f = h->mt.GetScene()->tree.Flat();
   memcpy(aabb, f.node_aabb.data(), f.node_aabb.size() * 8);
   memcpy(center, f.node_center.data(), f.node_center.size() * 8);
   memcpy(first_child, f.first_child.data(), f.first_child.size() * 4);
   memcpy(prim_begin, f.prim_begin.data(), f.prim_begin.size() * 4);
   memcpy(prim_count, f.prim_count.data(), f.prim_count.size() * 4);
   memcpy(prim_ids, f.tri_id.data(), f.tri_id.size() * 4);
+  return 1;
 }
 
 // vertex(9) normal(9) uvw(9) aabb(6) per triangle in AddPrimitive order;
@@ -190,6 +199,7 @@ int mth_flatten(void* p, int* n_tris, int* n_materials, int* n_textures, double*
   raytracer::FlatScene f;
   if (!f.Build(*scene)) {
     h->error = f.error;
+    h->shim_error = f.error;  // (mth_last_error reports the shim's own refusals through it)
     return 0;
   }
   *n_tris = (int)f.material.size();
@@ -680,6 +690,57 @@ void mth_update_geometry(void* p) { static_cast<Handle*>(p)->mt.UpdateGeometry()
 
 // MythTracer::UpdateGeometryInPlace; 0 with the facade's message when a device refuses
 int mth_update_geometry_in_place(void* p) { return static_cast<Handle*>(p)->mt.UpdateGeometryInPlace() ? 1 : 0; }
+
+// MythTracer::AddTriangle for n triangles: vertices (n x 9), normals and uvw (n x 9, or NULL for the Triangle's defaults),
+// all with the scene's material `material` (NULL: none), line numbers (n, or NULL for 0).  0 with a message, and no
+// triangle added, for an unknown material name or a bad list.
+int mth_add_triangles(void* p, int n, const double* v, const double* nrm, const double* uvw, const char* material,
+                      const int32_t* line_no) {
+  Handle* h = static_cast<Handle*>(p);
+  auto* scene = h->mt.GetScene();
+  Material* m = nullptr;
+  if (material != nullptr) {
+    auto it = scene->materials.find(material);
+    if (it == scene->materials.end()) {
+      h->shim_error = std::string("no material named ") + material;
+      return 0;
+    }
+    m = it->second.get();
+  }
+  if (n < 0 || (n > 0 && v == nullptr)) {
+    h->shim_error = "bad triangle list";
+    return 0;
+  }
+  h->shim_error.clear();
+  for (int i = 0; i < n; i++) {
+    Triangle* t = new Triangle();
+    for (int k = 0; k < 3; k++) {
+      const size_t at = (size_t)i * 9 + (size_t)k * 3;
+      t->vertex[k] = {v[at], v[at + 1], v[at + 2]};
+      if (nrm) t->normal[k] = {nrm[at], nrm[at + 1], nrm[at + 2]};
+      if (uvw) t->uvw[k] = {uvw[at], uvw[at + 1], uvw[at + 2]};
+    }
+    t->mtl = m;
+    t->debug_line_no = line_no ? line_no[i] : 0;
+    t->CacheAABB();
+    if (!h->mt.AddTriangle(t)) return 0;
+  }
+  return 1;
+}
+
+// MythTracer::RemoveTriangles
+int mth_remove_triangles(void* p, const int32_t* add_indices, int n) {
+  Handle* h = static_cast<Handle*>(p);
+  if (n < 0 || (n > 0 && add_indices == nullptr)) {
+    h->shim_error = "bad triangle index list";
+    return 0;
+  }
+  h->shim_error.clear();
+  return h->mt.RemoveTriangles(std::vector<int>(add_indices, add_indices + n)) ? 1 : 0;
+}
+
+// MythTracer::UpdateTrianglesInPlace; 0 with the facade's message when it or a device refuses
+int mth_update_triangles_in_place(void* p) { return static_cast<Handle*>(p)->mt.UpdateTrianglesInPlace() ? 1 : 0; }
 
 // MythTracer::SetRayTreeKeepTriangles
 void mth_set_raytree_keep_triangles(void* p, int keep) { static_cast<Handle*>(p)->mt.SetRayTreeKeepTriangles(keep != 0); }

@@ -72,6 +72,10 @@ bool FlatScene::Build(const Scene& scene) {
     error = "scene tree is not finalized";
     return false;
   }
+  if (tree.FlatIsStale()) {
+    error = "triangles were added or removed and the tree still describes the old ones: UpdateTrianglesInPlace() first";
+    return false;
+  }
   const FlatTree& f = tree.Flat();
   const size_t nt = f.tri_id.size();
 
@@ -227,7 +231,14 @@ bool MythTracer::Prepare() {
   uploaded_textures_ = flat.texture_of;
   uploaded_materials_ = flat.material_of;
   moved_.clear();  // (the upload took every vertex as it is)
+  ForgetEdit();    // (... and every triangle)
   return true;
+}
+
+void MythTracer::ForgetEdit() {
+  removed_.clear();
+  removal_pending_ = false;
+  added_ = 0;
 }
 
 bool MythTracer::SetTriangleVertices(const std::vector<int>& add_indices, const std::vector<V3D>& vertices) {
@@ -236,6 +247,9 @@ bool MythTracer::SetTriangleVertices(const std::vector<int>& add_indices, const 
     fprintf(stderr, "error: %s\n", error_.c_str());
     return false;
   };
+  if (EditPending()) {
+    return refuse("triangles were added or removed and the edit is pending: UpdateTrianglesInPlace() first");
+  }
   if (vertices.size() != add_indices.size() * 3) {
     return refuse(std::to_string(add_indices.size()) + " triangles need " + std::to_string(add_indices.size() * 3) +
                   " vertices, not " + std::to_string(vertices.size()));
@@ -259,7 +273,119 @@ void MythTracer::UpdateGeometry() {
   scene.tree.Refit();
   was_scene_finalized = false;
   moved_.clear();
+  ForgetEdit();
   DropDeviceScenes();
+}
+
+bool MythTracer::AddTriangle(Triangle* triangle) {
+  if (triangle == nullptr) {
+    error_ = "AddTriangle: the triangle is NULL";
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  }
+  if (!moved_.empty()) {  // (their indices are the uploaded scene's, like a removal's)
+    error_ = "triangles moved by SetTriangleVertices are pending: UpdateGeometryInPlace() first";
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    delete triangle;
+    return false;
+  }
+  scene.tree.AppendPrimitive(triangle);
+  added_++;
+  HostOnlyEdit();
+  return true;
+}
+
+// With nothing uploaded there is no scene to edit in place: the tree is built again by the next Prepare.
+void MythTracer::HostOnlyEdit() {
+  if (dev_ != nullptr) return;
+  if (scene.tree.IsFinalized()) scene.tree.Refit();
+  was_scene_finalized = false;
+}
+
+bool MythTracer::RemoveTriangles(const std::vector<int>& add_indices) {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (!moved_.empty()) {  // (a removal renumbers the triangles that the moved indices name)
+    return refuse("triangles moved by SetTriangleVertices are pending: UpdateGeometryInPlace() first");
+  }
+  if (removal_pending_) {
+    return refuse("RemoveTriangles was called already since the last upload or update: UpdateTrianglesInPlace() first");
+  }
+  if (added_ > 0) {
+    return refuse("triangles were added since the last upload or update, so the indices would not be the uploaded "
+                  "scene's: UpdateTrianglesInPlace() first");
+  }
+  if (!scene.tree.RemovePrimitives(add_indices)) return refuse(scene.tree.LastError());
+  removed_.assign(add_indices.begin(), add_indices.end());
+  removal_pending_ = true;
+  HostOnlyEdit();
+  return true;
+}
+
+bool MythTracer::UpdateTrianglesInPlace() {
+  auto refuse = [&](const std::string& why) {
+    error_ = why;
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  };
+  if (!was_scene_finalized || dev_ == nullptr) {  // nothing uploaded yet: the upload takes the triangles as they are
+    UpdateGeometry();
+    return Prepare();
+  }
+  if (!moved_.empty()) {
+    return refuse("triangles moved by SetTriangleVertices are pending: UpdateGeometryInPlace() first");
+  }
+  if (!EditPending()) return true;
+  // the added triangles: the host tree's last ones, their materials through the uploaded dense table
+  const size_t nt = scene.tree.PrimitiveCount(), na = added_;
+  std::unordered_map<const Material*, int32_t> index;
+  for (size_t i = 0; i < uploaded_materials_.size(); i++) index[uploaded_materials_[i]] = (int32_t)i;
+  std::vector<double> vertex(na * 9), normal(na * 9), uvw(na * 9);
+  std::vector<int32_t> material(na), line_no(na);
+  for (size_t j = 0; j < na; j++) {
+    const Triangle* t = scene.tree.GetTriangle(nt - na + j);
+    memcpy(&vertex[j * 9], t->vertex, 72);
+    memcpy(&normal[j * 9], t->normal, 72);
+    memcpy(&uvw[j * 9], t->uvw, 72);
+    line_no[j] = t->debug_line_no;
+    material[j] = -1;
+    if (t->mtl != nullptr) {
+      const auto it = index.find(t->mtl);
+      if (it == index.end()) {
+        return refuse("added triangle " + std::to_string(nt - na + j) + " points at a material that was not uploaded: "
+                      "UpdateTrianglesInPlace adds no material (UpdateGeometry() uploads the scene anew)");
+      }
+      material[j] = it->second;
+    }
+  }
+  // From here on a refusal leaves no replica behind the host: everything is dropped and uploaded anew by the next Prepare.
+  auto give_up = [&](const std::string& why) {
+    const std::string text = why + mt_last_error();
+    UpdateGeometry();
+    return refuse(text);
+  };
+  scene.tree.RefitRoot();
+  std::vector<mt_scene*> all(1, dev_);
+  all.insert(all.end(), replicas_.begin(), replicas_.end());
+  for (size_t r = 0; r < all.size(); r++) {
+    if (mt_scene_edit_triangles(all[r], removed_.data(), (int)removed_.size(), (int)na, vertex.data(), normal.data(), uvw.data(),
+                                material.data(), line_no.data(), nullptr) != MT_OK) {
+      return give_up(r == 0 ? "editing the triangles in place failed: " : "editing the triangles in place failed on a replica: ");
+    }
+    if (r == 0) {  // at once its new tree: the host tree speaks the order dev_ speaks
+      FlatTree f;
+      mt_scene* const first = dev_;
+      if (OctTree::ReadFlat([first](mt_octree_arrays* a) { return mt_scene_read_tree(first, a); }, &f) != MT_OK) {
+        return give_up("reading the edited tree failed: ");
+      }
+      scene.tree.Adopt(std::move(f));
+    }
+  }
+  ForgetEdit();
+  return true;
 }
 
 bool MythTracer::UpdateGeometryInPlace() {
@@ -272,6 +398,9 @@ bool MythTracer::UpdateGeometryInPlace() {
     fprintf(stderr, "error: %s\n", error_.c_str());
     return false;
   };
+  if (EditPending()) {  // (the host's triangles are numbered anew already; the devices' are not)
+    return refuse("triangles were added or removed and the edit is pending: UpdateTrianglesInPlace() first");
+  }
   scene.tree.RefitRoot();
   // the moved triangles, each once (all of them when the caller edited MutableTriangle(i)->vertex itself)
   const size_t nt = scene.tree.PrimitiveCount();
@@ -317,6 +446,7 @@ bool MythTracer::UpdateTriangleMaterials() {
     return false;
   };
   if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes them as they are
+  if (EditPending()) return refuse("triangles were added or removed and the edit is pending: UpdateTrianglesInPlace() first");
   // FlatScene::Build's stream order, through the uploaded dense table
   const FlatTree& f = scene.tree.Flat();
   std::unordered_map<const Material*, int32_t> index;
@@ -347,6 +477,11 @@ bool MythTracer::UpdateTriangleMaterials() {
 
 bool MythTracer::UpdateTriangleAttributes() {
   if (!was_scene_finalized || dev_ == nullptr) return Prepare();  // nothing uploaded yet: the upload takes them as they are
+  if (EditPending()) {
+    error_ = "triangles were added or removed and the edit is pending: UpdateTrianglesInPlace() first";
+    fprintf(stderr, "error: %s\n", error_.c_str());
+    return false;
+  }
   // FlatScene::Build's stream order
   const FlatTree& f = scene.tree.Flat();
   const size_t nt = f.tri_id.size();

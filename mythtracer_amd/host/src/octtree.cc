@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "mythtracer_hip.h"
 #include "primitive_triangle.h"
@@ -30,6 +31,47 @@ void OctTree::AddPrimitive(Primitive* p) {
   }
   prims_.emplace_back(p);
   root_aabb_.Extend(p->GetAABB());  // octtree.cc:12-13
+}
+
+void OctTree::AppendPrimitive(Primitive* p) {
+  if (dynamic_cast<Triangle*>(p) == nullptr) {
+    fprintf(stderr, "error: OctTree::AppendPrimitive: only Triangle primitives are supported\n");
+    delete p;
+    return;
+  }
+  prims_.emplace_back(p);
+  root_aabb_.Extend(p->GetAABB());
+  DropGeometryOnly();
+  flat_is_stale_ = finalized_;
+}
+
+bool OctTree::RemovePrimitives(const std::vector<int>& add_indices) {
+  std::vector<bool> gone(prims_.size(), false);
+  for (int i : add_indices) {
+    if (i < 0 || (size_t)i >= prims_.size() || gone[(size_t)i]) {
+      error_ = "OctTree::RemovePrimitives: index " + std::to_string(i) +
+               (i < 0 || (size_t)i >= prims_.size() ? " outside the tree's " + std::to_string(prims_.size()) + " triangles"
+                                                    : std::string(" is listed twice"));
+      return false;
+    }
+    gone[(size_t)i] = true;
+  }
+  if (add_indices.empty()) return true;
+  size_t kept = 0;
+  for (size_t i = 0; i < prims_.size(); i++) {
+    if (!gone[i]) prims_[kept++] = std::move(prims_[i]);
+  }
+  prims_.resize(kept);
+  root_aabb_ = AABB();
+  for (const auto& p : prims_) root_aabb_.Extend(p->GetAABB());
+  DropGeometryOnly();
+  flat_is_stale_ = finalized_;
+  return true;
+}
+
+void OctTree::DropGeometryOnly() {
+  if (geometry_only_) mt_scene_destroy(geometry_only_);
+  geometry_only_ = nullptr;
 }
 
 AABB OctTree::GetAABB() const { return root_aabb_; }
@@ -70,21 +112,21 @@ void OctTree::Refit() {
   root_aabb_ = AABB();
   for (const auto& p : prims_) root_aabb_.Extend(p->GetAABB());
   finalized_ = false;
+  flat_is_stale_ = false;
   flat_ = FlatTree();
-  if (geometry_only_) mt_scene_destroy(geometry_only_);
-  geometry_only_ = nullptr;
+  DropGeometryOnly();
 }
 
 void OctTree::RefitRoot() {
   root_aabb_ = AABB();
   for (const auto& p : prims_) root_aabb_.Extend(p->GetAABB());
-  if (geometry_only_) mt_scene_destroy(geometry_only_);
-  geometry_only_ = nullptr;
+  DropGeometryOnly();
 }
 
 void OctTree::Adopt(FlatTree flat) {
   flat_ = std::move(flat);
   finalized_ = true;
+  flat_is_stale_ = false;
 }
 
 // flat_ from mt_octree_build + mt_octree_read on device_; false with error_ set, and flat_ empty, when the build fails
@@ -219,6 +261,10 @@ bool OctTree::IntersectRays(int n, const double* rays, const Primitive** prims, 
                             double* points) const {
   if (!finalized_) {
     error_ = "OctTree::IntersectRays before Finalize";
+    return false;
+  }
+  if (flat_is_stale_) {
+    error_ = "OctTree::IntersectRays: triangles were appended or removed after Finalize; the tree awaits Adopt or Refit";
     return false;
   }
   if (geometry_only_ == nullptr) {
